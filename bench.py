@@ -2,6 +2,7 @@
 """Benchmark of the hot path: Soft-Truncation training step of the NCSN++/DDPM++ score network.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed step's results as DIR/*.npy)
 
 One "step" = one call of ``losses.get_step_fn(...)(state, batch)`` -- time sampling, perturbation,
 score-network forward and backward on the HIP engine, gradient all-reduce (N > 1), clip + Adam, EMA --
@@ -159,6 +160,8 @@ def parse():
                   help='side file with everything the stdout line leaves out (per-kernel tables, workloads, sampler, probes)')
   ap.add_argument('--force-exchange', action='store_true',
                   help='N = 1: run the WHOLE benchmark (the reported value too) with the exchange forced on')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)')
   return ap.parse_args()
 
 
@@ -565,6 +568,30 @@ def short_line(out, workload, detail_path=None):
   return text
 
 
+DUMP_SAMPLE = 1 << 20      # parameter entries kept per dumped vector (4 MB in float32)
+
+
+def dump_outputs(path, losses_, state):
+  """--dump-outputs: what the step function handed its caller in the LAST timed step, as float32 .npy files under `path`:
+  losses.npy (the per-sample losses it returned), params.npy / ema.npy (the model's parameters and the EMA's shadow copy it
+  left in `state`; of more than DUMP_SAMPLE entries, the same seeded sample of positions, in position order).  Weights, batch
+  and noise are seeded, so two builds run with the same arguments can be compared file by file.  Rank 0's losses only."""
+  os.makedirs(path, exist_ok=True)
+
+  def sample(name, tensors):
+    with torch.no_grad():
+      flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+      n = flat.numel()
+      if n > DUMP_SAMPLE:
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique()
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, f'{name}.npy'), flat.cpu().numpy().astype(np.float32))
+
+  np.save(os.path.join(path, 'losses.npy'), losses_.detach().cpu().numpy().astype(np.float32))
+  sample('params', list(state['model'].parameters()))
+  sample('ema', list(state['ema'].shadow_params))
+
+
 def write_detail(out, path):
   """Everything the run measured, full precision, per-kernel tables included -- the file the stdout line names in `detail`."""
   try:
@@ -825,6 +852,8 @@ def main():
     losses_ = step_fn(state, batch)
   sync()
   elapsed = time.perf_counter() - t0
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, losses_, state)     # now: the steps below reuse the loss buffer and move the weights
   proxy = None
   if world == 1 and not args.no_exchange_proxy and not args.force_exchange:
     try:

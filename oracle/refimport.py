@@ -5,8 +5,7 @@ absent third-party modules are stubbed.  This module perf
 stubbing and returns the reference's modules so that
 
 * tools/make_golden.py can generate the fixtures under tests/golden/ (inputs + the reference's
-  outputs), and
-* tests/test_ref_live.py can compare the restatements with the live reference when it is present.
+  outputs, including the reference's side of tests/test_ref_live.py in ref_live.{json,npz}).
 
 Nothing here travels anywhere: /root/reference does not exist on the GPU box, so every user of
 this module must be skipped when ``available()`` is False.  No reference source is copied.

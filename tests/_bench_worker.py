@@ -2,7 +2,8 @@
 tensors, the oracle's C restatement injected as the engine's library, a fixture-size net in place of the 61.8 M-parameter one.
 Only bench.py's four seams are replaced (device_of, init_group, device_sync, build_training) -- argument parsing, seeding, the
 sharded batch, priming / warm-up / timed steps between barriers, the MAX over ranks, the global images/s and the emitted stdout
-line are bench.py's own code.  RANK / WORLD_SIZE / MASTER_* come from the environment, as under torch.distributed.run."""
+line are bench.py's own code.  RANK / WORLD_SIZE / MASTER_* come from the environment, as under torch.distributed.run; BENCH_STEPS
+(default 3) and BENCH_DUMP (a --dump-outputs directory) from the test."""
 import os
 import sys
 
@@ -52,12 +53,15 @@ def main():
   calls = []
   real_all_reduce = dist.all_reduce
   dist.all_reduce = lambda *a, **k: (calls.append(a[0].numel()), real_all_reduce(*a, **k))[1]
-  sys.argv = ['bench.py', '--gpus', os.environ['WORLD_SIZE'], '--steps', '3', '--warmup', '1', '--no-kernel-timer',
+  steps = int(os.environ.get('BENCH_STEPS', '3'))
+  sys.argv = ['bench.py', '--gpus', os.environ['WORLD_SIZE'], '--steps', str(steps), '--warmup', '1', '--no-kernel-timer',
               '--detail', os.environ['BENCH_DETAIL']]
+  if os.environ.get('BENCH_DUMP'):
+    sys.argv += ['--dump-outputs', os.environ['BENCH_DUMP']]
   bench.main()
   # the gradient exchange really ran in every step: more all-reduces than the one MAX over the elapsed times
   print(f'rank {os.environ["RANK"]}: {len(calls)} all-reduces', file=sys.stderr)
-  assert len(calls) >= 1 + (2 + 1 + 3), calls
+  assert len(calls) >= 1 + (2 + 1 + steps), calls
 
 
 if __name__ == '__main__':

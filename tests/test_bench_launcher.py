@@ -32,10 +32,8 @@ def test_bench_single_process_stays_single():
   assert rec['n_gpus'] == 1 and rec['ranks_counted'] == 1
 
 
-@pytest.mark.timeout(600)
-def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
-  """bench.py's real main() at WORLD_SIZE = 2 through to the emitted stdout line, on the CPU checker over gloo
-  (tests/_bench_worker.py replaces four seams only): n_gpus = 2, value = GLOBAL images/s, the line is short and alone."""
+def _two_rank_bench(tmp_path, **env_extra):
+  """tests/_bench_worker.py as ranks 0 and 1 over gloo; returns their (stdout, stderr) after checking both exited 0."""
   import socket
   s = socket.socket()
   s.bind(('127.0.0.1', 0))
@@ -44,7 +42,7 @@ def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
   subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle')])
   base = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
   base.update(WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), BENCH_DETAIL=str(tmp_path / 'detail.json'),
-              STK_POISON='1')
+              STK_POISON='1', **env_extra)
   procs = []
   for rank in range(2):
     env = dict(base, RANK=str(rank), LOCAL_RANK=str(rank))
@@ -53,6 +51,14 @@ def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
   outs = [p.communicate(timeout=560) for p in procs]
   for p, (so, se) in zip(procs, outs):
     assert p.returncode == 0, se[-3000:]
+  return outs
+
+
+@pytest.mark.timeout(600)
+def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
+  """bench.py's real main() at WORLD_SIZE = 2 through to the emitted stdout line, on the CPU checker over gloo
+  (tests/_bench_worker.py replaces four seams only): n_gpus = 2, value = GLOBAL images/s, the line is short and alone."""
+  outs = _two_rank_bench(tmp_path)
   assert outs[1][0] == '', outs[1][0]                       # only rank 0 writes to stdout
   stdout0 = outs[0][0]
   assert stdout0.count('\n') == 1 and len(stdout0) < 4000, stdout0
@@ -67,3 +73,26 @@ def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
   detail = json.load(open(line['detail']))
   assert detail['n_gpus'] == 2 and detail['value'] == pytest.approx(line['value'], rel=1e-3)
   assert len(outs[0][1]) < 4000, outs[0][1][-4000:]         # stderr stays short too (no progress bars, no tables)
+
+
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_is_repeatable(tmp_path):
+  """--dump-outputs DIR: the last timed step's losses and a fixed sample of the parameters and EMA it left, as float32 .npy
+  files, identical from run to run with the same arguments; --steps sets the timed steps and the line reports ms_per_step."""
+  import numpy as np
+  dumps = []
+  for run in range(2):
+    d = tmp_path / f'dump{run}'
+    outs = _two_rank_bench(tmp_path, BENCH_STEPS='2', BENCH_DUMP=str(d))
+    line = json.loads(outs[0][0])
+    assert line['steps'] == 2 and line['ms_per_step'] > 0
+    assert line['value'] == pytest.approx(8 * 1e3 / line['ms_per_step'], rel=1e-3)
+    dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+  a, b = dumps
+  assert set(a) == {'losses.npy', 'params.npy', 'ema.npy'}
+  assert sum(v.nbytes for v in a.values()) <= 64 << 20
+  assert a['losses.npy'].shape == (4,)                       # rank 0's per-GPU batch
+  for name, v in a.items():
+    assert v.dtype == np.float32 and np.isfinite(v).all(), name
+    assert np.array_equal(v, b[name]), name
+  assert not np.array_equal(a['params.npy'], a['ema.npy'])   # the EMA trails the weights

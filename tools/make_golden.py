@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE itself (its PyTorch CPU path, imported from
 /root/reference through oracle/refimport.py) on small seeded inputs.
 
-Run in the build container only (the reference never travels):   python tools/make_golden.py
+Run in the build container only (the reference never travels):   python tools/make_golden.py [samplers | ref_live]
 
 Every fixture is data: inputs (including every noise draw, made explicit) and the reference's outputs.
 No reference source is stored.  tests/test_oracle_golden.py then pins the restatements (sde_lib, losses,
@@ -16,9 +16,12 @@ for p in (ROOT, os.path.join(ROOT, 'oracle'), os.path.join(ROOT, 'tests')):
   if p not in sys.path:
     sys.path.insert(0, p)
 
+import json
+
 import numpy as np
 import torch
 
+import _ref_cases as rc
 import refimport
 from _model_util import patched_rng
 
@@ -286,11 +289,70 @@ def samplers_fixture(ns):
   np.savez_compressed(os.path.join(OUT, 'samplers.npz'), **out)
 
 
+def _jsonable(v):
+  return list(v) if isinstance(v, tuple) else v
+
+
+def ref_live_fixture(ns):
+  """The reference's side of every case of tests/test_ref_live.py (tests/_ref_cases.py): ref_live.json holds config values,
+  state_dict layouts and weight digests, ref_live.npz the network inputs and outputs."""
+  meta, arrays = {'configs': {}, 'full_size': {}}, {}
+  for name, (dotted, _) in sorted(rc.FULL.items()):
+    flat = rc.flatten(refimport.get_config(dotted))
+    flat.pop('device')
+    flat.pop('data.tfrecords_path', None)
+    meta['configs'][name] = {k: _jsonable(v) for k, v in flat.items()}
+    rcfg = refimport.get_config(dotted)
+    rmodel = ns.mutils.create_model(rcfg, ns.sde_lib.get_sde(rcfg, None))
+    meta['full_size'][name] = rc.layout(rmodel)
+    del rmodel
+
+  torch.manual_seed(0)
+  rcfg = rc.init_config(refimport.get_config(rc.VP))
+  meta['init'] = rc.digests(ns.mutils.create_model(rcfg, ns.sde_lib.get_sde(rcfg, None)).state_dict())
+
+  meta['activations'] = {}
+  for name in rc.ACTIVATIONS:
+    rcfg = rc.activation_config(refimport.get_config(rc.VP), name)
+    torch.manual_seed(0)
+    rmodel = ns.mutils.create_model(rcfg, ns.sde_lib.get_sde(rcfg, None))
+    g = torch.Generator().manual_seed(3)
+    rc.randomize_(rmodel, g)
+    meta['activations'][name] = rc.digests(rmodel.state_dict())
+    x = torch.randn(3, 3, 16, 16, generator=g)
+    t = torch.rand(3, generator=g) * 999
+    rmodel.eval()
+    with torch.no_grad():
+      want = rmodel(x, t)
+    arrays.update({f'act_{name}_x': npy(x), f'act_{name}_t': npy(t), f'act_{name}_out': npy(want)})
+
+  rcfg = rc.cat_config(refimport.get_config(rc.VE_HQ))
+  torch.manual_seed(0)
+  rmodel = ns.mutils.create_model(rcfg, ns.sde_lib.get_sde(rcfg, None))
+  meta['cat_layout'] = rc.layout(rmodel)
+  g = torch.Generator().manual_seed(3)
+  rc.randomize_(rmodel, g)
+  meta['cat'] = rc.digests(rmodel.state_dict())
+  x = torch.rand(2, 3, 16, 16, generator=g)
+  sig = torch.rand(2, generator=g) * 5 + 0.1
+  rmodel.eval()
+  with torch.no_grad():
+    want = rmodel(x, sig)
+  arrays.update({'cat_x': npy(x), 'cat_sigma': npy(sig), 'cat_out': npy(want)})
+
+  with open(os.path.join(OUT, 'ref_live.json'), 'w') as f:
+    json.dump(meta, f, indent=0)
+    f.write('\n')
+  np.savez_compressed(os.path.join(OUT, 'ref_live.npz'), **arrays)
+
+
 def main():
   os.makedirs(OUT, exist_ok=True)
   ns = refimport.load()
   if len(sys.argv) > 1 and sys.argv[1] == 'samplers':
     return samplers_fixture(ns)
+  if len(sys.argv) > 1 and sys.argv[1] == 'ref_live':
+    return ref_live_fixture(ns)
   sde_fixture(ns)
   op_fixture(ns)
   for fam in FAMILIES:
@@ -298,6 +360,7 @@ def main():
   for fam in ('vp', 've'):
     likelihood_fixture(ns, fam)
   samplers_fixture(ns)
+  ref_live_fixture(ns)
   for f in sorted(os.listdir(OUT)):
     print(f, os.path.getsize(os.path.join(OUT, f)))
 
