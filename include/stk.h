@@ -244,7 +244,8 @@ int stk_conv2d_wgrad_f32(const float* x1, int C1, const float* x2, int C2, const
  * Results equal the fp32-input calls up to the position of the split (errors at the fp32 rounding level).
  * ------------------------------------------------------------------------------------------ */
 /* Scale record of a GroupNorm (+SiLU) (+dropout) output from its parameters alone: rec[0] = (max|gamma| sqrt(L - 1) +
- * max|beta|) / (1 - drop_p) >= |y| for ANY input (L = (C / G) HW elements per group), rec[1..255] = 0. */
+ * max|beta|) / (1 - drop_p) >= |y| for ANY input (L = (C / G) HW elements per group), rec[1..255] = 0.  sqrt(L - 1) is
+ * taken 2^-16 high so that the record also bounds the fp32 output, whose xhat may round above sqrt(L - 1). */
 int stk_gn_bound_f32(const float* gamma, const float* beta, int C, int G, int HW, float drop_p, float* rec, void* stream);
 /* GroupNorm forward whose output goes to plane consumers: stk_gn_fwd_f32 + stk_gn_bound_f32 (rec) +
  * stk_split_planes_f32 (planes) in one call -- and one pass over x for the shapes stk_gn_fwd_pl_fused reports (whole

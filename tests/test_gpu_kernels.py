@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from _tolerances import PL_DGRAD_RTOL, PL_FWD_RTOL, PL_WGRAD_RTOL
 from _util import call, close, dev_of, rnd
 
 pytestmark = pytest.mark.gpu
@@ -469,7 +470,17 @@ def test_conv(ref_lib, hip_lib, case, scratch):
     o['dbias_only'] = db2
     return o
 
-  compare(both(ref_lib, hip_lib, fn), 1e-4, 'conv')
+  outs = both(ref_lib, hip_lib, fn)
+  if scratch and hip_lib.is_device:
+    # outputs of the fp16 two-way-split kernels (stk_conv2d_variant 5) are held to the contraction bounds
+    split = [int(hip_lib.conv2d_variant(k, C1, C2, *dims, layout)) == 5 for k in (0, 1, 2)]
+    tight = {'y': PL_FWD_RTOL if split[0] else None, 'y_plain': PL_FWD_RTOL if split[0] else None,
+             'dx1': PL_DGRAD_RTOL if split[1] else None, 'dx2': PL_DGRAD_RTOL if split[1] else None,
+             'dw': PL_WGRAD_RTOL if split[2] else None}
+    for k, tol in tight.items():
+      if tol is not None and k in outs[0]:
+        close(outs[1][k], outs[0][k], rtol=tol, what=f'conv (split kernel):{k}')
+  compare(outs, 1e-4, 'conv')
 
 
 WP_CASES = [c for c in CONV_CASES if c[7] == 1 and c[3] == c[9] and c[4] == c[10]]
