@@ -19,6 +19,9 @@
 // split-K: each slice writes its partial tile to a scratch slab and a second kernel sums the slabs in a
 // fixed order into dw (deterministic -- no float atomics).
 #include "igemm.h"
+#include "stk_fp16.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -566,6 +569,11 @@ struct EpSlab {
     }
   }
 };
+// OneProduct<EP>: epilogue EP of the one-product forward kernels (include/stk_fp16.h; conv_x2.h / conv_x2d.h read it with
+// is_x1).  A type of its own, so that the fp16 kernels are instantiations with symbols of their own and the fp32 ones keep theirs.
+template <class EP> struct OneProduct : EP {};
+template <class EP> struct is_x1 { static constexpr bool value = false; };
+template <class EP> struct is_x1<OneProduct<EP>> { static constexpr bool value = true; };
 // sum of the split slabs in a fixed order, then the same epilogue arithmetic as EpFwd / EpDgrad.
 // VEC = 4 (H W % 4 == 0, 16-byte aligned tensors): four consecutive pixels of one image per thread -- 16-byte loads of the
 // `splits` slabs and of the residual, one 16-byte store (round 4: the scalar form spent 9 us on 33 MB).
@@ -1030,17 +1038,26 @@ inline void x3_weight_strides(const ConvP& p, int dgrad, long& sm, long& sk) {
   else { sm = dgrad ? p.Cout : 1; sk = dgrad ? 1 : p.Cout; }          // NIN w[Cin][Cout]
 }
 // wp_ready: weights already prepared by stk_conv2d_wprep_batch (then ws only holds the K-split slabs)
+// x1: the one-product forms (include/stk_fp16.h): hi(w) hi(x) only.  With planes a chunk then covers a PAIR of 32-channel
+// groups (conv_x2d.h), so the chunk count roughly halves; the plan keeps its number of K splits (and slab layout) unless the
+// halved count leaves some empty.
+inline X3Plan x1_plan(const X3Plan& r, int nch1) {
+  X3Plan r1 = r;
+  r1.chunks_per_split = (nch1 + r.splits - 1) / r.splits;
+  r1.splits = (nch1 + r1.chunks_per_split - 1) / r1.chunks_per_split;
+  return r1;
+}
 template <class EP>
-int launch_x3(ConvP p, const X3Plan& r, const float* s1, int S1, const float* s2, int S2, int M, long Ng, int dgrad,
+int launch_x3(ConvP p, const X3Plan& r0, const float* s1, int S1, const float* s2, int S2, int M, long Ng, int dgrad,
               void* ws, hipStream_t s, const void* wp_ready = nullptr, float* amax = nullptr,
-              const void* planes = nullptr, const float* planes_amax = nullptr, bool amax_valid = false) {
+              const void* planes = nullptr, const float* planes_amax = nullptr, bool amax_valid = false, bool x1 = false) {
   x3::Src q;
   q.s1 = s1; q.s2 = S2 > 0 ? s2 : s1; q.S1 = S1; q.S2 = S2; q.Kc = S1 + S2; q.Mpad = x3::pad128(M); q.taps = p.taps;
   q.pl = static_cast<const unsigned char*>(planes); q.pl_stride = planes ? pl::plane_bytes(p.N, S1, p.HW) : 0;
   unsigned short* wp = reinterpret_cast<unsigned short*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
   float* xpart = reinterpret_cast<float*>(((uintptr_t)wp + x3::wp_bytes(M, q.Kc, p.taps) + 255) & ~(uintptr_t)255);
   p.part = reinterpret_cast<float*>(((uintptr_t)(xpart + 2 * x2::NPART) + 255) & ~(uintptr_t)255);
-  p.part_stride = r.slab;
+  p.part_stride = r0.slab;
   {
     // fp16 two-way split (conv_x2.h): |x| maxima of the activation operand(s), weights prepared here unless the caller did
     // with a caller-owned amax buffer (768 floats: |x1|, |x2|, |dy| partials) the maxima stay available to the layer's
@@ -1068,13 +1085,36 @@ int launch_x3(ConvP p, const X3Plan& r, const float* s1, int S1, const float* s2
       STK_CHECK_LAUNCH();
       q.wp = wp;
     }
-    const int tm = q.Mpad / 128, tn = stk_cdiv((int)Ng, 128), nch = p.taps * (q.Kc / x3::KC);
+    const int tm = q.Mpad / 128, tn = stk_cdiv((int)Ng, 128);
+    const int nch = planes && x1 ? p.taps * ((q.Kc / x3::KC + 1) / 2) : p.taps * (q.Kc / x3::KC);
+    const X3Plan r = planes && x1 ? x1_plan(r0, nch) : r0;
+    // one-product kernels exist for the forward only: in the data-gradient instantiation STK_X1 / STK_X1L name the fp32
+    // kernels (that branch is never taken there), so no dead fp16 code is built
+    constexpr bool kFwd = std::is_same<EP, EpFwd>::value;
+    if (x1 && !kFwd) return STK_EINVAL;
+#define STK_X1(E) std::conditional_t<kFwd, OneProduct<E>, E>
+#define STK_X1L(DUAL, TAPS) std::conditional_t<kFwd, x2::ActLoader16<DUAL, TAPS>, x2::ActLoader<DUAL, TAPS>>
     const dim3 grid((unsigned)(tm * tn * r.splits));
 #define STK_X2_LAUNCH(E, DUAL, TAPS)                                                                              \
-  hipLaunchKernelGGL((x2::gemm_kernel<x2::ActLoader<DUAL, TAPS>, E>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, \
+  if (x1) hipLaunchKernelGGL((x2::gemm_kernel<STK_X1L(DUAL, TAPS), STK_X1(E)>), grid, dim3(256), 0, s, p, q, M, \
+                             (int)Ng, tm, tn, nch, r.chunks_per_split, xpart, nx);                                \
+  else hipLaunchKernelGGL((x2::gemm_kernel<x2::ActLoader<DUAL, TAPS>, E>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, \
                      nch, r.chunks_per_split, xpart, nx)
 #define STK_PL_LAUNCH(E, TAPS)                                                                                    \
-  if (x2d::halo_ok(p, TAPS, r.splits)) {                                                                          \
+  if (x1) {                                                                                                       \
+    /* one product, two channel groups per chunk (conv_x2d.h, X1) */                                              \
+    if (x2d::halo_ok(p, TAPS, r0.splits)) {                                                                       \
+      if (p.W == 64)                                                                                              \
+        hipLaunchKernelGGL((x2d::gemm_halo_kernel<64, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
+      else if (p.W == 32)                                                                                         \
+        hipLaunchKernelGGL((x2d::gemm_halo_kernel<32, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
+      else                                                                                                        \
+        hipLaunchKernelGGL((x2d::gemm_halo_kernel<16, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
+    } else {                                                                                                      \
+      hipLaunchKernelGGL((x2d::gemm_kernel<TAPS, 128, STK_X1(E)>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch, \
+                         r.chunks_per_split, xpart, nx);                                                          \
+    }                                                                                                             \
+  } else if (x2d::halo_ok(p, TAPS, r.splits)) {                                                                   \
     /* one halo tile of the activations per channel group serves the nine taps */                                 \
     if (p.W == 64)                                                                                                \
       hipLaunchKernelGGL((x2d::gemm_halo_kernel<64, E, 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
@@ -1091,7 +1131,7 @@ int launch_x3(ConvP p, const X3Plan& r, const float* s1, int S1, const float* s2
   if (planes) { if (p.taps == 9) { STK_PL_LAUNCH(E, 9); } else { STK_PL_LAUNCH(E, 1); } }                         \
   else if (p.taps == 9) { if (S2 > 0) STK_X2_LAUNCH(E, true, 9); else STK_X2_LAUNCH(E, false, 9); }               \
   else { if (S2 > 0) STK_X2_LAUNCH(E, true, 1); else STK_X2_LAUNCH(E, false, 1); }
-    if (r.splits == 1) {
+    if (r0.splits == 1) {
       STK_X2_LAUNCH_E(EP)
       STK_CHECK_LAUNCH();
       return STK_OK;
@@ -1102,6 +1142,8 @@ int launch_x3(ConvP p, const X3Plan& r, const float* s1, int S1, const float* s2
 #undef STK_X2_LAUNCH_E
 #undef STK_X2_LAUNCH
 #undef STK_PL_LAUNCH
+#undef STK_X1
+#undef STK_X1L
     STK_CHECK_LAUNCH();
     return STK_OK;
   }
@@ -1197,7 +1239,7 @@ extern "C" {
 static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
                     const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
                     float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                    const void* wp, float* amax, void* ws, long ws_bytes, void* stream, bool x_rec_valid);
+                    const void* wp, float* amax, void* ws, long ws_bytes, void* stream, bool x_rec_valid, bool f16x1 = false);
 
 int stk_conv2d_fwd_wp_f32(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
                           const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
@@ -1218,7 +1260,7 @@ int stk_conv2d_fwd_rec_f32(const float* x1, int C1, const float* x2, int C2, con
 static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
                     const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
                     float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                    const void* wp, float* amax, void* ws, long ws_bytes, void* stream, bool x_rec_valid) {
+                    const void* wp, float* amax, void* ws, long ws_bytes, void* stream, bool x_rec_valid, bool f16x1) {
   if (!x1 || !w || !y || (C2 > 0 && !x2) || out_div == 0.f || (w_layout != 0 && w_layout != 1) ||
       (w_layout == 1 && (KH != 1 || KW != 1)))
     return STK_EINVAL;
@@ -1251,7 +1293,7 @@ static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const floa
   }
   const X3Plan xr = x3_plan(p, p.Cin, C1, C2, Cout, Ng);
   if (ws && xr.ok && ws_bytes >= x3_ws_bytes(xr, Cout, p.Cin, p.taps))
-    return launch_x3<EpFwd>(p, xr, x1, C1, x2, C2, Cout, Ng, 0, ws, s, wp, amax, nullptr, nullptr, x_rec_valid);
+    return launch_x3<EpFwd>(p, xr, x1, C1, x2, C2, Cout, Ng, 0, ws, s, wp, amax, nullptr, nullptr, x_rec_valid, f16x1);
   if (wp) return STK_EINVAL;      // prepared weights exist only for the shapes stk_conv2d_wp_bytes reports
   if (p.taps == 9) {
     using CB = Cfg<128, 128, 36>; using CS = Cfg<64, 64, 36>;
@@ -1406,9 +1448,9 @@ int stk_conv2d_pl_ksplit(int dir, int C1, int C2, int N, int H, int W, int Cout,
   return dir == 0 ? x3_plan_pl(p, p.Cin, Cout, Ng).splits : x3_plan_pl(p, Cout, p.Cin, Ng).splits;
 }
 
-int stk_conv2d_fwd_pl_f32(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
-                          const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
-                          int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+static int fwd_pl_impl(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                       const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                       int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
   if (!xpl || !xamax || !w || !y || out_div == 0.f || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
     return STK_EINVAL;
   if (!stk_conv2d_pl_ok(0, C, 0, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
@@ -1419,7 +1461,37 @@ int stk_conv2d_fwd_pl_f32(const void* xpl, const float* xamax, int C, const floa
   const long Ng = (long)N * p.HW;
   const X3Plan xr = x3_plan_pl(p, C, Cout, Ng);
   if (!ws || ws_bytes < x3_ws_bytes(xr, Cout, C, p.taps)) return STK_EINVAL;
-  return launch_x3<EpFwd>(p, xr, nullptr, C, nullptr, 0, Cout, Ng, 0, ws, (hipStream_t)stream, wp, nullptr, xpl, xamax);
+  return launch_x3<EpFwd>(p, xr, nullptr, C, nullptr, 0, Cout, Ng, 0, ws, (hipStream_t)stream, wp, nullptr, xpl, xamax, false,
+                          f16x1);
+}
+int stk_conv2d_fwd_pl_f32(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                          const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                          int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
+                     ws_bytes, stream, false);
+}
+
+/* ---- include/stk_fp16.h: the one-product twins of the three forward entries -------------------------------------------- */
+int stk_conv2d_fwd_pl_f16x1(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                            const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                            int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
+                     ws_bytes, stream, true);
+}
+int stk_conv2d_fwd_wp_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                            const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                            float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                            const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, false, true);
+}
+int stk_conv2d_fwd_rec_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                             const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                             float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                             const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+  if (!amax) return STK_EINVAL;
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, true, true);
 }
 
 int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,

@@ -176,21 +176,25 @@ inline long wp_bytes(int M, int Kc, int taps) { return HEADER + 2L * taps * x3::
 
 // ---- loaders (same slicing contract as conv_x3.h: st(g) of a chunk precedes ld(g) of the next one) -------------------
 // 16 fp32 values of one LDS row -> two fp16 planes.  Slices 0..7 convert one pair each, 8..11 write one 16-byte piece.
-struct Split16 {
+// X1 (the one-product forward of include/stk_fp16.h): the hi plane only -- one rounding, no lo residual.
+template <bool X1>
+struct Split16X {
   unsigned pk[2][8];
   __device__ __forceinline__ void st(int g, const float (&r)[16], float s, unsigned char* tile, int row, int k0,
                                      unsigned okm = 0xffffu) {
     if (g < 8) {
       const float v0 = s * igemm::keep_if(r[2 * g], okm, 2 * g), v1 = s * igemm::keep_if(r[2 * g + 1], okm, 2 * g + 1);
       pk[0][g] = pack_h2(v0, v1);
-      pk[1][g] = pack_h2(lo_part(v0), lo_part(v1));
+      if (!X1) pk[1][g] = pack_h2(lo_part(v0), lo_part(v1));
     } else if (g < 12) {
       const int sp = (g - 8) >> 1, h = (g - 8) & 1;
+      if (X1 && sp) return;
       *reinterpret_cast<u32x4*>(tile + sp * PLANE + row * PITCH + k0 * 2 + h * 16) =
           u32x4{pk[sp][4 * h], pk[sp][4 * h + 1], pk[sp][4 * h + 2], pk[sp][4 * h + 3]};
     }
   }
 };
+using Split16 = Split16X<false>;
 
 struct WpLoader {        // four 16-byte pieces per chunk: split j>>1, row (tid>>2) + 64 (j&1), segment tid&3
   __amdgpu_buffer_rsrc_t rs; unsigned voff, plane2, chunk2; int row, seg;
@@ -213,11 +217,11 @@ struct WpLoader {        // four 16-byte pieces per chunk: split j>>1, row (tid>
 };
 
 // activations, lanes along pixels; a thread holds 16 channels of one tap-shifted pixel (x3::ActLoader's addressing)
-template <bool DUAL, int TAPS>
-struct ActLoader {
+template <bool DUAL, int TAPS, bool X1>
+struct ActLoaderT {
   __amdgpu_buffer_rsrc_t rs1, rs2;
   int nl, kg, tb1, tb2; unsigned mask; float scale;
-  float r[16]; Split16 sp;
+  float r[16]; Split16X<X1> sp;
   __device__ __forceinline__ void init(const ConvP& p, const x3::Src& q, int n0, int tid, float s) {
     nl = tid & 127;
     kg = __builtin_amdgcn_readfirstlane(tid >> 7);      // which 16 of the chunk's 32 channels
@@ -253,6 +257,8 @@ struct ActLoader {
   }
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp.st(g, r, scale, t, nl, kg * 16); }
 };
+template <bool DUAL, int TAPS> struct ActLoader : ActLoaderT<DUAL, TAPS, false> {};
+template <bool DUAL, int TAPS> struct ActLoader16 : ActLoaderT<DUAL, TAPS, true> {};     // hi plane only (OneProduct forward)
 
 // (Round 4, measured and dropped: a loader for the 1x1 layers that fetches 4 pixels x 4 channels per thread with 16-byte loads
 // instead of 16 four-byte ones -- what had made the per-tap weight gradient 30 % faster -- changes nothing here: 384 -> 128 at
@@ -260,11 +266,14 @@ struct ActLoader {
 // chunks in all, and the chunk time is the staging round trip of the fp32-operand pipeline, profiles/r04_experiments.txt.)
 // ---- the kernel: out tile 128 x 128, 4 waves of 64 x 64, chunks of 32 k; 12 MFMAs per 16-k step and wave -------------
 // Grid (XCD-remapped): one flat dimension of tiles x K-splits.  xpart: `nxpart` (256 / 512) partial |x| maxima.
+// X1 (EP = OneProduct<..>, include/stk_fp16.h): only the hi(w) hi(x) MFMAs of each half chunk (4 of 12) are issued, with an
+// ActLoader16 (no lo plane) as BL.
 template <class BL, class EP, int WPS = 2>       // WPS: waves per SIMD the register allocation must admit
 __global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                    int nchunks_total, int chunks_per_split, const float* __restrict__ xpart,
                                                    int nxpart) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+  constexpr bool X1 = is_x1<EP>::value;
   unsigned char* As = lds;
   unsigned char* Bs = lds + OPER;
   const int tid = threadIdx.x;
@@ -309,6 +318,7 @@ __global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, x3::Src q, int 
   // three products per tile, the two cross terms first; MFMA g: product g / 4, tile (g / 2) & 1, g & 1
   constexpr int SA[3] = {1, 0, 0}, SB[3] = {0, 1, 0};
 #define STK_X2_MFMA(G)                                                                                              \
+  if (!X1 || ((G) >> 2) == 2)                                                                                       \
   acc[((G) >> 1) & 1][(G) & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[((G) >> 1) & 1][SA[(G) >> 2]], b[(G) & 1][SB[(G) >> 2]], \
                                                                         acc[((G) >> 1) & 1][(G) & 1], 0, 0, 0);
 #pragma unroll

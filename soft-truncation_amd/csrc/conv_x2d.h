@@ -47,11 +47,16 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* 
 // 2 x 32 KB x 2 workgroups per CU = 128 KB of the 160 KB.
 // ABL (ablation, benchmarks only -- results are garbage unless 0): bit 0 stages B only for the first tap of a channel
 // group, bit 1 stages A only for the first chunk, bit 2 reads the operand fragments only in the first chunk.
+// X1 = EP is a OneProduct<..> epilogue (forward of the fp16 mode, include/stk_fp16.h): ONE product per element, hi(w) hi(x).
+// The LDS image stays as it is, but its two split slots hold split 0 of TWO consecutive 32-channel groups (2 cc, 2 cc + 1):
+// a chunk covers 64 k with the same DMA, barrier and fragment-read counts and issues 4 instead of 6 MFMAs per tile;
+// nchunks_total counts channel-group PAIRS.  An odd group count leaves the last pair's second slot to the dead-offset DMA of zeros.
 template <int TAPS, int TN, class EP, int NBUF = 1, int ABL = 0>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                       int nchunks_total, int chunks_per_split,
                                                       const float* __restrict__ xpart, int nxpart) {
   using G = Geo<TN>;
+  constexpr bool X1 = is_x1<EP>::value;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[G::LDS * NBUF];
   unsigned char* const As = lds;
   unsigned char* const Bs = lds + G::A_BYTES;
@@ -80,9 +85,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
   // B: planes [split][n][cb][pixel][32]; wave w stages rows (TN / 4) w .. + TN / 4 - 1 in blocks of 16
   const __amdgpu_buffer_rsrc_t b_rs = x3::make_rsrc(q.pl, 2L * q.pl_stride);
   const unsigned b_ps = (unsigned)q.pl_stride;
+  const int Cb = q.Kc >> 5;
   unsigned b_base[G::BBLK], b_mask[G::BBLK];
   {
-    const int Cb = q.Kc >> 5;
 #pragma unroll
     for (int jb = 0; jb < G::BBLK; ++jb) {
       const int n = n0 + (TN / 4) * wid + 16 * jb + (lane >> 2);
@@ -105,7 +110,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
     const unsigned a_soff = (unsigned)c * a_chunk2;
     unsigned char* const As = lds + buf * G::LDS;
     unsigned char* const Bs = As + G::A_BYTES;
-    if (!(ABL & 2) || c == c_begin) {
+    if (X1) {                                                             // slot s = split 0 of group 2 cc + s
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const unsigned dead = (2 * cc + s >= Cb) ? 0x80000000u : 0u;        // scalar: past the last group, zeros
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          dma16(a_rs, As + s * G::A_PLANE + (32 * wid + 16 * h) * 64, (a_voff + h * 1024u) | dead,
+                (unsigned)((2 * cc + s) * TAPS + tap) * a_chunk2);
+      }
+    } else if (!(ABL & 2) || c == c_begin) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -120,8 +134,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
       const unsigned dead = (((b_mask[jb] >> tap) & 1u) ^ 1u) << 31;      // halo / out-of-range rows: DMA of zeros
       const unsigned vo = (b_base[jb] + (unsigned)shift) | dead;
 #pragma unroll
-      for (int s = 0; s < 2; ++s)
-        dma16(b_rs, Bs + s * G::B_PLANE + ((TN / 4) * wid + 16 * jb) * 64, vo, b_soff + s * b_ps);
+      for (int s = 0; s < 2; ++s) {
+        if (X1)
+          dma16(b_rs, Bs + s * G::B_PLANE + ((TN / 4) * wid + 16 * jb) * 64, vo | (2 * cc + s >= Cb ? 0x80000000u : 0u),
+                (unsigned)(2 * cc + s) * (unsigned)p.HW * 64u);
+        else
+          dma16(b_rs, Bs + s * G::B_PLANE + ((TN / 4) * wid + 16 * jb) * 64, vo, b_soff + s * b_ps);
+      }
     }
   };
 
@@ -151,12 +170,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
       b[j][s] = *reinterpret_cast<const halfx8*>(b_rd + (OFF) + s * G::B_PLANE + j * 32 * 64 + (KO));      \
   }
 #define STK_D_FRAGS(KO) STK_D_FRAGS_AT(KO, 0)
-  // three products per tile, the two cross terms first (fixed accumulation order)
+  // three products per tile, the two cross terms first (fixed accumulation order); X1: slot 0 then slot 1 (two groups)
   constexpr int SA[3] = {1, 0, 0}, SB[3] = {0, 1, 0};
+  constexpr int NPR = X1 ? 2 : 3;
 #define STK_D_MFMAS                                                                                        \
-  _Pragma("unroll") for (int pr = 0; pr < 3; ++pr) _Pragma("unroll") for (int i = 0; i < 2; ++i)             \
+  _Pragma("unroll") for (int pr = 0; pr < NPR; ++pr) _Pragma("unroll") for (int i = 0; i < 2; ++i)           \
     _Pragma("unroll") for (int j = 0; j < G::NJ; ++j) {                                                     \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][SA[pr]], b[j][SB[pr]], acc[i][j], 0, 0, 0);   \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][X1 ? pr : SA[pr]], b[j][X1 ? pr : SB[pr]], acc[i][j], 0, 0, 0); \
     }
 
   halfx8 a[2][2], b[G::NJ][2];
@@ -224,10 +244,13 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
 // W = 16 / 32 / 64 are instantiated.  The template still carries the two forms that were measured slower and retired in round 6 --
 // NB = 2 (two B buffers, two workgroups per CU) and W = 128 (row strips for the 128- / 256-wide maps: 67 KB of LDS, 187.9 -> 203.1 us)
 // -- because they share all of the kernel's code paths but a few constants.
+// X1 (EP = OneProduct<..>): the one-product form of gemm_kernel above -- the halo tile's two split slots hold split 0 of
+// channel groups 2 cc and 2 cc + 1, and `ngroups` counts group PAIRS.
 template <int W, class EP, int NB>
 __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                            int ngroups, const float* __restrict__ xpart, int nxpart) {
   constexpr int TN = 128, R = TN / W, TP = W + 2, HR = (R + 2) * TP, NI = (HR + 15) / 16, HRP = NI * 16;
+  constexpr bool X1 = is_x1<EP>::value;
   constexpr int A_PLANE = 128 * 64, A_BYTES = 2 * A_PLANE, B_PLANE = HRP * 64, B_BYTES = 2 * B_PLANE;
   constexpr int NK = (NI + 3) / 4;                                        // B instructions per wave and plane
   static_assert(NB == 1 || 2 * NK <= 8, "the B pieces of a group are issued one per chunk over taps 0..7");
@@ -255,9 +278,9 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, i
   const __amdgpu_buffer_rsrc_t b_rs = x3::make_rsrc(q.pl, 2L * q.pl_stride);
   const unsigned b_ps = (unsigned)q.pl_stride;
   // halo tile rows of this lane: instruction i = wid + 4 k covers LDS rows 16 i .. 16 i + 15, lane -> row 16 i + lane / 4
+  const int Cb = q.Kc >> 5;
   unsigned b_voff[NK];
   {
-    const int Cb = q.Kc >> 5;
     const int b = n0 / p.HW, hw0 = n0 - b * p.HW, y0 = hw0 / p.W, x0 = hw0 - y0 * p.W;      // x0 = 0 unless the map is wider than a tile
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
@@ -269,6 +292,18 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, i
     }
   }
   auto stage_a = [&](int c) {
+    if (X1) {                                                             // chunk c = (group pair, tap)
+      const int cc = c / 9, tap = c - 9 * cc;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const unsigned dead = (2 * cc + s >= Cb) ? 0x80000000u : 0u;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          dma16(a_rs, As + s * A_PLANE + (32 * wid + 16 * h) * 64, (a_voff + h * 1024u) | dead,
+                (unsigned)((2 * cc + s) * 9 + tap) * a_chunk2);
+      }
+      return;
+    }
     const unsigned a_soff = (unsigned)c * a_chunk2;
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -279,6 +314,11 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, i
   // piece (k, s) of group cc's halo tile into B buffer `buf`; k is a compile-time constant at every call site
   auto stage_b = [&](int cc, int buf, int k, int s) {
     if (wid + 4 * k >= NI) return;                                        // wave-uniform
+    if (X1) {
+      dma16(b_rs, Bs + buf * B_BYTES + s * B_PLANE + (wid + 4 * k) * 1024, b_voff[k] | (2 * cc + s >= Cb ? 0x80000000u : 0u),
+            (unsigned)(2 * cc + s) * (unsigned)p.HW * 64u);
+      return;
+    }
     dma16(b_rs, Bs + buf * B_BYTES + s * B_PLANE + (wid + 4 * k) * 1024, b_voff[k],
           (unsigned)cc * (unsigned)p.HW * 64u + s * b_ps);
   };
@@ -309,10 +349,11 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, i
 
   halfx8 a[2][2], b[2][2];
   constexpr int SA[3] = {1, 0, 0}, SB[3] = {0, 1, 0};
+  constexpr int NPR = X1 ? 2 : 3;
 #define STK_H_MFMAS                                                                                        \
-  _Pragma("unroll") for (int pr = 0; pr < 3; ++pr) _Pragma("unroll") for (int i = 0; i < 2; ++i)             \
+  _Pragma("unroll") for (int pr = 0; pr < NPR; ++pr) _Pragma("unroll") for (int i = 0; i < 2; ++i)           \
     _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                         \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][SA[pr]], b[j][SB[pr]], acc[i][j], 0, 0, 0);   \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][X1 ? pr : SA[pr]], b[j][X1 ? pr : SB[pr]], acc[i][j], 0, 0, 0); \
     }
 #define STK_H_FRAGS(KA, KSEG)                                                                              \
   _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                          \

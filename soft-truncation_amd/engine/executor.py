@@ -14,6 +14,12 @@ network, the dropout seed, is read from device memory (``seed_dev`` of ``stk_gn_
 replay draws fresh masks.  ``STK_GRAPHS=0`` disables capture; attaching a kernel timer
 (events cannot be recorded inside a replay) does so too.
 
+Precision: ``with ex.precision('fp16'):`` runs the forward-only evaluations inside it on the one-product twins of the
+split convolutions (include/stk_fp16.h): hi(w) hi(x) with fp32 accumulation instead of the three products of the fp32
+path.  Programs (and so their hipGraph captures) are planned per precision; a forward that a backward may follow (grad
+mode, training) raises inside the block.  Everything else -- GroupNorm, resampling, attention, the thin-side and
+f32-input convolutions -- runs exactly as in fp32.
+
 Backend selection is explicit and never silent: the default backend is the HIP library
 (``engine.lib.load()``, raises if it is not built); a test may inject another implementation
 of include/stk.h (the oracle's CPU restatement) with ``set_backend``.
@@ -63,6 +69,15 @@ class _GnFoldDesc(ctypes.Structure):       # StkGnFoldDesc of include/stk.h
 _LIB_ONLY = os.environ.get('STK_LIB_ONLY', '1' if _POISON else '0') == '1'
 # STK_WP_SIDE=0: the data-gradient weight blocks are prepared in front of the forward with the forward blocks (A/B switch)
 _WP_SIDE = os.environ.get('STK_WP_SIDE', '1') != '0'
+
+PRECISIONS = ('fp32', 'fp16')
+
+
+def check_precision(precision):
+  """'fp32' / 'fp16', else ValueError."""
+  if precision not in PRECISIONS:
+    raise ValueError(f'precision must be one of {PRECISIONS}, got {precision!r}')
+  return precision
 
 from torch.utils._python_dispatch import TorchDispatchMode
 
@@ -421,6 +436,22 @@ class Executor:
     # (training.mixed, the reconstruction term: losses.py:134-164, 295-320) runs one engine backward per evaluation inside
     # ONE .backward(); buckets may only leave with the last of them.
     self._awaiting = weakref.WeakSet()
+    self.mode = 'fp32'       # precision of forward-only evaluations (Executor.precision)
+
+  @contextlib.contextmanager
+  def precision(self, precision):
+    """Evaluate forward-only programs in `precision` inside the block ('fp32' = the default path, bit for bit; 'fp16' =
+    the one-product convolutions of include/stk_fp16.h).  Raises ValueError for an unknown precision, StkMissingError
+    when 'fp16' is asked of a library without the fp16 entries (there is no silent fp32 fallback)."""
+    check_precision(precision)
+    if precision == 'fp16' and not getattr(self.lib, 'has_fp16', False):
+      raise stk_lib.StkMissingError(f'backend {self.lib.backend} ({self.lib.path}) does not export include/stk_fp16.h: '
+                                    f'no fp16 mode')
+    saved, self.mode = self.mode, precision
+    try:
+      yield self
+    finally:
+      self.mode = saved
 
   # -- parameters ---------------------------------------------------------------------------------
   def set_backend(self, backend):
@@ -454,11 +485,13 @@ class Executor:
     return True
 
   # -- programs -----------------------------------------------------------------------------------
-  def program(self, B, H, W, need_xgrad):
-    key = (B, H, W, need_xgrad)
+  def program(self, B, H, W, need_xgrad, precision='fp32'):
+    # fp16 programs are keyed apart: their own contexts, their own hipGraph captures (the fp32 keys stay as they were)
+    key = (B, H, W, need_xgrad) if precision == 'fp32' else (B, H, W, need_xgrad, precision)
     prog = self.programs.get(key)
     if prog is None:
       g = Graph(self.flat, self.lib)
+      g.precision = precision
       out = self.model._emit(g, B, H, W, need_xgrad)
       g.finalize(out, self.lib)
       prog = self.programs[key] = Program(g, self.flat.device)
@@ -530,6 +563,7 @@ class Executor:
                  prog.ws.data_ptr(), prog.graph.ws_bytes, training, seed, seed_dev)
     rt.prof = self.profiler
     rt.with_backward = with_backward
+    rt.f16 = prog.graph.precision == 'fp16'
     if self.use_wp and prog.wp is not None and prog.wp_table is not None:
       rt.wp = prog.wp.data_ptr()
     if c.pl is not None:
@@ -590,7 +624,10 @@ class Executor:
 
   def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat):
     B, _, H, W = x.shape
-    prog = self.program(B, H, W, need_xgrad)
+    if self.mode != 'fp32' and (with_backward or need_xgrad or training):
+      raise ValueError(f'precision {self.mode!r} is for forward-only evaluation (sampling): a forward that a backward may '
+                       f'follow (grad mode, need_xgrad, training) runs in fp32 only')
+    prog = self.program(B, H, W, need_xgrad, self.mode)
     c = prog.acquire()
     g = prog.graph
     self._copy_in(c, 'x', x)

@@ -86,6 +86,7 @@ class Runtime:
     self.seed_dev = seed_dev
     self.wp = 0           # base address of the program's prepared-weight arena (0: every conv prepares per call)
     self.with_backward = True   # False: a no-grad evaluation (nothing is kept for a backward pass)
+    self.f16 = False            # fp16 mode (Executor.precision): split-form convolutions call their one-product twins
     self.pl = 0           # base address of the context's planes arena (pre-split conv operands)
     self.dypl = 0         # ... and of its scratch for the planes of the gradient a data-gradient call consumes
     self.prof = None      # optional engine.profile.KernelTimer: HIP events around the contraction launches
@@ -373,6 +374,11 @@ class Conv(Op):
   def _dims(self):
     return (self.N, self.H, self.W, self.Cout, self.OH, self.OW, self.KH, self.KW, self.stride, self.pad)
 
+  def f16_form(self, lib):
+    """True when this layer's forward is a split form, i.e. has a one-product twin (include/stk_fp16.h) in the fp16 mode;
+    the thin-side, f32-input-tile and strided forms run as in fp32."""
+    return self.pl_fwd or self._kind(lib, 'fwd').endswith('.x2')
+
   # prepared weights (include/stk.h "Prepared weights"): byte offsets of this layer's blocks in the program's arena,
   # assigned by Graph.finalize; None = this direction of this shape prepares nothing
   wp_off = (None, None)
@@ -465,17 +471,22 @@ class Conv(Op):
 
   def forward(self, rt):
     temb = rt.v(self.temb) + 4 * self.temb_col if self.temb is not None else None
+    f16 = rt.f16 and self.f16_form(rt.lib)
     if self.pl_fwd:
       t = self.x1
       if t.pl_maker is self:
         rt.make_planes(t)
-      rt.timed(self._label_pl(rt.lib, 'fwd'), self.flops, rt.lib.conv2d_fwd_pl_f32,
+      label = self._label_pl(rt.lib, 'fwd')
+      rt.timed(label + '.f16' if f16 else label, self.flops, rt.lib.conv2d_fwd_pl_f16x1 if f16 else rt.lib.conv2d_fwd_pl_f32,
                rt.planes(t), rt.rec(t), self.C1, rt.v(self.w), self.w_layout, rt.v(self.bias), temb, self.temb_stride,
                rt.v(self.res), self.out_div, rt.v(self.y), self.N, self.H, self.W, self.Cout, self.KH, self.KW,
                self._wp(rt, 0), rt.ws, rt.ws_bytes, rt.stream)
       return
-    rt.timed(self._kind(rt.lib, 'fwd'), self.flops,
-             rt.lib.conv2d_fwd_rec_f32 if self.x_from is not None else rt.lib.conv2d_fwd_wp_f32,
+    if f16:
+      fn = rt.lib.conv2d_fwd_rec_f16x1 if self.x_from is not None else rt.lib.conv2d_fwd_wp_f16x1
+    else:
+      fn = rt.lib.conv2d_fwd_rec_f32 if self.x_from is not None else rt.lib.conv2d_fwd_wp_f32
+    rt.timed(self._kind(rt.lib, 'fwd') + ('.f16' if f16 else ''), self.flops, fn,
              rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, rt.v(self.w), self.w_layout,
              rt.v(self.bias), temb, self.temb_stride, rt.v(self.res), self.out_div,
              rt.v(self.y), *self._dims(), self._wp(rt, 0), rt.v(self.amax), rt.ws, rt.ws_bytes, rt.stream)
@@ -1041,6 +1052,7 @@ class Graph:
   def __init__(self, flat, lib=None):
     self.flat = flat                  # engine.flat.FlatParams (parameter -> flat offset)
     self.lib = lib                    # the backend the plan is made for (ops may ask it which kernels take a shape)
+    self.precision = 'fp32'           # 'fp16': a forward-only program of the fp16 mode (Executor.program)
     self.ops = []
     self.tensors = []
     self.conv_amax = []               # the convolutions' 768-float amax buffers (offsets assigned by finalize)

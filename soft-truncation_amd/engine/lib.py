@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/stk.h.
+"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has it, include/stk_fp16.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -108,6 +108,13 @@ SIGNATURES = {
   'stk_samples_to_uint8': [P, P, I, I, L, S],
   'stk_preprocess_u8': [P, P, I, I, I, I, I, I, I, U64, S],
 }
+# include/stk_fp16.h: the one-product forward twins (fp16 mode).  Only the product library exports them; they are bound when
+# present and `StkLib.has_fp16` says whether they are.  Asking for the fp16 mode without them is an error (engine/executor.py).
+SIGNATURES_FP16 = {
+  'stk_conv2d_fwd_pl_f16x1': SIGNATURES['stk_conv2d_fwd_pl_f32'],
+  'stk_conv2d_fwd_rec_f16x1': SIGNATURES['stk_conv2d_fwd_rec_f32'],
+  'stk_conv2d_fwd_wp_f16x1': SIGNATURES['stk_conv2d_fwd_wp_f32'],
+}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -139,6 +146,15 @@ class StkLib:
         setattr(self, name[4:], fn)
       else:
         setattr(self, name[4:], self._checked(name, fn))
+    present = [name for name in SIGNATURES_FP16 if hasattr(self._cdll, name)]
+    if present and len(present) != len(SIGNATURES_FP16):
+      raise StkMissingError(f'{path} exports only part of include/stk_fp16.h: {present}')
+    self.has_fp16 = bool(present)
+    for name in present:
+      fn = getattr(self._cdll, name)
+      fn.argtypes = SIGNATURES_FP16[name]
+      fn.restype = c_int
+      setattr(self, name[4:], self._checked(name, fn))
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 

@@ -66,7 +66,13 @@ def get_likelihood_residual_fn(config, sde, score_fn, variance='ddpm'):
 
 
 def get_likelihood_fn(config, sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45'):
-  """``likelihood_fn(model, data, logdet=0., eps=1e-5, mode='correct') -> (bpd[B], z, nfe)`` (likelihood.py:42-134)."""
+  """``likelihood_fn(model, data, logdet=0., eps=1e-5, mode='correct') -> (bpd[B], z, nfe)`` (likelihood.py:42-134).
+
+  fp32 only: config.sampling.precision = 'fp16' raises ValueError (the RK45 tolerances of 1e-5 sit below fp16-level
+  noise in the drift, and the divergence estimator differentiates the network, which the fp16 mode does not)."""
+  if mutils.sampling_precision(config) != 'fp32':
+    raise ValueError("likelihood computation runs in fp32 only: config.sampling.precision='fp16' is refused (RK45 at "
+                     "rtol = atol = 1e-5 sits below fp16-level noise in the drift; the divergence needs a backward)")
 
   def drift_fn(model, x, t):
     score_fn = mutils.get_score_fn(config, sde, model, train=False, continuous=True)

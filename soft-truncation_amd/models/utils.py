@@ -91,6 +91,33 @@ def frozen_weights(model):
   return engine().frozen_weights() if callable(engine) else contextlib.nullcontext()
 
 
+PRECISIONS = ('fp32', 'fp16')
+
+
+def precision(model, precision):
+  """Context manager: the network evaluations of `model` inside it run in `precision` -- 'fp32' (the default path) or
+  'fp16' (one fp16 product per multiply-add in the split convolutions, include/stk_fp16.h; forward-only: a forward that
+  a backward may follow raises ValueError inside the block).  For a user's own loop around get_score_fn.  A no-op for
+  models without an engine (the value is still checked)."""
+  import contextlib
+  if precision not in PRECISIONS:
+    raise ValueError(f'precision must be one of {PRECISIONS}, got {precision!r}')
+  inner = getattr(model, 'module', model)
+  engine = getattr(inner, 'engine', None)
+  return engine().precision(precision) if callable(engine) else contextlib.nullcontext()
+
+
+def sampling_precision(config):
+  """config.sampling.precision: 'fp32' when the key is absent (the reference's configs have none), else checked."""
+  try:
+    p = config.sampling.precision
+  except (AttributeError, KeyError):
+    return 'fp32'
+  if p not in PRECISIONS:
+    raise ValueError(f'config.sampling.precision must be one of {PRECISIONS}, got {p!r}')
+  return p
+
+
 def get_model_fn(model, train=False):
   """Callable running the model in train or eval mode, re-asserted on every call (models/utils.py:97-126)."""
 

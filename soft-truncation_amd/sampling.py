@@ -307,7 +307,12 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   """``sampling_fn(model) -> (samples, nfe)`` for ``config.sampling.method`` (sampling.py:80-125)."""
   s = config.sampling
   kind = s.method.lower()
+  precision = mutils.sampling_precision(config)
   if kind == 'ode':
+    if precision != 'fp32':
+      raise ValueError(f"config.sampling.precision={precision!r} is not supported by the ODE sampler: RK45 at rtol = atol = "
+                       f"1e-5 sits below the fp16-level noise of the drift, and its step controller's behaviour there is "
+                       f"unmeasured; use precision='fp32' or method='pc'")
     return get_ode_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler,
                            denoise=s.noise_removal, eps=eps, device=config.device)
   if kind == 'pc':
@@ -315,14 +320,15 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
                           corrector=get_corrector(s.corrector.lower()), inverse_scaler=inverse_scaler, snr=s.snr,
                           n_steps=s.n_steps_each, probability_flow=s.probability_flow,
                           continuous=config.training.continuous, denoise=s.noise_removal, eps=eps,
-                          device=config.device)
+                          device=config.device, precision=precision)
   raise ValueError(f"Sampler name {s.method} unknown.")
 
 
 def get_pc_sampler(config, sde, shape, predictor, corrector, inverse_scaler, snr, n_steps=1,
-                   probability_flow=False, continuous=False, denoise=True, eps=1e-3, device='cuda'):
+                   probability_flow=False, continuous=False, denoise=True, eps=1e-3, device='cuda', precision='fp32'):
   """Predictor-corrector sampler (sampling.py:365-433): at each of the N times from T down to eps the corrector runs
-  first, then the predictor; ``nfe = N (n_steps + 1)``."""
+  first, then the predictor; ``nfe = N (n_steps + 1)``.  precision='fp16': every network evaluation of the loop, the
+  final denoising step included, runs in the engine's fp16 mode (models.utils.precision)."""
   predict = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
                               probability_flow=probability_flow, continuous=continuous, config=config)
   correct = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
@@ -331,7 +337,7 @@ def get_pc_sampler(config, sde, shape, predictor, corrector, inverse_scaler, snr
 
   def pc_sampler(model):
     # the parameters are fixed for the whole loop: convolution weights are prepared once (models.utils.frozen_weights)
-    with torch.no_grad(), mutils.frozen_weights(model):
+    with torch.no_grad(), mutils.frozen_weights(model), mutils.precision(model, precision):
       x = sde.prior_sampling(shape).to(device)
       grid = torch.linspace(sde.T, eps, sde.N, device=device)
       for i in tqdm(range(sde.N)):
