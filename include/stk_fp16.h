@@ -15,8 +15,9 @@
  * On shapes whose forward is not a split form (thin-side streaming kernels, the f32-input MFMA tiles, stride 2) a twin
  * returns the same result as its fp32 entry, bit for bit.
  *
- * Forward only: the twins leave nothing a backward could reuse beyond what the fp32 entries leave (the |x| records of
- * stk_conv2d_fwd_wp_f16x1 are the same), and there are no data- or weight-gradient twins.
+ * The twins leave nothing a backward could reuse beyond what the fp32 entries leave (the |x| records of
+ * stk_conv2d_fwd_wp_f16x1 are the same).  The data- and weight-gradient twins of the fp16 training mode are declared in
+ * stk_fp16_train.h.
  */
 #ifndef STK_FP16_H
 #define STK_FP16_H

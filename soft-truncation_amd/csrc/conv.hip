@@ -20,8 +20,7 @@
 // fixed order into dw (deterministic -- no float atomics).
 #include "igemm.h"
 #include "stk_fp16.h"
-
-#include <type_traits>
+#include "stk_fp16_train.h"
 
 namespace {
 
@@ -569,8 +568,8 @@ struct EpSlab {
     }
   }
 };
-// OneProduct<EP>: epilogue EP of the one-product forward kernels (include/stk_fp16.h; conv_x2.h / conv_x2d.h read it with
-// is_x1).  A type of its own, so that the fp16 kernels are instantiations with symbols of their own and the fp32 ones keep theirs.
+// OneProduct<EP>: epilogue EP of the one-product kernels (include/stk_fp16.h, include/stk_fp16_train.h; conv_x2.h / conv_x2d.h
+// read it with is_x1).  A type of its own, so that the fp16 kernels are instantiations with symbols of their own and the fp32 ones keep theirs.
 template <class EP> struct OneProduct : EP {};
 template <class EP> struct is_x1 { static constexpr bool value = false; };
 template <class EP> struct is_x1<OneProduct<EP>> { static constexpr bool value = true; };
@@ -1038,7 +1037,7 @@ inline void x3_weight_strides(const ConvP& p, int dgrad, long& sm, long& sk) {
   else { sm = dgrad ? p.Cout : 1; sk = dgrad ? 1 : p.Cout; }          // NIN w[Cin][Cout]
 }
 // wp_ready: weights already prepared by stk_conv2d_wprep_batch (then ws only holds the K-split slabs)
-// x1: the one-product forms (include/stk_fp16.h): hi(w) hi(x) only.  With planes a chunk then covers a PAIR of 32-channel
+// x1: the one-product forms (include/stk_fp16.h, include/stk_fp16_train.h): hi(w) hi(x) only.  With planes a chunk then covers a PAIR of 32-channel
 // groups (conv_x2d.h), so the chunk count roughly halves; the plan keeps its number of K splits (and slab layout) unless the
 // halved count leaves some empty.
 inline X3Plan x1_plan(const X3Plan& r, int nch1) {
@@ -1088,12 +1087,9 @@ int launch_x3(ConvP p, const X3Plan& r0, const float* s1, int S1, const float* s
     const int tm = q.Mpad / 128, tn = stk_cdiv((int)Ng, 128);
     const int nch = planes && x1 ? p.taps * ((q.Kc / x3::KC + 1) / 2) : p.taps * (q.Kc / x3::KC);
     const X3Plan r = planes && x1 ? x1_plan(r0, nch) : r0;
-    // one-product kernels exist for the forward only: in the data-gradient instantiation STK_X1 / STK_X1L name the fp32
-    // kernels (that branch is never taken there), so no dead fp16 code is built
-    constexpr bool kFwd = std::is_same<EP, EpFwd>::value;
-    if (x1 && !kFwd) return STK_EINVAL;
-#define STK_X1(E) std::conditional_t<kFwd, OneProduct<E>, E>
-#define STK_X1L(DUAL, TAPS) std::conditional_t<kFwd, x2::ActLoader16<DUAL, TAPS>, x2::ActLoader<DUAL, TAPS>>
+    // one-product kernels: forward (include/stk_fp16.h) and data gradient (include/stk_fp16_train.h) alike
+#define STK_X1(E) OneProduct<E>
+#define STK_X1L(DUAL, TAPS) x2::ActLoader16<DUAL, TAPS>
     const dim3 grid((unsigned)(tm * tn * r.splits));
 #define STK_X2_LAUNCH(E, DUAL, TAPS)                                                                              \
   if (x1) hipLaunchKernelGGL((x2::gemm_kernel<STK_X1L(DUAL, TAPS), STK_X1(E)>), grid, dim3(256), 0, s, p, q, M, \
@@ -1328,7 +1324,7 @@ int stk_conv2d_fwd_f32(const float* x1, int C1, const float* x2, int C2, const f
 static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
                       int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
                       int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                      void* stream, bool dy_rec_valid);
+                      void* stream, bool dy_rec_valid, bool f16x1 = false);
 int stk_conv2d_dgrad_wp_f32(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
                             int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
                             int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
@@ -1348,7 +1344,7 @@ int stk_conv2d_dgrad_rec_f32(const float* dy, const float* w, int w_layout, floa
 static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
                       int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
                       int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                      void* stream, bool dy_rec_valid) {
+                      void* stream, bool dy_rec_valid, bool f16x1) {
   if (!dy || !w || (!dx1 && !dx2) || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && (KH != 1 || KW != 1)))
     return STK_EINVAL;
   ConvP p = {};
@@ -1371,7 +1367,7 @@ static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1,
   }
   const X3Plan xr = x3_plan(p, Cout, Cout, 0, Cin, Ng);
   if (ws && xr.ok && ws_bytes >= x3_ws_bytes(xr, Cin, Cout, p.taps))
-    return launch_x3<EpDgrad>(p, xr, dy, Cout, nullptr, 0, Cin, Ng, 1, ws, s, wp, amax, nullptr, nullptr, dy_rec_valid);
+    return launch_x3<EpDgrad>(p, xr, dy, Cout, nullptr, 0, Cin, Ng, 1, ws, s, wp, amax, nullptr, nullptr, dy_rec_valid, f16x1);
   if (wp) return STK_EINVAL;
   if (p.taps == 9) {
     using CB = Cfg<128, 128, 36>; using CS = Cfg<64, 64, 36>;
@@ -1494,9 +1490,9 @@ int stk_conv2d_fwd_rec_f16x1(const float* x1, int C1, const float* x2, int C2, c
                   pad, wp, amax, ws, ws_bytes, stream, true, true);
 }
 
-int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
-                            float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
-                            int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+static int dgrad_pl_impl(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
+                         float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
+                         int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
   if (!dypl || !dyamax || !w || (!dx1 && !dx2) || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
     return STK_EINVAL;
   if (!stk_conv2d_pl_ok(1, C1, C2, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
@@ -1507,7 +1503,14 @@ int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* 
   const long Ng = (long)N * p.HW;
   const X3Plan xr = x3_plan_pl(p, Cout, p.Cin, Ng);
   if (!ws || ws_bytes < x3_ws_bytes(xr, p.Cin, Cout, p.taps)) return STK_EINVAL;
-  return launch_x3<EpDgrad>(p, xr, nullptr, Cout, nullptr, 0, p.Cin, Ng, 1, ws, (hipStream_t)stream, wp, nullptr, dypl, dyamax);
+  return launch_x3<EpDgrad>(p, xr, nullptr, Cout, nullptr, 0, p.Cin, Ng, 1, ws, (hipStream_t)stream, wp, nullptr, dypl, dyamax,
+                            false, f16x1);
+}
+int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
+                            float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
+                            int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return dgrad_pl_impl(dypl, dyamax, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, KH, KW, wp, ws, ws_bytes,
+                       stream, false);
 }
 
 /* 3x3 / stride 1 / pad 1 weight gradient with x and dy given as planes (conv_x2w.h) */
@@ -1530,8 +1533,14 @@ int stk_conv2d_wgrad_pl_f32(const void* xpl, const float* xrec, const void* dypl
 
 /* ... with the number of workgroups its K split fills chosen by the caller (0 = the library's default for a launch that shares the chip
  * with another stream; <= 1024).  Same result up to the summation order of the slabs. */
+static int wgrad_pl_impl(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw, float alpha,
+                         float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream, bool f16x1);
 int stk_conv2d_wgrad_pl_wgs_f32(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
                                 float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream) {
+  return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, wgs, stream, false);
+}
+static int wgrad_pl_impl(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw, float alpha,
+                         float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream, bool f16x1) {
   if (!xpl || !xrec || !dypl || !dyrec || !dw || !ws || wgs < 0 || wgs > 1024) return STK_EINVAL;
   const x2w::Plan q = x2w::plan(N, H, W, Cin, Cout, wgs);
   if (!q.ok) return STK_EUNSUPPORTED;
@@ -1546,7 +1555,18 @@ int stk_conv2d_wgrad_pl_wgs_f32(const void* xpl, const float* xrec, const void* 
   a.nchunks_total = (int)((long)N * H * W / 32); a.chunks_per_split = q.chunks_per_split;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)(a.tiles_co * a.tiles_ci * q.splits));
-  if (q.groups == 2) {
+  if (f16x1) {                                   // the one-product form: same plan, slabs and reduce (conv_x2w.h, X1_FORM)
+    constexpr int X1 = x2w::X1_FORM;
+    if (q.groups == 2) {
+      if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 2 | X1>), grid, dim3(512), 0, s, a);
+      else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 2 | X1>), grid, dim3(512), 0, s, a);
+      else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 2 | X1>), grid, dim3(512), 0, s, a);
+      else hipLaunchKernelGGL((x2w::wgrad_kernel<4, 2 | X1>), grid, dim3(512), 0, s, a);
+    } else if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 1 | X1>), grid, dim3(256), 0, s, a);
+    else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 1 | X1>), grid, dim3(256), 0, s, a);
+    else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 1 | X1>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((x2w::wgrad_kernel<4, 1 | X1>), grid, dim3(256), 0, s, a);
+  } else if (q.groups == 2) {
     if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 2>), grid, dim3(512), 0, s, a);
     else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 2>), grid, dim3(512), 0, s, a);
     else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 2>), grid, dim3(512), 0, s, a);
@@ -1674,9 +1694,18 @@ long stk_conv2d_wgrad_ws_bytes(int C1, int C2, int N, int Cout, int OH, int OW, 
   return (m > nx ? m : nx) * 4 + 256 + 256 + 3L * x2::NPART * 4;      // + partial maxima of dy, x1, x2
 }
 
+static int wgrad_amax_impl(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
+                           float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                           int KW, int stride, int pad, const float* amax, int have, void* stream, bool f16x1);
 int stk_conv2d_wgrad_amax_f32(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
                               float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
                               int KW, int stride, int pad, const float* amax, int have, void* stream) {
+  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
+                         have, stream, false);
+}
+static int wgrad_amax_impl(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
+                           float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                           int KW, int stride, int pad, const float* amax, int have, void* stream, bool f16x1) {
   if (!x1 || !dy || !dw || !ws || (C2 > 0 && !x2) || (w_layout != 0 && w_layout != 1) ||
       (w_layout == 1 && (KH != 1 || KW != 1)))
     return STK_EINVAL;
@@ -1711,7 +1740,9 @@ int stk_conv2d_wgrad_amax_f32(const float* x1, int C1, const float* x2, int C2, 
     p.x1 = x1; p.x2 = C2 > 0 ? x2 : x1; p.dy = dy; p.w_layout = w_layout; p.part = ws; p.part_stride = xq.slab;
     const int tm = stk_cdiv(Cout, 128), tn = stk_cdiv(p.Cin, 128);
     const int nch = (int)((long)N * p.HW / 32);
-    if (xq.rows3) {
+    // the one-product form has no three-taps kernel: its 3x3 layers run the per-tap x2::wgemm_kernel below (a 128 x 128 tile
+    // per tap, the same K split and slabs [tap][Cout][Cin])
+    if (xq.rows3 && !f16x1) {
       const int tn64 = stk_cdiv(p.Cin, 64);
       const dim3 grid3((unsigned)(3 * tm * tn64 * xq.splits));
       float* parts = reinterpret_cast<float*>(((uintptr_t)(ws + (long)xq.splits * xq.slab) + 255) & ~(uintptr_t)255);
@@ -1757,15 +1788,23 @@ int stk_conv2d_wgrad_amax_f32(const float* x1, int C1, const float* x2, int C2, 
         if (C2 > 0) hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x2, (long)N * C2 * p.HW, parts + 2 * x2::NPART);
       }
       const int nx = C2 > 0 ? 2 * x2::NPART : x2::NPART;
-#define STK_X2_WGRAD1(BLOADER)                                                                                              \
-  hipLaunchKernelGGL((x2::wgemm_kernel<x2::RowsU<false, false>, BLOADER, EpWgrad, true>), grid, dim3(256), 0, s, p, Cout,  \
+#define STK_X2_WGRAD1(BL, ARGS)                                                                                             \
+  hipLaunchKernelGGL((x2::wgemm_kernel<x2::RowsU<false, false>, x2::BL<ARGS>, EpWgrad, true>), grid, dim3(256), 0, s, p, Cout, \
                      p.Cin, tm, tn, nch, xq.chunks_per_split, p.taps, dyp, xp, nx)
+// the one-product form (include/stk_fp16_train.h): hi-plane loaders (RowsU16 / RowsB16), OneProduct epilogue, no schedule pins
+#define STK_X2_WGRAD1_X1(BL, ARGS)                                                                                          \
+  hipLaunchKernelGGL((x2::wgemm_kernel<x2::RowsU16<false, false>, x2::BL##16<ARGS>, OneProduct<EpWgrad>, false>), grid,      \
+                     dim3(256), 0, s, p, Cout, p.Cin, tm, tn, nch, xq.chunks_per_split, p.taps, dyp, xp, nx)
 #define STK_COMMA ,
-      if (p.taps == 1) { if (C2 > 0) STK_X2_WGRAD1(x2::RowsU<true STK_COMMA true>); else STK_X2_WGRAD1(x2::RowsU<true STK_COMMA false>); }
-      else if (W >= 16) { if (C2 > 0) STK_X2_WGRAD1(x2::RowsB<true STK_COMMA 16>); else STK_X2_WGRAD1(x2::RowsB<false STK_COMMA 16>); }
-      else if (W == 8) { if (C2 > 0) STK_X2_WGRAD1(x2::RowsB<true STK_COMMA 8>); else STK_X2_WGRAD1(x2::RowsB<false STK_COMMA 8>); }
-      else { if (C2 > 0) STK_X2_WGRAD1(x2::RowsB<true STK_COMMA 4>); else STK_X2_WGRAD1(x2::RowsB<false STK_COMMA 4>); }
+#define STK_X2_WGRAD1_ALL(L)                                                                                                \
+      if (p.taps == 1) { if (C2 > 0) L(RowsU, true STK_COMMA true); else L(RowsU, true STK_COMMA false); }                  \
+      else if (W >= 16) { if (C2 > 0) L(RowsB, true STK_COMMA 16); else L(RowsB, false STK_COMMA 16); }                     \
+      else if (W == 8) { if (C2 > 0) L(RowsB, true STK_COMMA 8); else L(RowsB, false STK_COMMA 8); }                        \
+      else { if (C2 > 0) L(RowsB, true STK_COMMA 4); else L(RowsB, false STK_COMMA 4); }
+      if (f16x1) { STK_X2_WGRAD1_ALL(STK_X2_WGRAD1_X1) } else { STK_X2_WGRAD1_ALL(STK_X2_WGRAD1) }
+#undef STK_X2_WGRAD1_ALL
 #undef STK_COMMA
+#undef STK_X2_WGRAD1_X1
 #undef STK_X2_WGRAD1
       STK_CHECK_LAUNCH();
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((xq.slab + 3) / 4)), dim3(256), 0, s, ws, dw, xq.slab, xq.splits,
@@ -1809,6 +1848,44 @@ int stk_conv2d_wgrad_f32(const float* x1, int C1, const float* x2, int C2, const
                          int KW, int stride, int pad, void* stream) {
   return stk_conv2d_wgrad_amax_f32(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride,
                                    pad, nullptr, 0, stream);
+}
+
+/* ---- include/stk_fp16_train.h: the one-product twins of the backward entries ------------------------------------------ */
+int stk_conv2d_dgrad_pl_f16x1(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
+                              float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
+                              int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return dgrad_pl_impl(dypl, dyamax, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, KH, KW, wp, ws, ws_bytes,
+                       stream, true);
+}
+int stk_conv2d_dgrad_wp_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                              int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                              int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                              void* stream) {
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, false, true);
+}
+int stk_conv2d_dgrad_rec_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                               int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                               int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                               void* stream) {
+  if (!amax) return STK_EINVAL;
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, true, true);
+}
+int stk_conv2d_wgrad_pl_f16x1(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
+                              float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream) {
+  return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, 0, stream, true);
+}
+int stk_conv2d_wgrad_pl_wgs_f16x1(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
+                                  float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs,
+                                  void* stream) {
+  return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, wgs, stream, true);
+}
+int stk_conv2d_wgrad_amax_f16x1(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
+                                float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                                int KW, int stride, int pad, const float* amax, int have, void* stream) {
+  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
+                         have, stream, true);
 }
 
 int stk_gemm_f32(const float* A, long sam, long sak, long sab, const float* B, long sbk, long sbn, long sbb, float* C,

@@ -531,22 +531,24 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(ConvP p, int tiles_m, int t
 // longer hide behind the second half-chunk alone, so a chunk's work is laid out over both halves: the split of chunk
 // c + 1 (registers only) and the load issue of chunk c + 2 ride on the MFMAs of kk = 0, the eight LDS stores on those of
 // kk = 1 (after the barrier that retires the reads of chunk c).
-template <bool DUAL, int SEG>
-struct RowsB : x3::RowsLoader<true, DUAL, SEG> {           // x: 16 consecutive (tap-shifted) pixels of one input channel
+template <bool DUAL, int SEG, bool X1>
+struct RowsBT : x3::RowsLoader<true, DUAL, SEG> {          // x: 16 consecutive (tap-shifted) pixels of one input channel
   using B = x3::RowsLoader<true, DUAL, SEG>;
-  Split16 sp2; float scale;
+  Split16X<X1> sp2; float scale;
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp2.st(g, B::r, scale, t, B::row, B::half * 16, B::okm); }
 };
+template <bool DUAL, int SEG> struct RowsB : RowsBT<DUAL, SEG, false> {};
+template <bool DUAL, int SEG> struct RowsB16 : RowsBT<DUAL, SEG, true> {};     // hi plane only (OneProduct weight gradient)
 
 // Unshifted rows (dy always; x of a 1x1 layer): the thread's 16 consecutive pixels are one aligned 64-byte run, read as
 // four 16-byte loads.  (x3::RowsLoader reads a run element by element because a tap shift breaks the alignment and needs
 // a per-element mask; with 32 such loads per thread and chunk, each touching 64 separate 64-byte segments, the per-tap
 // kernel was bound by address processing: 54 us for the 256 -> 256 layer at 16 x 16 against ~6 us of MFMAs.)
-template <bool IS_X, bool DUAL>
-struct RowsU {
+template <bool IS_X, bool DUAL, bool X1>
+struct RowsUT {
   __amdgpu_buffer_rsrc_t rs;
   int rowoff, bstride, row, half; bool rowok; unsigned voff;
-  float r[16]; Split16 sp2; float scale;
+  float r[16]; Split16X<X1> sp2; float scale;
   __device__ __forceinline__ void init(const ConvP& p, const x3::Src&, int o0, int tid, int) {
     row = tid >> 1; half = tid & 1; voff = 0x80000000u;
     const int ch = o0 + row;
@@ -580,12 +582,17 @@ struct RowsU {
   }
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp2.st(g, r, scale, t, row, half * 16); }
 };
+template <bool IS_X, bool DUAL> struct RowsU : RowsUT<IS_X, DUAL, false> {};
+template <bool IS_X, bool DUAL> struct RowsU16 : RowsUT<IS_X, DUAL, true> {};  // hi plane only (OneProduct weight gradient)
 
+// X1 (EP = OneProduct<EpWgrad>, include/stk_fp16_train.h): RowsU16 / RowsB16 loaders, split-0 fragments only, and the 4
+// hi(dy) hi(x) MFMAs of the 12 per half chunk.
 template <class AL, class BL, class EP, bool PIN>
 __global__ __launch_bounds__(256) void wgemm_kernel(ConvP p, int M, int Nn, int tiles_m, int tiles_n, int nchunks_total,
                                                     int chunks_per_split, int taps_z, const float* __restrict__ dypart,
                                                     const float* __restrict__ xpart, int nxpart) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+  constexpr bool X1 = is_x1<EP>::value;
   unsigned char* As = lds;
   unsigned char* Bs = lds + OPER;
   const int tid = threadIdx.x;
@@ -623,12 +630,13 @@ __global__ __launch_bounds__(256) void wgemm_kernel(ConvP p, int M, int Nn, int 
   const unsigned char* b_rd = Bs + (wn0 + fc) * PITCH + fk * 16;
 
 #define STK_W1_FRAGS(KK)                                                                               \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int s = 0; s < 2; ++s) {         \
+  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int s = 0; s < (X1 ? 1 : 2); ++s) {         \
     a[i][s] = *reinterpret_cast<const halfx8*>(a_rd + s * PLANE + i * 32 * PITCH + (KK) * 32);          \
     b[i][s] = *reinterpret_cast<const halfx8*>(b_rd + s * PLANE + i * 32 * PITCH + (KK) * 32);          \
   }
   constexpr int SA[3] = {1, 0, 0}, SB[3] = {0, 1, 0};
 #define STK_W1_MFMA(G)                                                                                              \
+  if (!X1 || ((G) >> 2) == 2)                                                                                       \
   acc[((G) >> 1) & 1][(G) & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[((G) >> 1) & 1][SA[(G) >> 2]], b[(G) & 1][SB[(G) >> 2]], \
                                                                         acc[((G) >> 1) & 1][(G) & 1], 0, 0, 0);
 #pragma unroll

@@ -72,8 +72,17 @@ constexpr int BUF = 2 * A_PLANE + 2 * B_PLANE;   // 36864 per stage
 // and a SIMD holds ONE wave of this kernel in the two-stream geometry): seven times SLOWER, because hipcc then puts an s_waitcnt vmcnt(0)
 // in front of every DMA and every following fragment read (it cannot prove that the DMA's LDS bytes are not the ones being read, even
 // with the two stages as two __shared__ objects), which makes every DMA synchronous.  The burst at the chunk boundary stays.
-template <int COLS, int GROUPS = 1>
-__global__ __launch_bounds__(256 * GROUPS, 2) void wgrad_kernel(Args a) {
+// FORM = GROUPS | X1_FORM (wgrad_kernel<COLS, GROUPS | X1_FORM>): the weight gradient of the fp16 training mode
+// (include/stk_fp16_train.h), ONE product per element, hi(dy) hi(x) -- only split 0 of both operands is DMA'd (the split-1
+// slots of the stages stay unused) and only the SA = SB = 0 MFMA of the three is issued: half the DMA bytes, 9 instead of 27
+// MFMAs and 12 instead of 24 fragment reads per half chunk.  (A flag bit of the second template argument rather than a third
+// argument: the fp32 kernels keep their symbols and, with the body left in the kernel, exactly their code.)
+constexpr int X1_FORM = 16;
+template <int COLS, int FORM = 1>
+__global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
+  constexpr int GROUPS = FORM & 15;
+  constexpr bool X1 = (FORM & X1_FORM) != 0;
+  constexpr int NS = X1 ? 1 : 2;            // planes staged and read per operand
   constexpr int STAGES = 2;
   constexpr bool TWO = COLS == 4;           // 4 x 4 maps: a chunk is two whole images
   constexpr int ROWS = 32 / COLS;           // chunk rows (TWO: 8 = 4 + 4)
@@ -143,13 +152,14 @@ __global__ __launch_bounds__(256 * GROUPS, 2) void wgrad_kernel(Args a) {
       const int xx = x0 + a_c[j] - 1;
       const unsigned vo = (xx >= 0 && xx < a.W) ? (unsigned)(a_chunk + a_rel[j]) : 0x80000000u;    // outside the map: DMA of zeros
 #pragma unroll
-      for (int s = 0; s < 2; ++s)
+      for (int s = 0; s < NS; ++s)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (lds_void*)(buf + s * A_PLANE + wid * A_BLK + j * 1024), 16,
                                                  (int)vo, (int)(s * (unsigned)a.dy_ps), 0, 0);
     }
     const int b_chunk = ((b * a.Cib + tci) * a.HW + hw0) * 64;
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
+      if (X1 && b_pl[u]) continue;                                       // split 1 of x (wave-uniform)
       const int yy = y0 + b_ty[u] - 1;
       const unsigned vo = (yy >= 0 && yy < a.H) ? (unsigned)(b_chunk + b_rel[u]) : 0x80000000u;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (lds_void*)(buf + b_dst[u]), 16, (int)vo, (int)(b_pl[u] * (unsigned)a.x_ps), 0, 0);
@@ -186,18 +196,18 @@ __global__ __launch_bounds__(256 * GROUPS, 2) void wgrad_kernel(Args a) {
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
+        for (int s = 0; s < NS; ++s)
           af[t][s] = cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(buf + s * A_PLANE + a_off[kk][0] - (t - 1) * 64)),
                          __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(buf + s * A_PLANE + a_off[kk][1] - (t - 1) * 64)));
 #pragma unroll
       for (int t3 = 0; t3 < 3; ++t3) {                                   // one kernel row: x at row qy + (kh - 1)
         halfx8 bf[2];
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
+        for (int s = 0; s < NS; ++s)
           bf[s] = cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(buf + s * B_PLANE + b_off[kk][0] + (t3 - 1) * COLS * 64)),
                       __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(buf + s * B_PLANE + b_off[kk][1] + (t3 - 1) * COLS * 64)));
 #pragma unroll
-        for (int pr = 0; pr < 3; ++pr)
+        for (int pr = X1 ? 2 : 0; pr < 3; ++pr)
 #pragma unroll
           for (int t = 0; t < 3; ++t)
             acc[3 * t3 + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t][SA[pr]], bf[SB[pr]], acc[3 * t3 + t], 0, 0, 0);

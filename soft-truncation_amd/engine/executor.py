@@ -20,6 +20,11 @@ path.  Programs (and so their hipGraph captures) are planned per precision; a fo
 mode, training) raises inside the block.  Everything else -- GroupNorm, resampling, attention, the thin-side and
 f32-input convolutions -- runs exactly as in fp32.
 
+Training precision: ``with ex.training_precision('fp16'):`` runs the evaluations inside it that a backward may follow
+(grad mode, need_xgrad) on the one-product twins in all three directions: the forward twins of include/stk_fp16.h and
+the data- / weight-gradient twins of include/stk_fp16_train.h, on the same streams as in fp32.  Such programs have keys
+and hipGraph captures of their own.  Forward-only evaluations inside the block still follow ``precision()``.
+
 Backend selection is explicit and never silent: the default backend is the HIP library
 (``engine.lib.load()``, raises if it is not built); a test may inject another implementation
 of include/stk.h (the oracle's CPU restatement) with ``set_backend``.
@@ -437,6 +442,7 @@ class Executor:
     # ONE .backward(); buckets may only leave with the last of them.
     self._awaiting = weakref.WeakSet()
     self.mode = 'fp32'       # precision of forward-only evaluations (Executor.precision)
+    self.train_mode = 'fp32'  # precision of evaluations a backward may follow (Executor.training_precision)
 
   @contextlib.contextmanager
   def precision(self, precision):
@@ -452,6 +458,22 @@ class Executor:
       yield self
     finally:
       self.mode = saved
+
+  @contextlib.contextmanager
+  def training_precision(self, precision):
+    """Evaluate the programs a backward may follow (grad mode, need_xgrad) in `precision` inside the block, forward and
+    backward ('fp32' = the default path, bit for bit; 'fp16' = the one-product convolutions of include/stk_fp16.h and
+    include/stk_fp16_train.h).  Forward-only evaluations keep following precision().  Raises ValueError for an unknown
+    precision, StkMissingError when 'fp16' is asked of a library without both fp16 tables."""
+    check_precision(precision)
+    if precision == 'fp16' and not (getattr(self.lib, 'has_fp16', False) and getattr(self.lib, 'has_fp16_train', False)):
+      raise stk_lib.StkMissingError(f'backend {self.lib.backend} ({self.lib.path}) does not export include/stk_fp16.h and '
+                                    f'include/stk_fp16_train.h: no fp16 training mode')
+    saved, self.train_mode = self.train_mode, precision
+    try:
+      yield self
+    finally:
+      self.train_mode = saved
 
   # -- parameters ---------------------------------------------------------------------------------
   def set_backend(self, backend):
@@ -486,7 +508,8 @@ class Executor:
 
   # -- programs -----------------------------------------------------------------------------------
   def program(self, B, H, W, need_xgrad, precision='fp32'):
-    # fp16 programs are keyed apart: their own contexts, their own hipGraph captures (the fp32 keys stay as they were)
+    # fp16 programs are keyed apart: their own contexts, their own hipGraph captures (the fp32 keys stay as they were);
+    # precision 'fp16' = forward-only (Executor.precision), 'fp16-train' = forward and backward (Executor.training_precision)
     key = (B, H, W, need_xgrad) if precision == 'fp32' else (B, H, W, need_xgrad, precision)
     prog = self.programs.get(key)
     if prog is None:
@@ -563,7 +586,8 @@ class Executor:
                  prog.ws.data_ptr(), prog.graph.ws_bytes, training, seed, seed_dev)
     rt.prof = self.profiler
     rt.with_backward = with_backward
-    rt.f16 = prog.graph.precision == 'fp16'
+    rt.f16 = prog.graph.precision in ('fp16', 'fp16-train')
+    rt.f16_bwd = prog.graph.precision == 'fp16-train'
     if self.use_wp and prog.wp is not None and prog.wp_table is not None:
       rt.wp = prog.wp.data_ptr()
     if c.pl is not None:
@@ -624,10 +648,14 @@ class Executor:
 
   def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat):
     B, _, H, W = x.shape
-    if self.mode != 'fp32' and (with_backward or need_xgrad or training):
+    if (with_backward or need_xgrad) and self.train_mode != 'fp32':
+      precision = self.train_mode + '-train'
+    elif self.mode != 'fp32' and (with_backward or need_xgrad or training):
       raise ValueError(f'precision {self.mode!r} is for forward-only evaluation (sampling): a forward that a backward may '
-                       f'follow (grad mode, need_xgrad, training) runs in fp32 only')
-    prog = self.program(B, H, W, need_xgrad, self.mode)
+                       f'follow (grad mode, need_xgrad, training) runs in fp32 only; training_precision() covers those')
+    else:
+      precision = self.mode
+    prog = self.program(B, H, W, need_xgrad, precision)
     c = prog.acquire()
     g = prog.graph
     self._copy_in(c, 'x', x)

@@ -87,6 +87,7 @@ class Runtime:
     self.wp = 0           # base address of the program's prepared-weight arena (0: every conv prepares per call)
     self.with_backward = True   # False: a no-grad evaluation (nothing is kept for a backward pass)
     self.f16 = False            # fp16 mode (Executor.precision): split-form convolutions call their one-product twins
+    self.f16_bwd = False        # ... in the backward too (Executor.training_precision, include/stk_fp16_train.h)
     self.pl = 0           # base address of the context's planes arena (pre-split conv operands)
     self.dypl = 0         # ... and of its scratch for the planes of the gradient a data-gradient call consumes
     self.prof = None      # optional engine.profile.KernelTimer: HIP events around the contraction launches
@@ -551,6 +552,10 @@ class Conv(Op):
     elif not rec_done and (dtemb is not None or gb is not None):
       lib.bias_grad_f32(gy, self.N, self.Cout, self.OH * self.OW, alpha, dtemb, self.temb_stride, gb,
                         rt.ws, rt.stream)
+    # fp16 training mode (include/stk_fp16_train.h): every contraction calls its one-product twin, which runs the non-split
+    # forms exactly as the fp32 entry does; the profiler label of a split form gets '.f16'
+    sfx = '_f16x1' if rt.f16_bwd else '_f32'
+    f16 = '.f16' if rt.f16_bwd else ''
     # data gradient first: its |dy| maxima are reused by the weight gradient (the two are independent otherwise)
     have = 1 if self._kind(lib, 'fwd').endswith('.x2') else 0
     if self.pl_fwd and not self.x_rec_own:
@@ -567,19 +572,20 @@ class Conv(Op):
     if src is not None and self.peer_planes is not None and (g1 is not None or g2 is not None):
       # the peer's dy planes (and the record they were scaled with) serve this 1x1 data gradient too
       ppl = rt.pl + src.dypl_off if self.peer_planes == 'own' else rt.dypl
-      rt.timed(self._label_pl(lib, 'dgrad'), self.flops, lib.conv2d_dgrad_pl_f32,
+      rt.timed(self._label_pl(lib, 'dgrad') + f16, self.flops, getattr(lib, 'conv2d_dgrad_pl' + sfx),
                ppl, rt.v(self.amax) + 4 * 512, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
                g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
                alpha, self.N, self.H, self.W, self.Cout, self.KH, self.KW, self._wp(rt, 1), rt.ws, rt.ws_bytes, rt.stream)
     elif pl_dgrad:
-      rt.timed(self._label_pl(lib, 'dgrad'), self.flops, lib.conv2d_dgrad_pl_f32,
+      rt.timed(self._label_pl(lib, 'dgrad') + f16, self.flops, getattr(lib, 'conv2d_dgrad_pl' + sfx),
                dypl, rec, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
                g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
                alpha, self.N, self.H, self.W, self.Cout, self.KH, self.KW, self._wp(rt, 1), rt.ws, rt.ws_bytes, rt.stream)
       have |= 2
     elif g1 is not None or g2 is not None:
-      rt.timed(self._kind(lib, 'dgrad'), self.flops,
-               lib.conv2d_dgrad_rec_f32 if (src is not None or self.dy_prod is not None) else lib.conv2d_dgrad_wp_f32,
+      kind = self._kind(lib, 'dgrad')
+      rt.timed(kind + (f16 if kind.endswith('.x2') else ''), self.flops,
+               getattr(lib, ('conv2d_dgrad_rec' if (src is not None or self.dy_prod is not None) else 'conv2d_dgrad_wp') + sfx),
                gy, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
                g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
                alpha, *self._dims(), self._wp(rt, 1), rt.v(self.amax), rt.ws, rt.ws_bytes, rt.stream)
@@ -587,19 +593,20 @@ class Conv(Op):
         have |= 2
     rt._cur = self.y.name
     if pl_wgrad and rt.side is not None and rt.prof is None and self.dypl_off is not None:
-      rt.side_launch(lib.conv2d_wgrad_pl_f32, rt.planes(self.x1), rt.rec(self.x1), dypl, dy_rec, gw, alpha, rt.ws2,
+      rt.side_launch(getattr(lib, 'conv2d_wgrad_pl' + sfx), rt.planes(self.x1), rt.rec(self.x1), dypl, dy_rec, gw, alpha, rt.ws2,
                      rt.ws_bytes, self.N, self.H, self.W, self.C1, self.Cout)
     elif pl_wgrad:
       # (on the main stream: STK_X2W_WGS_ALONE may ask for more workgroups than the side-stream launch above uses; see _X2W_WGS_ALONE)
-      rt.timed(self._label_pl(lib, 'wgrad'), self.flops, lib.conv2d_wgrad_pl_wgs_f32,
+      rt.timed(self._label_pl(lib, 'wgrad') + f16, self.flops, getattr(lib, 'conv2d_wgrad_pl_wgs' + sfx),
                rt.planes(self.x1), rt.rec(self.x1), dypl, dy_rec, gw, alpha, rt.ws, rt.ws_bytes,
                self.N, self.H, self.W, self.C1, self.Cout, _X2W_WGS_ALONE, rt.stream)
     elif gw is not None and rt.side is not None and rt.prof is None:
       # a weight gradient is a leaf of the backward: x, dy and this layer's own records in, dw out
-      rt.side_launch(lib.conv2d_wgrad_amax_f32, rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, alpha,
+      rt.side_launch(getattr(lib, 'conv2d_wgrad_amax' + sfx), rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, alpha,
                      rt.ws2, rt.ws_bytes, *self._dims(), rt.v(self.amax), have)
     elif gw is not None:
-      rt.timed(self._kind(lib, 'wgrad'), self.flops, lib.conv2d_wgrad_amax_f32,
+      kind = self._kind(lib, 'wgrad')
+      rt.timed(kind + (f16 if kind.endswith('.x2') else ''), self.flops, getattr(lib, 'conv2d_wgrad_amax' + sfx),
                rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, alpha,
                rt.ws, rt.ws_bytes, *self._dims(), rt.v(self.amax), have, rt.stream)
 
@@ -1052,7 +1059,7 @@ class Graph:
   def __init__(self, flat, lib=None):
     self.flat = flat                  # engine.flat.FlatParams (parameter -> flat offset)
     self.lib = lib                    # the backend the plan is made for (ops may ask it which kernels take a shape)
-    self.precision = 'fp32'           # 'fp16': a forward-only program of the fp16 mode (Executor.program)
+    self.precision = 'fp32'           # 'fp16' / 'fp16-train': a program of the fp16 mode / training mode (Executor.program)
     self.ops = []
     self.tensors = []
     self.conv_amax = []               # the convolutions' 768-float amax buffers (offsets assigned by finalize)

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has it, include/stk_fp16.h).
+"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h and
+include/stk_fp16_train.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -115,6 +116,16 @@ SIGNATURES_FP16 = {
   'stk_conv2d_fwd_rec_f16x1': SIGNATURES['stk_conv2d_fwd_rec_f32'],
   'stk_conv2d_fwd_wp_f16x1': SIGNATURES['stk_conv2d_fwd_wp_f32'],
 }
+# include/stk_fp16_train.h: the one-product backward twins (fp16 training mode).  Bound like SIGNATURES_FP16, when present;
+# `StkLib.has_fp16_train` says whether they are.
+SIGNATURES_FP16_TRAIN = {
+  'stk_conv2d_dgrad_pl_f16x1': SIGNATURES['stk_conv2d_dgrad_pl_f32'],
+  'stk_conv2d_dgrad_rec_f16x1': SIGNATURES['stk_conv2d_dgrad_rec_f32'],
+  'stk_conv2d_dgrad_wp_f16x1': SIGNATURES['stk_conv2d_dgrad_wp_f32'],
+  'stk_conv2d_wgrad_pl_f16x1': SIGNATURES['stk_conv2d_wgrad_pl_f32'],
+  'stk_conv2d_wgrad_pl_wgs_f16x1': SIGNATURES['stk_conv2d_wgrad_pl_wgs_f32'],
+  'stk_conv2d_wgrad_amax_f16x1': SIGNATURES['stk_conv2d_wgrad_amax_f32'],
+}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -146,17 +157,22 @@ class StkLib:
         setattr(self, name[4:], fn)
       else:
         setattr(self, name[4:], self._checked(name, fn))
-    present = [name for name in SIGNATURES_FP16 if hasattr(self._cdll, name)]
-    if present and len(present) != len(SIGNATURES_FP16):
-      raise StkMissingError(f'{path} exports only part of include/stk_fp16.h: {present}')
-    self.has_fp16 = bool(present)
-    for name in present:
-      fn = getattr(self._cdll, name)
-      fn.argtypes = SIGNATURES_FP16[name]
-      fn.restype = c_int
-      setattr(self, name[4:], self._checked(name, fn))
+    self.has_fp16 = self._bind_optional(SIGNATURES_FP16, 'include/stk_fp16.h')
+    self.has_fp16_train = self._bind_optional(SIGNATURES_FP16_TRAIN, 'include/stk_fp16_train.h')
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
+
+  def _bind_optional(self, table, header):
+    """Bind the entries of an optional header: all of them or none (a partial table raises StkMissingError)."""
+    present = [name for name in table if hasattr(self._cdll, name)]
+    if present and len(present) != len(table):
+      raise StkMissingError(f'{self.path} exports only part of {header}: {present}')
+    for name in present:
+      fn = getattr(self._cdll, name)
+      fn.argtypes = table[name]
+      fn.restype = c_int
+      setattr(self, name[4:], self._checked(name, fn))
+    return bool(present)
 
   def _checked(self, name, fn):
     strerror = self._cdll.stk_strerror

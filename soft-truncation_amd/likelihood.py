@@ -83,6 +83,9 @@ def get_likelihood_fn(config, sde, inverse_scaler, hutchinson_type='Rademacher',
     return get_div_fn(lambda xx, tt: drift_fn(model, xx, tt))(x, t, noise)
 
   def likelihood_fn(model, data, logdet=0., eps=1e-5, mode='correct'):
+    if mutils.current_training_precision(model) != 'fp32':
+      raise ValueError("likelihood computation runs in fp32 only: it was called inside training_precision('fp16') (its "
+                       "divergence differentiates the network; RK45 at rtol = atol = 1e-5 sits below fp16-level noise)")
     # hundreds of network evaluations on fixed parameters: prepare the convolution weights once
     with torch.no_grad(), mutils.frozen_weights(model):
       score_fn = mutils.get_score_fn(config, sde, model, train=False, continuous=True)

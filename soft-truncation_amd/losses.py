@@ -334,7 +334,11 @@ def get_step_fn(config, sde, train, optimize_fn=None):
   draw of t_min shared by the micro-batches, per-micro-batch loss + backward of its mean, ``optimize_fn``,
   ``step += 1``, EMA update.  With ``training.mixed`` each micro-batch is split in halves -- importance-sampled and
   uniform-time -- combined as L_is + w L_ddpm (optionally balanced by mean(L_is / L_ddpm)), and the function returns
-  B/2 losses (losses.py:295-320)."""
+  B/2 losses (losses.py:295-320).
+
+  ``config.training.precision = 'fp16'`` runs every micro-batch, forward and backward, in the engine's fp16 training mode
+  (models.utils.training_precision); an absent key means 'fp32', the default path, and any other value raises here."""
+  precision = mutils.config_training_precision(config)
   loss_fn = _pick_loss_fn(config, sde, train)
   tr = config.training
   mixed = bool(tr.mixed)
@@ -370,7 +374,11 @@ def get_step_fn(config, sde, train, optimize_fn=None):
     ddp.begin_step(model)
     try:
       for k in range(parts):
-        losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min)
+        if precision != 'fp32':
+          with mutils.training_precision(model, precision):
+            losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min)
+        else:
+          losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min)
         if k == parts - 1 and OVERLAP_EXCHANGE:
           # multi-GPU: buckets of the flat gradient buffer are all-reduced as the last backward finishes them (with
           # several network evaluations per loss -- training.mixed -- as the LAST of their backwards does)

@@ -107,6 +107,38 @@ def precision(model, precision):
   return engine().precision(precision) if callable(engine) else contextlib.nullcontext()
 
 
+def training_precision(model, precision):
+  """Context manager: the network evaluations of `model` inside it that a backward may follow (grad mode, an input
+  gradient) run in `precision`, forward and backward -- 'fp32' (the default path) or 'fp16' (one fp16 product per
+  multiply-add in every split convolution, include/stk_fp16.h and include/stk_fp16_train.h).  Forward-only evaluations
+  inside it keep following precision(), fp32 by default.  For a user's own training loop; get_step_fn applies it from
+  config.training.precision.  A no-op for models without an engine (the value is still checked)."""
+  import contextlib
+  if precision not in PRECISIONS:
+    raise ValueError(f'precision must be one of {PRECISIONS}, got {precision!r}')
+  inner = getattr(model, 'module', model)
+  engine = getattr(inner, 'engine', None)
+  return engine().training_precision(precision) if callable(engine) else contextlib.nullcontext()
+
+
+def current_training_precision(model):
+  """The training precision in force for `model` ('fp32' for a model without an engine)."""
+  inner = getattr(model, 'module', model)
+  engine = getattr(inner, 'engine', None)
+  return engine().train_mode if callable(engine) else 'fp32'
+
+
+def config_training_precision(config):
+  """config.training.precision: 'fp32' when the key is absent (the reference's configs have none), else checked."""
+  try:
+    p = config.training.precision
+  except (AttributeError, KeyError):
+    return 'fp32'
+  if p not in PRECISIONS:
+    raise ValueError(f'config.training.precision must be one of {PRECISIONS}, got {p!r}')
+  return p
+
+
 def sampling_precision(config):
   """config.sampling.precision: 'fp32' when the key is absent (the reference's configs have none), else checked."""
   try:
