@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (also writes the last timed step's results as DIR/*.npy)
+    python bench.py ... --full                             (also measures and checks everything beyond the headline figure)
 
 One "step" = one call of ``losses.get_step_fn(...)(state, batch)`` -- time sampling, perturbation,
 score-network forward and backward on the HIP engine, gradient all-reduce (N > 1), clip + Adam, EMA --
@@ -12,9 +13,15 @@ the global batch is 128 N.  Rank 0 prints ONE JSON line.
 
 `python bench.py --gpus N` outside a launcher starts the N ranks itself (torch.distributed.run on 127.0.0.1).
 
+A plain run does what the headline figure needs and nothing more: set up, two priming steps, W warm-up steps, K timed steps,
+the --dump-outputs files if asked for, the line.  Everything else below runs in a `--full` run only: the exchange-stream probe
+(N > 1, before the priming steps), and after the timed steps the exchange proxy, the per-kernel event brackets, the arithmetic
+check, the library-GEMM probe, the sampler, the CPU baseline, the parity probe and the other workloads.  The --no-* switches,
+--prof-steps and --sampler-steps drop single legs of a --full run.
+
 The stdout line (short_line) is SHORT by construction -- below 4000 characters, asserted in tests/test_bench_line.py for N = 1 and
 N = 8: the driver keeps the last 8000 characters of stdout, and the round-5 line (20 KB of per-kernel tables) arrived headless.  It
-carries the contract's scalars and `config`, plus:
+carries the contract's scalars and `config`, plus (a plain run: `step_roofline`, `headline` and `detail` only):
   roofline       the contraction kernel with the LARGEST TOTAL TIME in the step (whatever stream it runs on), timed with HIP events
                  on the launch stream in `--prof-steps` eager one-stream steps right after the timed ones:
                  achieved = algorithmic FLOPs per launch / average launch duration, against the ceiling of the matrix pipe for the
@@ -134,6 +141,10 @@ def parse():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=50)      # >= 50 timed steps after >= 10 warm-ups
   ap.add_argument('--warmup', type=int, default=10)
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check everything beyond the headline figure (N > 1: exchange-stream probe; after the '
+                       'timed steps: per-kernel roofline, N = 1: exchange proxy, arithmetic check, library-GEMM probe, sampler, '
+                       'CPU baseline, parity probe, other workloads); off: set up, warm up, time the steps, dump, print the line')
   ap.add_argument('--launch-check', action='store_true',
                   help='only bring up the N-rank process group (RCCL on GPUs, gloo without), count the ranks with one '
                        'all-reduce and print {"launch_check": true, "n_gpus": N}: tests the --gpus launcher without a GPU')
@@ -827,7 +838,7 @@ def main():
   score_model = state['model']
   batch = st.datasets.synthetic_batch(cfg, per_gpu_batch, device=device,
                                       generator=torch.Generator().manual_seed(1234 + rank))
-  if world > 1:
+  if world > 1 and args.full:
     # does the communicator's stream run beside the engine's launch and side streams on every rank?  (reported; a torchrun
     # rendezvous cannot be re-created from here, so a serialised exchange shows up in the line instead of being repaired)
     try:
@@ -855,7 +866,7 @@ def main():
   if args.dump_outputs and rank == 0:
     dump_outputs(args.dump_outputs, losses_, state)     # now: the steps below reuse the loss buffer and move the weights
   proxy = None
-  if world == 1 and not args.no_exchange_proxy and not args.force_exchange:
+  if world == 1 and args.full and not args.no_exchange_proxy and not args.force_exchange:
     try:
       proxy = exchange_proxy(st, step_fn, state, batch, args.steps, device)
       proxy['ms_per_step_without'] = 1e3 * elapsed / args.steps
@@ -866,11 +877,12 @@ def main():
   # recorded inside a replayed graph, so the same step is run `--prof-steps` more times right here with eager
   # launches, every contraction launch bracketed by events on the launch stream.
   timer = None
-  if not args.no_kernel_timer and rank == 0:
+  kernel_timer = args.full and not args.no_kernel_timer
+  if kernel_timer and rank == 0:
     from importlib import import_module
     timer = import_module('soft-truncation_amd.engine.profile').KernelTimer()
     score_model.module.engine().profiler = timer
-  if not args.no_kernel_timer:
+  if kernel_timer:
     for _ in range(args.prof_steps):
       step_fn(state, batch)
     sync()
@@ -924,7 +936,7 @@ def main():
       out['step_roofline'].update({'hbm_algorithmic_GBps': gbs, 'frac_hbm': gbs / 8000.0,
                                    'hbm_note': 'SURVEY.md 8(d) fused-traffic model: 3 x A_f bytes per image + 16 x 4 B per '
                                                'parameter per step, against 8 TB/s'})
-    if world == 1:
+    if world == 1 and args.full:
       out['arithmetic_check'] = arithmetic_check(device)
       try:
         lib_tf = pipe_probe(device)
@@ -937,21 +949,21 @@ def main():
                             'frac_of_library_gemm = 3 x achieved / library rate'})
       except Exception as e:   # reported, never fatal
         out['pipe_probe_error'] = repr(e)
-    if world == 1 and args.sampler_steps > 0:        # like the CPU baseline: only in the single-GPU run
+    if world == 1 and args.full and args.sampler_steps > 0:  # like the CPU baseline: only in the single-GPU run
       try:
         out['sampler'] = sampler_rate(st, cfg, sde, score_model, per_gpu_batch, args.sampler_steps, device)
       except Exception as e:                         # the reference's RVE sampling raises: report, do not fail
         out['sampler'] = {'error': repr(e)[:200]}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(st, cfg_name, args.cpu_batch, args.cpu_steps, args.fir, big_batch=args.cpu_big_batch)
-    if world == 1 and not args.no_parity_probe:
+    if world == 1 and args.full and not args.no_parity_probe:
       try:
         del state, score_model, step_fn              # free the benched replica's arenas before building the probe's
         torch.cuda.empty_cache()
         out['parity_probe'] = parity_probe(st, cfg_name, device)
       except Exception as e:
         out['parity_probe'] = {'error': repr(e)[:300]}
-    if world == 1 and args.workload == 'cifar10' and not args.no_extra_workloads and not args.fir and not args.batch:
+    if world == 1 and args.full and args.workload == 'cifar10' and not args.no_extra_workloads and not args.fir and not args.batch:
       # north_star: "throughput on 32x32 AND 256x256 batches": BASELINE configs[2] / configs[4] nets in the same driver-timed run
       try:
         del state, score_model, step_fn                  # (already gone when the parity probe ran)

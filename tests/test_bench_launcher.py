@@ -32,8 +32,9 @@ def test_bench_single_process_stays_single():
   assert rec['n_gpus'] == 1 and rec['ranks_counted'] == 1
 
 
-def _two_rank_bench(tmp_path, **env_extra):
-  """tests/_bench_worker.py as ranks 0 and 1 over gloo; returns their (stdout, stderr) after checking both exited 0."""
+def _bench_ranks(tmp_path, ranks=2, **env_extra):
+  """tests/_bench_worker.py as ranks 0 .. ranks - 1 over gloo (ranks = 1: one process, no group); returns their (stdout,
+  stderr) after checking every rank exited 0."""
   import socket
   s = socket.socket()
   s.bind(('127.0.0.1', 0))
@@ -41,10 +42,10 @@ def _two_rank_bench(tmp_path, **env_extra):
   s.close()
   subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'oracle')])
   base = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
-  base.update(WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), BENCH_DETAIL=str(tmp_path / 'detail.json'),
+  base.update(WORLD_SIZE=str(ranks), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), BENCH_DETAIL=str(tmp_path / 'detail.json'),
               STK_POISON='1', **env_extra)
   procs = []
-  for rank in range(2):
+  for rank in range(ranks):
     env = dict(base, RANK=str(rank), LOCAL_RANK=str(rank))
     procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, 'tests', '_bench_worker.py')], env=env,
                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
@@ -58,7 +59,7 @@ def _two_rank_bench(tmp_path, **env_extra):
 def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
   """bench.py's real main() at WORLD_SIZE = 2 through to the emitted stdout line, on the CPU checker over gloo
   (tests/_bench_worker.py replaces four seams only): n_gpus = 2, value = GLOBAL images/s, the line is short and alone."""
-  outs = _two_rank_bench(tmp_path)
+  outs = _bench_ranks(tmp_path, BENCH_FULL='1')
   assert outs[1][0] == '', outs[1][0]                       # only rank 0 writes to stdout
   stdout0 = outs[0][0]
   assert stdout0.count('\n') == 1 and len(stdout0) < 4000, stdout0
@@ -68,7 +69,7 @@ def test_bench_main_two_ranks_emits_one_short_line(tmp_path):
   assert line['steps'] == 3 and line['warmup'] == 1 and line['scaling'] == 'weak' and line['unit'] == 'images/s'
   # value is the whole job's rate: global batch x steps / max-over-ranks elapsed
   assert line['value'] == pytest.approx(8 * 1e3 / line['ms_per_step'], rel=1e-3)
-  # no GPU here: the exchange-stream probe cannot run, and the line says so instead of staying silent
+  # --full, no GPU here: the exchange-stream probe cannot run, and the line says so instead of staying silent
   assert line['exchange_serialised'] is True and 'error' in line['exchange_stream']
   detail = json.load(open(line['detail']))
   assert detail['n_gpus'] == 2 and detail['value'] == pytest.approx(line['value'], rel=1e-3)
@@ -83,7 +84,7 @@ def test_bench_dump_outputs_is_repeatable(tmp_path):
   dumps = []
   for run in range(2):
     d = tmp_path / f'dump{run}'
-    outs = _two_rank_bench(tmp_path, BENCH_STEPS='2', BENCH_DUMP=str(d))
+    outs = _bench_ranks(tmp_path, BENCH_STEPS='2', BENCH_DUMP=str(d))
     line = json.loads(outs[0][0])
     assert line['steps'] == 2 and line['ms_per_step'] > 0
     assert line['value'] == pytest.approx(8 * 1e3 / line['ms_per_step'], rel=1e-3)
@@ -96,3 +97,23 @@ def test_bench_dump_outputs_is_repeatable(tmp_path):
     assert v.dtype == np.float32 and np.isfinite(v).all(), name
     assert np.array_equal(v, b[name]), name
   assert not np.array_equal(a['params.npy'], a['ema.npy'])   # the EMA trails the weights
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_measures_only_the_headline(tmp_path):
+  """Without --full, bench.py's real main() sets up, warms up, times the steps, dumps and prints the line -- nothing else: no
+  exchange-stream probe at N = 2; at N = 1 no exchange proxy, arithmetic check, library-GEMM probe, sampler, CPU baseline,
+  parity probe or other workloads; no per-kernel event brackets (--no-kernel-timer is not given: they are --full's too)."""
+  extras = ('exchange_stream', 'exchange_proxy', 'roofline', 'roofline_best', 'kernels', 'arithmetic_check', 'pipe_probe_error',
+            'sampler', 'cpu_baseline', 'parity_probe', 'workloads')
+  for ranks in (2, 1):
+    outs = _bench_ranks(tmp_path, ranks=ranks, BENCH_DUMP=str(tmp_path / f'dump{ranks}'), BENCH_KERNEL_TIMER='1')
+    line = json.loads(outs[0][0])
+    detail = json.load(open(line['detail']))
+    assert line['n_gpus'] == ranks and line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0
+    assert line['value'] == pytest.approx(4 * ranks * 1e3 / line['ms_per_step'], rel=1e-3)
+    assert set(line['headline']) == {'cifar10'} and 'step_roofline' in line
+    for k in extras:
+      assert k not in line and k not in detail, (ranks, k)
+    assert 'exchange_serialised' not in line
+    assert sorted(os.listdir(tmp_path / f'dump{ranks}')) == ['ema.npy', 'losses.npy', 'params.npy']

@@ -11,7 +11,7 @@ W="$1"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/round_$W
 rm -rf $OUT; mkdir -p $OUT
-Q="--workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-exchange-proxy --no-extra-workloads --no-parity-probe --sampler-steps 0"
+Q="--full --workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-exchange-proxy --no-extra-workloads --no-parity-probe --sampler-steps 0"
 python bench.py $Q --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
 BENCH="env STK_WGRAD_STREAM=0 python bench.py $Q --detail /tmp/pw_detail.json"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
