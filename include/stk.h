@@ -162,9 +162,9 @@ int stk_gn_param_grad_batch(const StkGnFoldDesc* descs_dev, int count, int max_C
 long stk_conv2d_fwd_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW,
                              int stride, int pad);
 /* Which kernel family a call with full scratch takes (for profiling labels): dir 0 fwd, 1 dgrad, 2 wgrad;
- * returns 0 / 1 = f32-input MFMA with 64 / 128 tiles, (2 = the bf16 three-way split of rounds 1-5: retired) 3 = f32-input all-taps wgrad,
- * 4 = streaming kernel for a <= 4 channel side (stem, head, 3-channel pyramids), 5 = fp16 two-way split,
- * < 0 = unsupported shape. */
+ * returns 0 / 1 = f32-input MFMA with 64 / 128 tiles, 3 = f32-input all-taps wgrad,
+ * 4 = streaming kernel for a <= 4 channel side (stem, head, 3-channel pyramids), 5 = the split path (fp16 two-way split),
+ * < 0 = unsupported shape.  (2 is never returned: it was a retired kernel family.) */
 int stk_conv2d_variant(int dir, int C1, int C2, int N, int H, int W, int Cout, int OH, int OW,
                        int KH, int KW, int stride, int pad, int w_layout);
 long stk_conv2d_dgrad_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW,

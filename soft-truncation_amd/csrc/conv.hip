@@ -665,7 +665,6 @@ inline void launch_slab_sum(const ConvP& p, int splits, int M, long Ng, int dgra
   }
 }
 
-#include "conv_x3.h"
 #include "conv_thin.h"
 #include "conv_x2.h"
 #include "conv_pl.h"
@@ -987,14 +986,16 @@ inline int fill_common(ConvP& p, int N, int H, int W, int C1, int C2, int Cout, 
   return STK_OK;
 }
 
-// The bf16 three-way-split kernel (conv_x3.h) takes 3x3 / stride 1 / pad 1 and 1x1 / stride 1 layers whose channel
-// count is a multiple of the 32-wide k chunk (and, for a concat input, whose first source is too).  With at least
-// 192 tiles of 128 x 128 a workgroup owns a whole output tile.  Smaller problems (the 8x8 and 4x4 maps: 128 / 32
-// tiles at batch 128, where one workgroup per CU has nothing to overlap with) are split over K into partial slabs
-// that a second kernel sums in a fixed order and finishes with the usual epilogue.
-struct X3Plan { int ok; int splits; int chunks_per_split; long slab; int t64; int gps; };
-inline X3Plan x3_plan(const ConvP& p, int Kc, int S1, int S2, int M, long Ng) {
-  X3Plan r = {0, 1, 0, 0, 0, 0};
+// ---- the split path (conv_x2.h, conv_pl.h, conv_x2d.h, conv_x2w.h): fp16 two-way split, 3 MFMAs per fp32 product ----------
+// Forward and data gradient take it for 3x3 / stride 1 / pad 1 and 1x1 / stride 1 layers whose channel count is a multiple
+// of the 32-wide k chunk (and, for a concat input, whose first source is too).  With at least 192 tiles of 128 x 128 a
+// workgroup owns a whole output tile.  Smaller problems (the 8x8 and 4x4 maps: 128 / 32 tiles at batch 128, where one
+// workgroup per CU has nothing to overlap with) are split over K into partial slabs that a second kernel sums in a fixed
+// order and finishes with the usual epilogue.  M: output rows, Kc: channels reduced over, S1 / S2: channels of the two
+// sources.
+struct SplitPlan { int ok; int splits; int chunks_per_split; long slab; int t64; int gps; };
+inline SplitPlan split_plan(const ConvP& p, int Kc, int S1, int S2, int M, long Ng) {
+  SplitPlan r = {0, 1, 0, 0, 0, 0};
   const long big = (long)p.N * p.HW * 4 * (S1 > S2 ? S1 : S2);       // buffer loads: 32-bit byte offsets, bit 31 = dead lane
   const bool geom = (p.taps == 9 && p.pad == 1) || (p.taps == 1 && p.pad == 0);
   if (!(big < 0x7fffffffL && geom && p.stride == 1 && p.OH == p.H && p.OW == p.W && Kc % 32 == 0 &&
@@ -1022,136 +1023,134 @@ inline X3Plan x3_plan(const ConvP& p, int Kc, int S1, int S2, int M, long Ng) {
   r.ok = 1;
   return r;
 }
-// Plan of a PLANE-operand call (single source): the same plan (the 64 x 64-tile kernel of round 5 lost its in-step A/B and is retired)
-inline X3Plan x3_plan_pl(const ConvP& p, int Kc, int M, long Ng) { return x3_plan(p, Kc, Kc, 0, M, Ng); }
-inline long x3_ws_bytes(const X3Plan& r, int M, int Kc, int taps) {
-  // [prepared weights of this call][|x| partial maxima, 2 x 256 floats][K-split slabs], each 256-byte aligned
-  return r.ok ? x3::wp_bytes(M, Kc, taps) + 2048 + 1024 + (r.splits > 1 ? r.splits * r.slab * 4 : 0) : 0;
+// the plans of the two directions (fill_common'd p; a plane operand is the single-source case)
+inline SplitPlan fwd_split_plan(const ConvP& p) { return split_plan(p, p.Cin, p.C1, p.C2, p.Cout, (long)p.N * p.OHW); }
+inline SplitPlan dgrad_split_plan(const ConvP& p) { return split_plan(p, p.Cout, p.Cout, 0, p.Cin, (long)p.N * p.HW); }
+// The scratch of a split-path call: [prepared weights][|x| partial maxima, 2 x 256 floats][K-split slabs], each at a 256-byte
+// boundary.  Offsets count from ws rounded up to 256 bytes; `bytes` (0 when the plan is not ok) also covers that rounding.
+struct SplitWs { long xpart, part, bytes; };
+inline long align256(long v) { return (v + 255) & ~255L; }
+inline SplitWs split_ws(const SplitPlan& r, int M, int Kc, int taps) {
+  SplitWs o;
+  o.xpart = align256(x2::wp_bytes(M, Kc, taps));
+  o.part = align256(o.xpart + 2L * x2::NPART * 4);
+  o.bytes = r.ok ? 255 + o.part + (r.splits > 1 ? r.splits * r.slab * 4 : 0) : 0;
+  return o;
 }
-// dgrad = 1: rows are input channels, k output channels, taps flipped.  Every split kernel is the fp16 two-way split (3 MFMAs per
-// fp32 product, conv_x2.h / conv_x2d.h / conv_x2w.h); the bf16 three-way-split kernels of round 1 (six MFMAs) were the fallback
-// of a debugging switch until round 5 and are retired (DESIGN.md "Retired").
-
-inline void x3_weight_strides(const ConvP& p, int dgrad, long& sm, long& sk) {
+// Weight strides of the prepared rows: dgrad = 1: rows are input channels, k output channels (the taps are flipped by wprep).
+inline void split_weight_strides(const ConvP& p, int dgrad, long& sm, long& sk) {
   if (p.w_layout == 0) { sm = dgrad ? p.taps : (long)p.Cin * p.taps; sk = dgrad ? (long)p.Cin * p.taps : p.taps; }
   else { sm = dgrad ? p.Cout : 1; sk = dgrad ? 1 : p.Cout; }          // NIN w[Cin][Cout]
 }
-// wp_ready: weights already prepared by stk_conv2d_wprep_batch (then ws only holds the K-split slabs)
-// x1: the one-product forms (include/stk_fp16.h, include/stk_fp16_train.h): hi(w) hi(x) only.  With planes a chunk then covers a PAIR of 32-channel
-// groups (conv_x2d.h), so the chunk count roughly halves; the plan keeps its number of K splits (and slab layout) unless the
-// halved count leaves some empty.
-inline X3Plan x1_plan(const X3Plan& r, int nch1) {
-  X3Plan r1 = r;
+// The one-product forms (include/stk_fp16.h, include/stk_fp16_train.h): hi(w) hi(x) only.  With planes a chunk then covers a
+// PAIR of 32-channel groups (conv_x2d.h), so the chunk count roughly halves; the plan keeps its number of K splits (and slab
+// layout) unless the halved count leaves some empty.
+inline SplitPlan x1_plan(const SplitPlan& r, int nch1) {
+  SplitPlan r1 = r;
   r1.chunks_per_split = (nch1 + r.splits - 1) / r.splits;
   r1.splits = (nch1 + r1.chunks_per_split - 1) / r1.chunks_per_split;
   return r1;
 }
-template <class EP>
-int launch_x3(ConvP p, const X3Plan& r0, const float* s1, int S1, const float* s2, int S2, int M, long Ng, int dgrad,
-              void* ws, hipStream_t s, const void* wp_ready = nullptr, float* amax = nullptr,
-              const void* planes = nullptr, const float* planes_amax = nullptr, bool amax_valid = false, bool x1 = false) {
-  x3::Src q;
-  q.s1 = s1; q.s2 = S2 > 0 ? s2 : s1; q.S1 = S1; q.S2 = S2; q.Kc = S1 + S2; q.Mpad = x3::pad128(M); q.taps = p.taps;
-  q.pl = static_cast<const unsigned char*>(planes); q.pl_stride = planes ? pl::plane_bytes(p.N, S1, p.HW) : 0;
-  unsigned short* wp = reinterpret_cast<unsigned short*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  float* xpart = reinterpret_cast<float*>(((uintptr_t)wp + x3::wp_bytes(M, q.Kc, p.taps) + 255) & ~(uintptr_t)255);
-  p.part = reinterpret_cast<float*>(((uintptr_t)(xpart + 2 * x2::NPART) + 255) & ~(uintptr_t)255);
-  p.part_stride = r0.slab;
-  {
-    // fp16 two-way split (conv_x2.h): |x| maxima of the activation operand(s), weights prepared here unless the caller did
-    // with a caller-owned amax buffer (768 floats: |x1|, |x2|, |dy| partials) the maxima stay available to the layer's
-    // weight gradient, which would otherwise repeat these passes
-    if (amax) xpart = amax + (dgrad ? 2 * x2::NPART : 0);
-    if (planes) {
-      xpart = const_cast<float*>(planes_amax);      // the scale record the planes were written with
-    } else if (!(amax_valid && amax)) {   // amax_valid: the caller's record already holds this operand's maxima (both sources)
-      hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, s, s1, (long)p.N * S1 * p.HW, xpart);
-      if (S2 > 0)
-        hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, s, s2, (long)p.N * S2 * p.HW,
-                           xpart + x2::NPART);
-      STK_CHECK_LAUNCH();
-    }
-    const int nx = S2 > 0 ? 2 * x2::NPART : x2::NPART;
-    if (wp_ready) {
-      q.wp = static_cast<const unsigned short*>(wp_ready);
-    } else {
-      x2::WprepDesc one = {};
-      one.w = p.w; one.wp = reinterpret_cast<unsigned char*>(wp); one.M = M; one.Kc = q.Kc; one.Mpad = q.Mpad;
-      one.taps = p.taps; one.flip = dgrad;
-      x3_weight_strides(p, dgrad, one.sm, one.sk);
-      hipLaunchKernelGGL(x2::wamax_kernel, dim3(x2::WPART, 1), dim3(256), 0, s, nullptr, one);
-      hipLaunchKernelGGL(x2::wprep_kernel, dim3((unsigned)stk_cdiv((long)q.Mpad * q.Kc, 256L)), dim3(256), 0, s, nullptr, one);
-      STK_CHECK_LAUNCH();
-      q.wp = wp;
-    }
-    const int tm = q.Mpad / 128, tn = stk_cdiv((int)Ng, 128);
-    const int nch = planes && x1 ? p.taps * ((q.Kc / x3::KC + 1) / 2) : p.taps * (q.Kc / x3::KC);
-    const X3Plan r = planes && x1 ? x1_plan(r0, nch) : r0;
-    // one-product kernels: forward (include/stk_fp16.h) and data gradient (include/stk_fp16_train.h) alike
-#define STK_X1(E) OneProduct<E>
-#define STK_X1L(DUAL, TAPS) x2::ActLoader16<DUAL, TAPS>
-    const dim3 grid((unsigned)(tm * tn * r.splits));
-#define STK_X2_LAUNCH(E, DUAL, TAPS)                                                                              \
-  if (x1) hipLaunchKernelGGL((x2::gemm_kernel<STK_X1L(DUAL, TAPS), STK_X1(E)>), grid, dim3(256), 0, s, p, q, M, \
-                             (int)Ng, tm, tn, nch, r.chunks_per_split, xpart, nx);                                \
-  else hipLaunchKernelGGL((x2::gemm_kernel<x2::ActLoader<DUAL, TAPS>, E>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, \
-                     nch, r.chunks_per_split, xpart, nx)
-#define STK_PL_LAUNCH(E, TAPS)                                                                                    \
-  if (x1) {                                                                                                       \
-    /* one product, two channel groups per chunk (conv_x2d.h, X1) */                                              \
-    if (x2d::halo_ok(p, TAPS, r0.splits)) {                                                                       \
-      if (p.W == 64)                                                                                              \
-        hipLaunchKernelGGL((x2d::gemm_halo_kernel<64, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-      else if (p.W == 32)                                                                                         \
-        hipLaunchKernelGGL((x2d::gemm_halo_kernel<32, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-      else                                                                                                        \
-        hipLaunchKernelGGL((x2d::gemm_halo_kernel<16, STK_X1(E), 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-    } else {                                                                                                      \
-      hipLaunchKernelGGL((x2d::gemm_kernel<TAPS, 128, STK_X1(E)>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch, \
-                         r.chunks_per_split, xpart, nx);                                                          \
-    }                                                                                                             \
-  } else if (x2d::halo_ok(p, TAPS, r.splits)) {                                                                   \
-    /* one halo tile of the activations per channel group serves the nine taps */                                 \
-    if (p.W == 64)                                                                                                \
-      hipLaunchKernelGGL((x2d::gemm_halo_kernel<64, E, 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-    else if (p.W == 32)                                                                                           \
-      hipLaunchKernelGGL((x2d::gemm_halo_kernel<32, E, 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-    else                                                                                                          \
-      hipLaunchKernelGGL((x2d::gemm_halo_kernel<16, E, 1>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch / 9, xpart, nx); \
-  } else {                                                                                                        \
-    /* LDS-DMA staging of both operands, one tap x 32 channels per chunk (conv_x2d.h) */                          \
-    hipLaunchKernelGGL((x2d::gemm_kernel<TAPS, 128, E>), grid, dim3(256), 0, s, p, q, M, (int)Ng, tm, tn, nch,    \
-                       r.chunks_per_split, xpart, nx);                                                            \
+
+// The GEMM of a split-path call, written once for both forms: E is the epilogue (EpFwd / EpDgrad / EpSlab), wrapped in
+// OneProduct<> for the one-product form, which stages the hi planes only.
+struct SplitGemm {
+  ConvP p; x2::Src q; int M, Ng, tm, tn, nch, chunks_per_split; const float* xpart; int nx;
+  bool dual, planes, halo; dim3 grid; hipStream_t s;
+};
+template <class E, int TAPS>
+void split_gemm_taps(const SplitGemm& g) {
+  constexpr bool X1 = is_x1<E>::value;
+  if (!g.planes) {                       // fp32 activations, split while they are staged (x2::ActLoader)
+    using A1 = std::conditional_t<X1, x2::ActLoader16<false, TAPS>, x2::ActLoader<false, TAPS>>;
+    using A2 = std::conditional_t<X1, x2::ActLoader16<true, TAPS>, x2::ActLoader<true, TAPS>>;
+    if (g.dual) hipLaunchKernelGGL((x2::gemm_kernel<A2, E>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch,
+                                   g.chunks_per_split, g.xpart, g.nx);
+    else hipLaunchKernelGGL((x2::gemm_kernel<A1, E>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch,
+                            g.chunks_per_split, g.xpart, g.nx);
+  } else if (g.halo) {                   // one halo tile of the activation planes per channel group serves the nine taps
+    if (g.p.W == 64)
+      hipLaunchKernelGGL((x2d::gemm_halo_kernel<64, E, 1>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch / 9, g.xpart, g.nx);
+    else if (g.p.W == 32)
+      hipLaunchKernelGGL((x2d::gemm_halo_kernel<32, E, 1>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch / 9, g.xpart, g.nx);
+    else
+      hipLaunchKernelGGL((x2d::gemm_halo_kernel<16, E, 1>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch / 9, g.xpart, g.nx);
+  } else {                               // LDS-DMA staging of both operands, one tap x 32 channels per chunk
+    hipLaunchKernelGGL((x2d::gemm_kernel<TAPS, 128, E>), g.grid, dim3(256), 0, g.s, g.p, g.q, g.M, g.Ng, g.tm, g.tn, g.nch,
+                       g.chunks_per_split, g.xpart, g.nx);
   }
-#define STK_X2_LAUNCH_E(E)                                                                                        \
-  if (planes) { if (p.taps == 9) { STK_PL_LAUNCH(E, 9); } else { STK_PL_LAUNCH(E, 1); } }                         \
-  else if (p.taps == 9) { if (S2 > 0) STK_X2_LAUNCH(E, true, 9); else STK_X2_LAUNCH(E, false, 9); }               \
-  else { if (S2 > 0) STK_X2_LAUNCH(E, true, 1); else STK_X2_LAUNCH(E, false, 1); }
-    if (r0.splits == 1) {
-      STK_X2_LAUNCH_E(EP)
-      STK_CHECK_LAUNCH();
-      return STK_OK;
-    }
-    STK_X2_LAUNCH_E(EpSlab)
+}
+template <class E>
+void split_gemm(const SplitGemm& g) {
+  if (g.p.taps == 9) split_gemm_taps<E, 9>(g);
+  else split_gemm_taps<E, 1>(g);
+}
+
+// One forward (dgrad = 0) or data-gradient (dgrad = 1) call on the split path.  Operand: fp32 sources s1 / s2 (|x| maxima
+// taken here, or read from the caller's record `amax` when amax_valid), or planes with their scale record planes_amax.
+// wp_ready: weights already prepared by stk_conv2d_wprep_batch, else prepared into ws.  x1: the one-product form.
+template <class EP>
+int launch_split(ConvP p, const SplitPlan& r0, const float* s1, int S1, const float* s2, int S2, int M, long Ng, int dgrad,
+                 void* ws, hipStream_t s, const void* wp_ready, float* amax, const void* planes, const float* planes_amax,
+                 bool amax_valid, bool x1) {
+  x2::Src q;
+  q.s1 = s1; q.s2 = S2 > 0 ? s2 : s1; q.S1 = S1; q.S2 = S2; q.Kc = S1 + S2; q.Mpad = x2::pad128(M); q.taps = p.taps;
+  q.pl = static_cast<const unsigned char*>(planes); q.pl_stride = planes ? pl::plane_bytes(p.N, S1, p.HW) : 0;
+  const SplitWs lay = split_ws(r0, M, q.Kc, p.taps);
+  unsigned char* base = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  float* xpart = reinterpret_cast<float*>(base + lay.xpart);
+  p.part = reinterpret_cast<float*>(base + lay.part);
+  p.part_stride = r0.slab;
+  // with a caller-owned amax buffer (768 floats: |x1|, |x2|, |dy| partials) the maxima stay available to the layer's
+  // weight gradient, which would otherwise repeat these passes
+  if (amax) xpart = amax + (dgrad ? 2 * x2::NPART : 0);
+  if (planes) {
+    xpart = const_cast<float*>(planes_amax);      // the scale record the planes were written with
+  } else if (!(amax_valid && amax)) {   // amax_valid: the caller's record already holds this operand's maxima (both sources)
+    hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, s, s1, (long)p.N * S1 * p.HW, xpart);
+    if (S2 > 0)
+      hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, s, s2, (long)p.N * S2 * p.HW,
+                         xpart + x2::NPART);
     STK_CHECK_LAUNCH();
-    launch_slab_sum(p, r.splits, M, Ng, dgrad, s);
-#undef STK_X2_LAUNCH_E
-#undef STK_X2_LAUNCH
-#undef STK_PL_LAUNCH
-#undef STK_X1
-#undef STK_X1L
+  }
+  if (wp_ready) {
+    q.wp = static_cast<const unsigned short*>(wp_ready);
+  } else {
+    x2::WprepDesc one = {};
+    one.w = p.w; one.wp = base; one.M = M; one.Kc = q.Kc; one.Mpad = q.Mpad;
+    one.taps = p.taps; one.flip = dgrad;
+    split_weight_strides(p, dgrad, one.sm, one.sk);
+    hipLaunchKernelGGL(x2::wamax_kernel, dim3(x2::WPART, 1), dim3(256), 0, s, nullptr, one);
+    hipLaunchKernelGGL(x2::wprep_kernel, dim3((unsigned)stk_cdiv((long)q.Mpad * q.Kc, 256L)), dim3(256), 0, s, nullptr, one);
+    STK_CHECK_LAUNCH();
+    q.wp = reinterpret_cast<const unsigned short*>(base);
+  }
+  const int nch = planes && x1 ? p.taps * ((q.Kc / x2::KC + 1) / 2) : p.taps * (q.Kc / x2::KC);
+  const SplitPlan r = planes && x1 ? x1_plan(r0, nch) : r0;
+  SplitGemm g = {p, q, M, (int)Ng, q.Mpad / 128, stk_cdiv((int)Ng, 128), nch, r.chunks_per_split, xpart,
+                 S2 > 0 ? 2 * x2::NPART : x2::NPART, S2 > 0, planes != nullptr, planes && x2d::halo_ok(p, p.taps, r0.splits),
+                 dim3(), s};
+  g.grid = dim3((unsigned)(g.tm * g.tn * r.splits));
+  if (r0.splits == 1) {
+    if (x1) split_gemm<OneProduct<EP>>(g);
+    else split_gemm<EP>(g);
     STK_CHECK_LAUNCH();
     return STK_OK;
   }
+  if (x1) split_gemm<OneProduct<EpSlab>>(g);
+  else split_gemm<EpSlab>(g);
+  STK_CHECK_LAUNCH();
+  launch_slab_sum(p, r.splits, M, Ng, dgrad, s);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
 }
 
-// Weight gradient on the split kernel: 3x3 / stride 1 / pad 1 or 1x1 / stride 1, power-of-two maps of >= 8 columns and
-// >= 32 pixels, enough channels to fill 128-wide tiles.  One GEMM per tap, K (= pixels) split so that <= 512
-// workgroups run.
-struct X3WgradPlan { int ok; int splits; int chunks_per_split; long slab; int rows3; };
-inline X3WgradPlan x3_wgrad_plan(int C1, int C2, int N, int Cout, int H, int W, int OH, int OW, int KH, int KW, int stride,
-                                 int pad) {
-  X3WgradPlan q = {0, 0, 0, 0, 0};
+// Weight gradient on the split path: 3x3 / stride 1 / pad 1 or 1x1 / stride 1, power-of-two maps of >= 4 columns and
+// >= 16 pixels, enough channels to fill the tiles.  K (= pixels) split so that <= 512 workgroups run.
+struct SplitWgradPlan { int ok; int splits; int chunks_per_split; long slab; int rows3; };
+inline SplitWgradPlan split_wgrad_plan(int C1, int C2, int N, int Cout, int H, int W, int OH, int OW, int KH, int KW,
+                                       int stride, int pad) {
+  SplitWgradPlan q = {0, 0, 0, 0, 0};
   const int Cin = C1 + C2;
   const long K = (long)N * H * W;
   const int cmax = Cout > C1 ? (Cout > C2 ? Cout : C2) : (C1 > C2 ? C1 : C2);
@@ -1180,6 +1179,44 @@ inline X3WgradPlan x3_wgrad_plan(int C1, int C2, int N, int Cout, int H, int W, 
   q.slab = (long)Cout * Cin * taps;
   q.ok = 1;
   return q;
+}
+// The plane-operand weight gradient x2w::wgrad_kernel<COLS, FORM>, FORM = groups | X1_FORM (the one-product form).
+template <int FORM>
+void launch_x2w(const x2w::Args& a, int W, dim3 grid, hipStream_t s) {
+  const dim3 block(256 * (FORM & 15));
+  if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, FORM>), grid, block, 0, s, a);
+  else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, FORM>), grid, block, 0, s, a);
+  else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, FORM>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((x2w::wgrad_kernel<4, FORM>), grid, block, 0, s, a);
+}
+// The per-tap split weight gradient x2::wgemm_kernel: dy rows unshifted (RowsU); x rows shifted by the tap (RowsB, by map
+// width) or, for a 1x1 layer, unshifted.  X1: the one-product form -- hi-plane loaders (RowsU16 / RowsB16), the OneProduct
+// epilogue, no schedule pins.
+struct WgemmArgs {
+  ConvP p; int tm, tn, nch, chunks_per_split; const float* dyp; const float* xp; int nx; dim3 grid; hipStream_t s;
+};
+template <bool X1, class BL>
+void launch_wgemm_rows(const WgemmArgs& g) {
+  using AL = std::conditional_t<X1, x2::RowsU16<false, false>, x2::RowsU<false, false>>;
+  using E = std::conditional_t<X1, OneProduct<EpWgrad>, EpWgrad>;
+  hipLaunchKernelGGL((x2::wgemm_kernel<AL, BL, E, !X1>), g.grid, dim3(256), 0, g.s, g.p, g.p.Cout, g.p.Cin, g.tm, g.tn, g.nch,
+                     g.chunks_per_split, g.p.taps, g.dyp, g.xp, g.nx);
+}
+template <bool X1, bool DUAL>
+void launch_wgemm_src(const WgemmArgs& g) {
+  if (g.p.taps == 1)
+    launch_wgemm_rows<X1, std::conditional_t<X1, x2::RowsU16<true, DUAL>, x2::RowsU<true, DUAL>>>(g);
+  else if (g.p.W >= 16)
+    launch_wgemm_rows<X1, std::conditional_t<X1, x2::RowsB16<DUAL, 16>, x2::RowsB<DUAL, 16>>>(g);
+  else if (g.p.W == 8)
+    launch_wgemm_rows<X1, std::conditional_t<X1, x2::RowsB16<DUAL, 8>, x2::RowsB<DUAL, 8>>>(g);
+  else
+    launch_wgemm_rows<X1, std::conditional_t<X1, x2::RowsB16<DUAL, 4>, x2::RowsB<DUAL, 4>>>(g);
+}
+template <bool X1>
+void launch_wgemm(const WgemmArgs& g) {
+  if (g.p.C2 > 0) launch_wgemm_src<X1, true>(g);
+  else launch_wgemm_src<X1, false>(g);
 }
 
 struct WgradPlan { int big; int splits; int k_per_split; long slab; int mode9; };
@@ -1232,27 +1269,7 @@ inline WgradPlan wgrad_plan(int Cin, int N, int Cout, int OH, int OW, int KH, in
 
 extern "C" {
 
-static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
-                    const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
-                    float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                    const void* wp, float* amax, void* ws, long ws_bytes, void* stream, bool x_rec_valid, bool f16x1 = false);
-
-int stk_conv2d_fwd_wp_f32(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
-                          const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
-                          float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                          const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
-  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
-                  pad, wp, amax, ws, ws_bytes, stream, false);
-}
-/* ... with the |x1| / |x2| scale records already in amax[0..256) / amax[256..512) (stk_gn_fwd_pl_max_f32): no |x| pass */
-int stk_conv2d_fwd_rec_f32(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
-                           const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
-                           float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                           const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
-  if (!amax) return STK_EINVAL;
-  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
-                  pad, wp, amax, ws, ws_bytes, stream, true);
-}
+/* ---- forward ---------------------------------------------------------------------------------------------------------- */
 static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
                     const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
                     float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
@@ -1287,9 +1304,9 @@ static int fwd_impl(const float* x1, int C1, const float* x2, int C2, const floa
       return STK_OK;
     }
   }
-  const X3Plan xr = x3_plan(p, p.Cin, C1, C2, Cout, Ng);
-  if (ws && xr.ok && ws_bytes >= x3_ws_bytes(xr, Cout, p.Cin, p.taps))
-    return launch_x3<EpFwd>(p, xr, x1, C1, x2, C2, Cout, Ng, 0, ws, s, wp, amax, nullptr, nullptr, x_rec_valid, f16x1);
+  const SplitPlan xr = fwd_split_plan(p);
+  if (ws && xr.ok && ws_bytes >= split_ws(xr, Cout, p.Cin, p.taps).bytes)
+    return launch_split<EpFwd>(p, xr, x1, C1, x2, C2, Cout, Ng, 0, ws, s, wp, amax, nullptr, nullptr, x_rec_valid, f16x1);
   if (wp) return STK_EINVAL;      // prepared weights exist only for the shapes stk_conv2d_wp_bytes reports
   if (p.taps == 9) {
     using CB = Cfg<128, 128, 36>; using CS = Cfg<64, 64, 36>;
@@ -1321,26 +1338,42 @@ int stk_conv2d_fwd_f32(const float* x1, int C1, const float* x2, int C2, const f
                                KH, KW, stride, pad, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
-static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
-                      int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                      int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                      void* stream, bool dy_rec_valid, bool f16x1 = false);
-int stk_conv2d_dgrad_wp_f32(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
-                            int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                            int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                            void* stream) {
-  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
-                    amax, ws, ws_bytes, stream, false);
+int stk_conv2d_fwd_wp_f32(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                          const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                          float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                          const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, false, false);
 }
-/* ... with the |dy| scale record already in amax[512..768) (written by stk_bias_grad_amax*_f32): no |dy| pass */
-int stk_conv2d_dgrad_rec_f32(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
-                             int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                             int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                             void* stream) {
+
+/* ... with the |x1| / |x2| scale records already in amax[0..256) / amax[256..512) (stk_gn_fwd_pl_max_f32): no |x| pass */
+int stk_conv2d_fwd_rec_f32(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                           const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                           float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                           const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
   if (!amax) return STK_EINVAL;
-  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
-                    amax, ws, ws_bytes, stream, true);
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, true, false);
 }
+
+int stk_conv2d_fwd_wp_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                            const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                            float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                            const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, false, true);
+}
+
+int stk_conv2d_fwd_rec_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
+                             const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
+                             float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
+                             const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+  if (!amax) return STK_EINVAL;
+  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
+                  pad, wp, amax, ws, ws_bytes, stream, true, true);
+}
+
+/* ---- data gradient ---------------------------------------------------------------------------------------------------- */
 static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
                       int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
                       int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
@@ -1365,9 +1398,9 @@ static int dgrad_impl(const float* dy, const float* w, int w_layout, float* dx1,
     STK_CHECK_LAUNCH();
     return STK_OK;
   }
-  const X3Plan xr = x3_plan(p, Cout, Cout, 0, Cin, Ng);
-  if (ws && xr.ok && ws_bytes >= x3_ws_bytes(xr, Cin, Cout, p.taps))
-    return launch_x3<EpDgrad>(p, xr, dy, Cout, nullptr, 0, Cin, Ng, 1, ws, s, wp, amax, nullptr, nullptr, dy_rec_valid, f16x1);
+  const SplitPlan xr = dgrad_split_plan(p);
+  if (ws && xr.ok && ws_bytes >= split_ws(xr, Cin, Cout, p.taps).bytes)
+    return launch_split<EpDgrad>(p, xr, dy, Cout, nullptr, 0, Cin, Ng, 1, ws, s, wp, amax, nullptr, nullptr, dy_rec_valid, f16x1);
   if (wp) return STK_EINVAL;
   if (p.taps == 9) {
     using CB = Cfg<128, 128, 36>; using CS = Cfg<64, 64, 36>;
@@ -1392,317 +1425,42 @@ int stk_conv2d_dgrad_f32(const float* dy, const float* w, int w_layout, float* d
                                  pad, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
-/* ---- planes (conv_pl.h): activations pre-split into two fp16 planes, [split][n][c / 32][pixel][c % 32] ---- */
-long stk_planes_bytes(int N, int C, int HW) {
-  if (N <= 0 || C <= 0 || HW <= 0) return 0;
-  return 2 * pl::plane_bytes(N, C, HW);
+int stk_conv2d_dgrad_wp_f32(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                            int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                            int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                            void* stream) {
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, false, false);
 }
 
-int stk_amax_partial_f32(const float* x, long n, float* part, void* stream) {
-  if (!x || !part || n <= 0) return STK_EINVAL;
-  hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, (hipStream_t)stream, x, n, part);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
-}
-
-int stk_split_planes_f32(const float* x, int N, int C, int HW, const float* amax, int namax, void* planes, void* stream) {
-  if (!x || !amax || !planes || N <= 0 || C <= 0 || HW <= 0 || namax <= 0) return STK_EINVAL;
-  if (2 * pl::plane_bytes(N, C, HW) >= 0x7fffffffL) return STK_EUNSUPPORTED;      // 32-bit buffer offsets in the consumers
-  const long blocks = (long)N * ((C + 31) / 32) * stk_cdiv(HW, pl::SP_PIX);
-  hipLaunchKernelGGL(pl::split_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, N, C, HW, amax,
-                     namax, static_cast<unsigned char*>(planes), pl::plane_bytes(N, C, HW));
-  STK_CHECK_LAUNCH();
-  return STK_OK;
-}
-
-/* 1 when the forward (dir 0) / data-gradient (dir 1) call of this shape can read its activation operand (x resp. dy) as
- * planes: exactly the shapes that take the fp16 split kernel with a single-source operand. */
-int stk_conv2d_pl_ok(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
-  if (stride != 1 || pad != KH / 2) return 0;
-  const long Ng = (long)N * p.HW;
-  if (dir == 0) {
-    if (C2 > 0 || p.Cin <= 4 || Cout <= 4) return 0;        // two sources / thin-side streaming kernels
-    return x3_plan(p, p.Cin, C1, 0, Cout, Ng).ok;
-  }
-  if (dir == 1) {
-    if (Cout <= 4 || p.Cin <= 4) return 0;
-    return x3_plan(p, Cout, Cout, 0, p.Cin, Ng).ok;
-  }
-  return 0;
-}
-
-/* number of K splits the plane-operand forward (dir 0) / data-gradient (dir 1) call of this shape runs with: 1 = one
- * launch of x2d::gemm_kernel<.., EpFwd / EpDgrad>, > 1 = EpSlab partial tiles + a slab-sum launch (small maps),
- * 0 = the shape does not take plane operands.  (Profiler labels: bench.py names kernels by their rocprof symbol.) */
-int stk_conv2d_pl_ksplit(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW) {
-  if (!stk_conv2d_pl_ok(dir, C1, C2, N, H, W, Cout, KH, KW, 1, KH / 2)) return 0;
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2)) return 0;
-  const long Ng = (long)N * p.HW;
-  return dir == 0 ? x3_plan_pl(p, p.Cin, Cout, Ng).splits : x3_plan_pl(p, Cout, p.Cin, Ng).splits;
-}
-
-static int fwd_pl_impl(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
-                       const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
-                       int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
-  if (!xpl || !xamax || !w || !y || out_div == 0.f || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
-    return STK_EINVAL;
-  if (!stk_conv2d_pl_ok(0, C, 0, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
-  ConvP p = {};
-  fill_common(p, N, H, W, C, 0, Cout, H, W, KH, KW, 1, KH / 2);
-  p.w = w; p.w_layout = w_layout; p.bias = bias; p.temb = temb; p.temb_stride = temb_stride; p.res = res;
-  p.inv_div = 1.f / out_div; p.use_div = out_div != 1.f; p.y = y;
-  const long Ng = (long)N * p.HW;
-  const X3Plan xr = x3_plan_pl(p, C, Cout, Ng);
-  if (!ws || ws_bytes < x3_ws_bytes(xr, Cout, C, p.taps)) return STK_EINVAL;
-  return launch_x3<EpFwd>(p, xr, nullptr, C, nullptr, 0, Cout, Ng, 0, ws, (hipStream_t)stream, wp, nullptr, xpl, xamax, false,
-                          f16x1);
-}
-int stk_conv2d_fwd_pl_f32(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
-                          const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
-                          int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
-  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
-                     ws_bytes, stream, false);
-}
-
-/* ---- include/stk_fp16.h: the one-product twins of the three forward entries -------------------------------------------- */
-int stk_conv2d_fwd_pl_f16x1(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
-                            const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
-                            int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
-  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
-                     ws_bytes, stream, true);
-}
-int stk_conv2d_fwd_wp_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
-                            const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
-                            float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                            const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
-  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
-                  pad, wp, amax, ws, ws_bytes, stream, false, true);
-}
-int stk_conv2d_fwd_rec_f16x1(const float* x1, int C1, const float* x2, int C2, const float* w, int w_layout,
-                             const float* bias, const float* temb, int temb_stride, const float* res, float out_div,
-                             float* y, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW, int stride, int pad,
-                             const void* wp, float* amax, void* ws, long ws_bytes, void* stream) {
+/* ... with the |dy| scale record already in amax[512..768) (written by stk_bias_grad_amax*_f32): no |dy| pass */
+int stk_conv2d_dgrad_rec_f32(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                             int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                             int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                             void* stream) {
   if (!amax) return STK_EINVAL;
-  return fwd_impl(x1, C1, x2, C2, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, OH, OW, KH, KW, stride,
-                  pad, wp, amax, ws, ws_bytes, stream, true, true);
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, true, false);
 }
 
-static int dgrad_pl_impl(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
-                         float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
-                         int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
-  if (!dypl || !dyamax || !w || (!dx1 && !dx2) || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
-    return STK_EINVAL;
-  if (!stk_conv2d_pl_ok(1, C1, C2, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
-  ConvP p = {};
-  fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2);
-  p.w = w; p.w_layout = w_layout; p.dx1 = dx1; p.dx2 = C2 > 0 ? dx2 : nullptr;
-  p.beta1 = beta1; p.beta2 = beta2; p.alpha = alpha;
-  const long Ng = (long)N * p.HW;
-  const X3Plan xr = x3_plan_pl(p, Cout, p.Cin, Ng);
-  if (!ws || ws_bytes < x3_ws_bytes(xr, p.Cin, Cout, p.taps)) return STK_EINVAL;
-  return launch_x3<EpDgrad>(p, xr, nullptr, Cout, nullptr, 0, p.Cin, Ng, 1, ws, (hipStream_t)stream, wp, nullptr, dypl, dyamax,
-                            false, f16x1);
-}
-int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
-                            float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
-                            int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
-  return dgrad_pl_impl(dypl, dyamax, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, KH, KW, wp, ws, ws_bytes,
-                       stream, false);
+int stk_conv2d_dgrad_wp_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                              int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                              int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                              void* stream) {
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, false, true);
 }
 
-/* 3x3 / stride 1 / pad 1 weight gradient with x and dy given as planes (conv_x2w.h) */
-int stk_conv2d_wgrad_pl_ok(int N, int H, int W, int Cin, int Cout) { return x2w::plan(N, H, W, Cin, Cout).ok; }
-
-long stk_conv2d_wgrad_pl_ws_bytes(int N, int H, int W, int Cin, int Cout) {
-  // (covers every workgroup count a caller may ask for: the slabs of the deepest K split)
-  long m = 0;
-  for (int wgs : {0, 256, 512, 768, 1024}) {
-    const x2w::Plan q = x2w::plan(N, H, W, Cin, Cout, wgs);
-    if (q.ok && (long)q.splits * q.slab > m) m = (long)q.splits * q.slab;
-  }
-  return m ? m * 4 + 256 : 0;
+int stk_conv2d_dgrad_rec_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
+                               int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                               int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
+                               void* stream) {
+  if (!amax) return STK_EINVAL;
+  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
+                    amax, ws, ws_bytes, stream, true, true);
 }
 
-int stk_conv2d_wgrad_pl_f32(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
-                            float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream) {
-  return stk_conv2d_wgrad_pl_wgs_f32(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, 0, stream);
-}
-
-/* ... with the number of workgroups its K split fills chosen by the caller (0 = the library's default for a launch that shares the chip
- * with another stream; <= 1024).  Same result up to the summation order of the slabs. */
-static int wgrad_pl_impl(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw, float alpha,
-                         float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream, bool f16x1);
-int stk_conv2d_wgrad_pl_wgs_f32(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
-                                float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream) {
-  return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, wgs, stream, false);
-}
-static int wgrad_pl_impl(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw, float alpha,
-                         float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream, bool f16x1) {
-  if (!xpl || !xrec || !dypl || !dyrec || !dw || !ws || wgs < 0 || wgs > 1024) return STK_EINVAL;
-  const x2w::Plan q = x2w::plan(N, H, W, Cin, Cout, wgs);
-  if (!q.ok) return STK_EUNSUPPORTED;
-  if (ws_bytes < (long)q.splits * q.slab * 4) return STK_EINVAL;
-  x2w::Args a = {};
-  a.dypl = static_cast<const unsigned char*>(dypl); a.dyrec = dyrec; a.dy_ps = pl::plane_bytes(N, Cout, H * W);
-  a.xpl = static_cast<const unsigned char*>(xpl); a.xrec = xrec; a.x_ps = pl::plane_bytes(N, Cin, H * W);
-  if (2 * a.dy_ps >= 0x7fffffffL || 2 * a.x_ps >= 0x7fffffffL) return STK_EUNSUPPORTED;
-  a.part = ws; a.part_stride = q.slab;
-  a.N = N; a.H = H; a.W = W; a.HW = H * W; a.Cin = Cin; a.Cout = Cout; a.Cob = Cout / 32; a.Cib = Cin / 32;
-  a.tiles_co = stk_cdiv(Cout, 128); a.tiles_ci = Cin / 32;
-  a.nchunks_total = (int)((long)N * H * W / 32); a.chunks_per_split = q.chunks_per_split;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)(a.tiles_co * a.tiles_ci * q.splits));
-  if (f16x1) {                                   // the one-product form: same plan, slabs and reduce (conv_x2w.h, X1_FORM)
-    constexpr int X1 = x2w::X1_FORM;
-    if (q.groups == 2) {
-      if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 2 | X1>), grid, dim3(512), 0, s, a);
-      else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 2 | X1>), grid, dim3(512), 0, s, a);
-      else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 2 | X1>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((x2w::wgrad_kernel<4, 2 | X1>), grid, dim3(512), 0, s, a);
-    } else if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 1 | X1>), grid, dim3(256), 0, s, a);
-    else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 1 | X1>), grid, dim3(256), 0, s, a);
-    else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 1 | X1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((x2w::wgrad_kernel<4, 1 | X1>), grid, dim3(256), 0, s, a);
-  } else if (q.groups == 2) {
-    if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32, 2>), grid, dim3(512), 0, s, a);
-    else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16, 2>), grid, dim3(512), 0, s, a);
-    else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8, 2>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((x2w::wgrad_kernel<4, 2>), grid, dim3(512), 0, s, a);
-  } else if (W >= 32) hipLaunchKernelGGL((x2w::wgrad_kernel<32>), grid, dim3(256), 0, s, a);
-  else if (W == 16) hipLaunchKernelGGL((x2w::wgrad_kernel<16>), grid, dim3(256), 0, s, a);
-  else if (W == 8) hipLaunchKernelGGL((x2w::wgrad_kernel<8>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((x2w::wgrad_kernel<4>), grid, dim3(256), 0, s, a);
-  STK_CHECK_LAUNCH();
-  // measured (tools/bench_x2d.py, kernel + reduce, us, old -> new): 32 slabs 118.5 -> 117.0 / 55.1 -> 51.1, 64: 74.4 -> 72.3, 16: 206.0 ->
-  // 201.8, 8: 44.8 -> 39.7, but 128 slabs 124.1 -> 130.8 (1152 four-byte loads per thread): the coalesced form up to 64 slabs
-  if (q.splits <= 64)
-    hipLaunchKernelGGL(splitk_reduce9_kernel, dim3((unsigned)stk_cdiv((long)Cout * Cin, 256L)), dim3(256), 0, s, ws, dw, (long)Cout * Cin,
-                       q.splits, q.slab, alpha);
-  else
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((q.slab + 3) / 4)), dim3(256), 0, s, ws, dw, q.slab, q.splits,
-                       q.slab, alpha, 0, Cout, Cin, 9);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
-}
-
-/* map width of the halo-tile GEMM (x2d::gemm_halo_kernel<W, ..>) the plane-operand forward / data-gradient call of this
- * shape runs on, 0 = x2d::gemm_kernel (diagnostic: one profiler label per kernel symbol) */
-int stk_conv2d_pl_halo(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW) {
-  const int ks = stk_conv2d_pl_ksplit(dir, C1, C2, N, H, W, Cout, KH, KW);
-  if (ks <= 0) return 0;
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2)) return 0;
-  return x2d::halo_ok(p, p.taps, ks) ? x2d::halo_cols(W) : 0;
-}
-
-/* which kernel family a call with full scratch takes: 0/1 = f32-input MFMA with 64/128 tiles, 2 = bf16 three-way
- * split, 3 = f32-input all-taps weight gradient, 4 = thin-side streaming kernels, 5 = fp16 two-way split.  dir: 0 fwd, 1 dgrad, 2 wgrad. */
-int stk_conv2d_variant(int dir, int C1, int C2, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW,
-                       int stride, int pad, int w_layout) {
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, OH, OW, KH, KW, stride, pad)) return -1;
-  const int Cin = C1 + C2;
-  p.w_layout = w_layout;
-  if (dir == 0) {
-    const long Ng = (long)N * p.OHW;
-    if (thin::geometry_ok(p) && ((C2 == 0 && Cin <= 4) || Cout <= 4)) return 4;
-    if (x3_plan(p, Cin, C1, C2, Cout, Ng).ok) return 5;
-    return use_big_tile(Cout, Ng, 1) && !(p.taps == 1 && w_layout == 0 && (Cin % 8)) ? 1 : 0;
-  }
-  if (dir == 1) {
-    const long Ng = (long)N * p.HW;
-    if (thin::geometry_ok(p) && Cout <= 4) return 4;
-    if (x3_plan(p, Cout, Cout, 0, Cin, Ng).ok) return 5;
-    return use_big_tile(Cin, Ng, 1) && !(p.taps == 1 && w_layout == 1 && (Cout % 8)) ? 1 : 0;
-  }
-  if (thin::geometry_ok(p) && ((C2 == 0 && Cin <= 4) || Cout <= 4)) return 4;
-  {
-    const X3WgradPlan xq = x3_wgrad_plan(C1, C2, N, Cout, H, W, OH, OW, KH, KW, stride, pad);
-    if (xq.ok) return 5;
-  }
-  const bool can9 = stride == 1 && pad == 1 && C2 == 0 && OH == H && OW == W && w_layout == 0;
-  const WgradPlan q = wgrad_plan(Cin, N, Cout, OH, OW, KH, KW, can9);
-  return q.mode9 ? 3 : q.big;
-}
-
-/* Prepared weights (the bf16 three-way split in the A-tile layout of conv_x3.h), so that a caller whose weights change
- * once per optimizer step -- or never, in a sampling loop -- prepares them once instead of once per call.
- * dir: 0 forward, 1 data gradient.  Bytes are 0 for shapes whose call does not take the split kernel. */
-long stk_conv2d_wp_bytes(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
-  if (dir != 0 && dir != 1) return 0;
-  const int v = stk_conv2d_variant(dir, C1, C2, N, H, W, Cout, H, W, KH, KW, stride, pad, 0);
-  if (v != 2 && v != 5) return 0;
-  const int Cin = C1 + C2;
-  return (dir == 0 ? x3::wp_bytes(Cout, Cin, KH * KW) : x3::wp_bytes(Cin, Cout, KH * KW)) + 256;
-}
-
-/* Host-side fill of one descriptor; returns the number of (row, k) work items of this layer (the caller passes the
- * maximum over its table to stk_conv2d_wprep_batch) or a negative error.  wp must be 256-byte aligned. */
-long stk_conv2d_wp_desc(int dir, const float* w, int w_layout, int Cin, int Cout, int KH, int KW, void* wp,
-                        StkWprepDesc* out) {
-  if (!w || !wp || !out || (dir != 0 && dir != 1) || (w_layout != 0 && w_layout != 1) || Cin <= 0 || Cout <= 0 ||
-      (KH * KW != 9 && KH * KW != 1) || (w_layout == 1 && KH * KW != 1) || ((uintptr_t)wp & 255))
-    return STK_EINVAL;
-  ConvP p = {};
-  p.Cin = Cin; p.Cout = Cout; p.taps = KH * KW; p.w_layout = w_layout;
-  long sm, sk;
-  x3_weight_strides(p, dir, sm, sk);
-  out->w = w; out->wp = wp; out->sm = sm; out->sk = sk;
-  out->M = dir ? Cin : Cout; out->Kc = dir ? Cout : Cin; out->Mpad = x3::pad128(out->M); out->taps = p.taps;
-  out->flip = dir; out->reserved = 0;
-  return (long)out->Mpad * out->Kc;
-}
-
-int stk_conv2d_wprep_batch(const StkWprepDesc* descs_dev, int n, long max_items, void* stream) {
-  static_assert(sizeof(StkWprepDesc) == sizeof(x2::WprepDesc), "descriptor layout");
-  if (!descs_dev || n <= 0 || max_items <= 0 || n > 65535) return STK_EINVAL;
-  const dim3 grid((unsigned)stk_cdiv(max_items, 256L), (unsigned)n);
-  const x2::WprepDesc* d = reinterpret_cast<const x2::WprepDesc*>(descs_dev);
-  hipLaunchKernelGGL(x2::wamax_kernel, dim3(x2::WPART, (unsigned)n), dim3(256), 0, (hipStream_t)stream, d, x2::WprepDesc{});
-  hipLaunchKernelGGL(x2::wprep_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, x2::WprepDesc{});
-  STK_CHECK_LAUNCH();
-  return STK_OK;
-}
-
-long stk_conv2d_fwd_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
-  const long a = x3_ws_bytes(x3_plan(p, C1 + C2, C1, C2, Cout, (long)N * H * W), Cout, C1 + C2, p.taps);
-  const long b = C2 == 0 ? x3_ws_bytes(x3_plan_pl(p, C1, Cout, (long)N * H * W), Cout, C1, p.taps) : 0;      // the plane-operand plan
-  return a > b ? a : b;
-}
-
-long stk_conv2d_dgrad_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
-  ConvP p = {};
-  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
-  const long a = x3_ws_bytes(x3_plan(p, Cout, Cout, 0, C1 + C2, (long)N * H * W), C1 + C2, Cout, p.taps);
-  const long b = x3_ws_bytes(x3_plan_pl(p, Cout, C1 + C2, (long)N * H * W), C1 + C2, Cout, p.taps);
-  return a > b ? a : b;
-}
-
-long stk_conv2d_wgrad_ws_bytes(int C1, int C2, int N, int Cout, int OH, int OW, int KH, int KW) {
-  const WgradPlan a = wgrad_plan(C1 + C2, N, Cout, OH, OW, KH, KW, true);
-  const WgradPlan b = wgrad_plan(C1 + C2, N, Cout, OH, OW, KH, KW, false);
-  const X3WgradPlan x = x3_wgrad_plan(C1, C2, N, Cout, OH, OW, OH, OW, KH, KW, 1, KH == 3 ? 1 : 0);
-  const long na = (long)a.splits * a.slab, nb = (long)b.splits * b.slab, nx = x.ok ? (long)x.splits * x.slab : 0;
-  long m = na > nb ? na : nb;
-  if (C2 == 0 && C1 <= 4) { const long t = (long)thin::wgrad_slabs(N, (long)OH * OW, Cout) * Cout * C1 * KH * KW; m = t > m ? t : m; }
-  if (Cout <= 4) { const long t = (long)thin::wgrad_slabs(N, (long)OH * OW, C1 + C2) * Cout * (C1 + C2) * KH * KW; m = t > m ? t : m; }
-  return (m > nx ? m : nx) * 4 + 256 + 256 + 3L * x2::NPART * 4;      // + partial maxima of dy, x1, x2
-}
-
-static int wgrad_amax_impl(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
-                           float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                           int KW, int stride, int pad, const float* amax, int have, void* stream, bool f16x1);
-int stk_conv2d_wgrad_amax_f32(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
-                              float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                              int KW, int stride, int pad, const float* amax, int have, void* stream) {
-  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
-                         have, stream, false);
-}
+/* ---- weight gradient -------------------------------------------------------------------------------------------------- */
 static int wgrad_amax_impl(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
                            float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
                            int KW, int stride, int pad, const float* amax, int have, void* stream, bool f16x1) {
@@ -1735,83 +1493,45 @@ static int wgrad_amax_impl(const float* x1, int C1, const float* x2, int C2, con
     STK_CHECK_LAUNCH();
     return STK_OK;
   }
-  const X3WgradPlan xq = x3_wgrad_plan(C1, C2, N, Cout, H, W, OH, OW, KH, KW, stride, pad);
+  const SplitWgradPlan xq = split_wgrad_plan(C1, C2, N, Cout, H, W, OH, OW, KH, KW, stride, pad);
   if (xq.ok && ws_bytes >= (long)xq.splits * xq.slab * 4 + 256 + 3L * x2::NPART * 4) {      // slabs + the |dy| / |x| partial maxima
     p.x1 = x1; p.x2 = C2 > 0 ? x2 : x1; p.dy = dy; p.w_layout = w_layout; p.part = ws; p.part_stride = xq.slab;
-    const int tm = stk_cdiv(Cout, 128), tn = stk_cdiv(p.Cin, 128);
-    const int nch = (int)((long)N * p.HW / 32);
-    // the one-product form has no three-taps kernel: its 3x3 layers run the per-tap x2::wgemm_kernel below (a 128 x 128 tile
-    // per tap, the same K split and slabs [tap][Cout][Cin])
-    if (xq.rows3 && !f16x1) {
+    // fp16 two-way split of both operands (conv_x2.h): |dy| and |x| maxima first.  Maxima the layer's forward (x) /
+    // data-gradient (dy) calls left in `amax` are reused, the others taken here, behind the slabs.
+    float* parts = reinterpret_cast<float*>(((uintptr_t)(ws + (long)xq.splits * xq.slab) + 255) & ~(uintptr_t)255);
+    const dim3 ab(x2::NPART), at(x2::AMAX_THREADS);
+    const float* dyp = parts;
+    const float* xp = parts + x2::NPART;
+    if (amax && (have & 2)) dyp = amax + 2 * x2::NPART;
+    else hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, dy, (long)N * Cout * p.OHW, parts);
+    if (amax && (have & 1)) {
+      xp = amax;
+    } else {
+      hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x1, (long)N * C1 * p.HW, parts + x2::NPART);
+      if (C2 > 0) hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x2, (long)N * C2 * p.HW, parts + 2 * x2::NPART);
+    }
+    const int nx = C2 > 0 ? 2 * x2::NPART : x2::NPART;
+    const int tm = stk_cdiv(Cout, 128), nch = (int)((long)N * p.HW / 32);
+    if (xq.rows3 && !f16x1) {          // 3x3 on maps of >= 8 columns: three taps per workgroup (x2::wgrad3_kernel)
       const int tn64 = stk_cdiv(p.Cin, 64);
       const dim3 grid3((unsigned)(3 * tm * tn64 * xq.splits));
-      float* parts = reinterpret_cast<float*>(((uintptr_t)(ws + (long)xq.splits * xq.slab) + 255) & ~(uintptr_t)255);
-      {
-        // fp16 two-way split of both operands (conv_x2.h): |dy| and |x| maxima first
-        const dim3 ab(x2::NPART), at(x2::AMAX_THREADS);
-        // maxima the layer's forward (x) / data-gradient (dy) calls left in `amax` are reused, the others taken here
-        const float* dyp = parts;
-        const float* xp = parts + x2::NPART;
-        if (amax && (have & 2)) dyp = amax + 2 * x2::NPART;
-        else hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, dy, (long)N * Cout * p.OHW, parts);
-        if (amax && (have & 1)) {
-          xp = amax;
-        } else {
-          hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x1, (long)N * C1 * p.HW, parts + x2::NPART);
-          if (C2 > 0) hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x2, (long)N * C2 * p.HW, parts + 2 * x2::NPART);
-        }
-        const int nx = C2 > 0 ? 2 * x2::NPART : x2::NPART;
-        if (C2 > 0) hipLaunchKernelGGL((x2::wgrad3_kernel<true>), grid3, dim3(256), 0, s, p, tm, tn64, nch, xq.chunks_per_split,
-                                       dyp, xp, nx);
-        else hipLaunchKernelGGL((x2::wgrad3_kernel<false>), grid3, dim3(256), 0, s, p, tm, tn64, nch, xq.chunks_per_split,
-                                dyp, xp, nx);
-      }
-      STK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((xq.slab + 3) / 4)), dim3(256), 0, s, ws, dw, xq.slab, xq.splits,
-                         xq.slab, alpha, w_layout, Cout, p.Cin, p.taps);
-      STK_CHECK_LAUNCH();
-      return STK_OK;
+      if (C2 > 0) hipLaunchKernelGGL((x2::wgrad3_kernel<true>), grid3, dim3(256), 0, s, p, tm, tn64, nch, xq.chunks_per_split,
+                                     dyp, xp, nx);
+      else hipLaunchKernelGGL((x2::wgrad3_kernel<false>), grid3, dim3(256), 0, s, p, tm, tn64, nch, xq.chunks_per_split,
+                              dyp, xp, nx);
+    } else {
+      // per tap (x2::wgemm_kernel).  The one-product form has no three-taps kernel: its 3x3 layers run here too (a 128 x 128
+      // tile per tap, the same K split and slabs [tap][Cout][Cin]).
+      const int tn = stk_cdiv(p.Cin, 128);
+      const WgemmArgs g = {p, tm, tn, nch, xq.chunks_per_split, dyp, xp, nx, dim3((unsigned)(p.taps * tm * tn * xq.splits)), s};
+      if (f16x1) launch_wgemm<true>(g);
+      else launch_wgemm<false>(g);
     }
-    const dim3 grid((unsigned)(p.taps * tm * tn * xq.splits));
-    {
-      // fp16 two-way split of both operands (x2::wgemm_kernel): maxima as for the three-taps kernel above
-      float* parts = reinterpret_cast<float*>(((uintptr_t)(ws + (long)xq.splits * xq.slab) + 255) & ~(uintptr_t)255);
-      const dim3 ab(x2::NPART), at(x2::AMAX_THREADS);
-      const float* dyp = parts;
-      const float* xp = parts + x2::NPART;
-      if (amax && (have & 2)) dyp = amax + 2 * x2::NPART;
-      else hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, dy, (long)N * Cout * p.OHW, parts);
-      if (amax && (have & 1)) {
-        xp = amax;
-      } else {
-        hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x1, (long)N * C1 * p.HW, parts + x2::NPART);
-        if (C2 > 0) hipLaunchKernelGGL(x2::amax_partial_kernel, ab, at, 0, s, x2, (long)N * C2 * p.HW, parts + 2 * x2::NPART);
-      }
-      const int nx = C2 > 0 ? 2 * x2::NPART : x2::NPART;
-#define STK_X2_WGRAD1(BL, ARGS)                                                                                             \
-  hipLaunchKernelGGL((x2::wgemm_kernel<x2::RowsU<false, false>, x2::BL<ARGS>, EpWgrad, true>), grid, dim3(256), 0, s, p, Cout, \
-                     p.Cin, tm, tn, nch, xq.chunks_per_split, p.taps, dyp, xp, nx)
-// the one-product form (include/stk_fp16_train.h): hi-plane loaders (RowsU16 / RowsB16), OneProduct epilogue, no schedule pins
-#define STK_X2_WGRAD1_X1(BL, ARGS)                                                                                          \
-  hipLaunchKernelGGL((x2::wgemm_kernel<x2::RowsU16<false, false>, x2::BL##16<ARGS>, OneProduct<EpWgrad>, false>), grid,      \
-                     dim3(256), 0, s, p, Cout, p.Cin, tm, tn, nch, xq.chunks_per_split, p.taps, dyp, xp, nx)
-#define STK_COMMA ,
-#define STK_X2_WGRAD1_ALL(L)                                                                                                \
-      if (p.taps == 1) { if (C2 > 0) L(RowsU, true STK_COMMA true); else L(RowsU, true STK_COMMA false); }                  \
-      else if (W >= 16) { if (C2 > 0) L(RowsB, true STK_COMMA 16); else L(RowsB, false STK_COMMA 16); }                     \
-      else if (W == 8) { if (C2 > 0) L(RowsB, true STK_COMMA 8); else L(RowsB, false STK_COMMA 8); }                        \
-      else { if (C2 > 0) L(RowsB, true STK_COMMA 4); else L(RowsB, false STK_COMMA 4); }
-      if (f16x1) { STK_X2_WGRAD1_ALL(STK_X2_WGRAD1_X1) } else { STK_X2_WGRAD1_ALL(STK_X2_WGRAD1) }
-#undef STK_X2_WGRAD1_ALL
-#undef STK_COMMA
-#undef STK_X2_WGRAD1_X1
-#undef STK_X2_WGRAD1
-      STK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((xq.slab + 3) / 4)), dim3(256), 0, s, ws, dw, xq.slab, xq.splits,
-                         xq.slab, alpha, w_layout, Cout, p.Cin, p.taps);
-      STK_CHECK_LAUNCH();
-      return STK_OK;
-    }
+    STK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((xq.slab + 3) / 4)), dim3(256), 0, s, ws, dw, xq.slab, xq.splits,
+                       xq.slab, alpha, w_layout, Cout, p.Cin, p.taps);
+    STK_CHECK_LAUNCH();
+    return STK_OK;
   }
   const bool can9 = stride == 1 && pad == 1 && C2 == 0 && OH == H && OW == W && w_layout == 0;
   const WgradPlan q = wgrad_plan(p.Cin, N, Cout, OH, OW, KH, KW, can9);
@@ -1850,42 +1570,307 @@ int stk_conv2d_wgrad_f32(const float* x1, int C1, const float* x2, int C2, const
                                    pad, nullptr, 0, stream);
 }
 
-/* ---- include/stk_fp16_train.h: the one-product twins of the backward entries ------------------------------------------ */
+int stk_conv2d_wgrad_amax_f32(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
+                              float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                              int KW, int stride, int pad, const float* amax, int have, void* stream) {
+  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
+                         have, stream, false);
+}
+
+int stk_conv2d_wgrad_amax_f16x1(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
+                                float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
+                                int KW, int stride, int pad, const float* amax, int have, void* stream) {
+  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
+                         have, stream, true);
+}
+
+/* ---- planes (conv_pl.h): activations pre-split into two fp16 planes, [split][n][c / 32][pixel][c % 32] ---- */
+long stk_planes_bytes(int N, int C, int HW) {
+  if (N <= 0 || C <= 0 || HW <= 0) return 0;
+  return 2 * pl::plane_bytes(N, C, HW);
+}
+
+int stk_amax_partial_f32(const float* x, long n, float* part, void* stream) {
+  if (!x || !part || n <= 0) return STK_EINVAL;
+  hipLaunchKernelGGL(x2::amax_partial_kernel, dim3(x2::NPART), dim3(x2::AMAX_THREADS), 0, (hipStream_t)stream, x, n, part);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+int stk_split_planes_f32(const float* x, int N, int C, int HW, const float* amax, int namax, void* planes, void* stream) {
+  if (!x || !amax || !planes || N <= 0 || C <= 0 || HW <= 0 || namax <= 0) return STK_EINVAL;
+  if (2 * pl::plane_bytes(N, C, HW) >= 0x7fffffffL) return STK_EUNSUPPORTED;      // 32-bit buffer offsets in the consumers
+  const long blocks = (long)N * ((C + 31) / 32) * stk_cdiv(HW, pl::SP_PIX);
+  hipLaunchKernelGGL(pl::split_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, N, C, HW, amax,
+                     namax, static_cast<unsigned char*>(planes), pl::plane_bytes(N, C, HW));
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+/* 1 when the forward (dir 0) / data-gradient (dir 1) call of this shape can read its activation operand (x resp. dy) as
+ * planes: exactly the shapes that take the fp16 split kernel with a single-source operand. */
+int stk_conv2d_pl_ok(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
+  if (stride != 1 || pad != KH / 2) return 0;
+  if (dir == 0) {
+    if (C2 > 0 || p.Cin <= 4 || Cout <= 4) return 0;        // two sources / thin-side streaming kernels
+    return fwd_split_plan(p).ok;
+  }
+  if (dir == 1) {
+    if (Cout <= 4 || p.Cin <= 4) return 0;
+    return dgrad_split_plan(p).ok;
+  }
+  return 0;
+}
+
+/* number of K splits the plane-operand forward (dir 0) / data-gradient (dir 1) call of this shape runs with: 1 = one
+ * launch of x2d::gemm_kernel<.., EpFwd / EpDgrad>, > 1 = EpSlab partial tiles + a slab-sum launch (small maps),
+ * 0 = the shape does not take plane operands.  (Profiler labels: bench.py names kernels by their rocprof symbol.) */
+int stk_conv2d_pl_ksplit(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW) {
+  if (!stk_conv2d_pl_ok(dir, C1, C2, N, H, W, Cout, KH, KW, 1, KH / 2)) return 0;
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2)) return 0;
+  return dir == 0 ? fwd_split_plan(p).splits : dgrad_split_plan(p).splits;
+}
+
+/* map width of the halo-tile GEMM (x2d::gemm_halo_kernel<W, ..>) the plane-operand forward / data-gradient call of this
+ * shape runs on, 0 = x2d::gemm_kernel (diagnostic: one profiler label per kernel symbol) */
+int stk_conv2d_pl_halo(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW) {
+  const int ks = stk_conv2d_pl_ksplit(dir, C1, C2, N, H, W, Cout, KH, KW);
+  if (ks <= 0) return 0;
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2)) return 0;
+  return x2d::halo_ok(p, p.taps, ks) ? x2d::halo_cols(W) : 0;
+}
+
+/* ---- forward with the activations given as planes -------------------------------------------------------------------- */
+static int fwd_pl_impl(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                       const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                       int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
+  if (!xpl || !xamax || !w || !y || out_div == 0.f || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
+    return STK_EINVAL;
+  if (!stk_conv2d_pl_ok(0, C, 0, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
+  ConvP p = {};
+  fill_common(p, N, H, W, C, 0, Cout, H, W, KH, KW, 1, KH / 2);
+  p.w = w; p.w_layout = w_layout; p.bias = bias; p.temb = temb; p.temb_stride = temb_stride; p.res = res;
+  p.inv_div = 1.f / out_div; p.use_div = out_div != 1.f; p.y = y;
+  const long Ng = (long)N * p.HW;
+  const SplitPlan xr = fwd_split_plan(p);
+  if (!ws || ws_bytes < split_ws(xr, Cout, C, p.taps).bytes) return STK_EINVAL;
+  return launch_split<EpFwd>(p, xr, nullptr, C, nullptr, 0, Cout, Ng, 0, ws, (hipStream_t)stream, wp, nullptr, xpl, xamax, false,
+                             f16x1);
+}
+
+int stk_conv2d_fwd_pl_f32(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                          const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                          int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
+                     ws_bytes, stream, false);
+}
+
+int stk_conv2d_fwd_pl_f16x1(const void* xpl, const float* xamax, int C, const float* w, int w_layout, const float* bias,
+                            const float* temb, int temb_stride, const float* res, float out_div, float* y, int N, int H,
+                            int W, int Cout, int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return fwd_pl_impl(xpl, xamax, C, w, w_layout, bias, temb, temb_stride, res, out_div, y, N, H, W, Cout, KH, KW, wp, ws,
+                     ws_bytes, stream, true);
+}
+
+/* ---- data gradient with dy given as planes ---------------------------------------------------------------------------- */
+static int dgrad_pl_impl(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
+                         float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
+                         int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream, bool f16x1) {
+  if (!dypl || !dyamax || !w || (!dx1 && !dx2) || (w_layout != 0 && w_layout != 1) || (w_layout == 1 && KH != 1))
+    return STK_EINVAL;
+  if (!stk_conv2d_pl_ok(1, C1, C2, N, H, W, Cout, KH, KW, 1, KH / 2)) return STK_EUNSUPPORTED;
+  ConvP p = {};
+  fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, 1, KH / 2);
+  p.w = w; p.w_layout = w_layout; p.dx1 = dx1; p.dx2 = C2 > 0 ? dx2 : nullptr;
+  p.beta1 = beta1; p.beta2 = beta2; p.alpha = alpha;
+  const long Ng = (long)N * p.HW;
+  const SplitPlan xr = dgrad_split_plan(p);
+  if (!ws || ws_bytes < split_ws(xr, p.Cin, Cout, p.taps).bytes) return STK_EINVAL;
+  return launch_split<EpDgrad>(p, xr, nullptr, Cout, nullptr, 0, p.Cin, Ng, 1, ws, (hipStream_t)stream, wp, nullptr, dypl, dyamax,
+                               false, f16x1);
+}
+
+int stk_conv2d_dgrad_pl_f32(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
+                            float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
+                            int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
+  return dgrad_pl_impl(dypl, dyamax, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, KH, KW, wp, ws, ws_bytes,
+                       stream, false);
+}
+
 int stk_conv2d_dgrad_pl_f16x1(const void* dypl, const float* dyamax, const float* w, int w_layout, float* dx1, int C1,
                               float beta1, float* dx2, int C2, float beta2, float alpha, int N, int H, int W, int Cout,
                               int KH, int KW, const void* wp, void* ws, long ws_bytes, void* stream) {
   return dgrad_pl_impl(dypl, dyamax, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, KH, KW, wp, ws, ws_bytes,
                        stream, true);
 }
-int stk_conv2d_dgrad_wp_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
-                              int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                              int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                              void* stream) {
-  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
-                    amax, ws, ws_bytes, stream, false, true);
+
+/* 3x3 / stride 1 / pad 1 weight gradient with x and dy given as planes (conv_x2w.h) */
+int stk_conv2d_wgrad_pl_ok(int N, int H, int W, int Cin, int Cout) { return x2w::plan(N, H, W, Cin, Cout).ok; }
+
+long stk_conv2d_wgrad_pl_ws_bytes(int N, int H, int W, int Cin, int Cout) {
+  // (covers every workgroup count a caller may ask for: the slabs of the deepest K split)
+  long m = 0;
+  for (int wgs : {0, 256, 512, 768, 1024}) {
+    const x2w::Plan q = x2w::plan(N, H, W, Cin, Cout, wgs);
+    if (q.ok && (long)q.splits * q.slab > m) m = (long)q.splits * q.slab;
+  }
+  return m ? m * 4 + 256 : 0;
 }
-int stk_conv2d_dgrad_rec_f16x1(const float* dy, const float* w, int w_layout, float* dx1, int C1, float beta1, float* dx2,
-                               int C2, float beta2, float alpha, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                               int KW, int stride, int pad, const void* wp, float* amax, void* ws, long ws_bytes,
-                               void* stream) {
-  if (!amax) return STK_EINVAL;
-  return dgrad_impl(dy, w, w_layout, dx1, C1, beta1, dx2, C2, beta2, alpha, N, H, W, Cout, OH, OW, KH, KW, stride, pad, wp,
-                    amax, ws, ws_bytes, stream, true, true);
+
+static int wgrad_pl_impl(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw, float alpha,
+                         float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream, bool f16x1) {
+  if (!xpl || !xrec || !dypl || !dyrec || !dw || !ws || wgs < 0 || wgs > 1024) return STK_EINVAL;
+  const x2w::Plan q = x2w::plan(N, H, W, Cin, Cout, wgs);
+  if (!q.ok) return STK_EUNSUPPORTED;
+  if (ws_bytes < (long)q.splits * q.slab * 4) return STK_EINVAL;
+  x2w::Args a = {};
+  a.dypl = static_cast<const unsigned char*>(dypl); a.dyrec = dyrec; a.dy_ps = pl::plane_bytes(N, Cout, H * W);
+  a.xpl = static_cast<const unsigned char*>(xpl); a.xrec = xrec; a.x_ps = pl::plane_bytes(N, Cin, H * W);
+  if (2 * a.dy_ps >= 0x7fffffffL || 2 * a.x_ps >= 0x7fffffffL) return STK_EUNSUPPORTED;
+  a.part = ws; a.part_stride = q.slab;
+  a.N = N; a.H = H; a.W = W; a.HW = H * W; a.Cin = Cin; a.Cout = Cout; a.Cob = Cout / 32; a.Cib = Cin / 32;
+  a.tiles_co = stk_cdiv(Cout, 128); a.tiles_ci = Cin / 32;
+  a.nchunks_total = (int)((long)N * H * W / 32); a.chunks_per_split = q.chunks_per_split;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(a.tiles_co * a.tiles_ci * q.splits));
+  // the one-product form: same plan, slabs and reduce (conv_x2w.h, X1_FORM)
+  if (f16x1) {
+    if (q.groups == 2) launch_x2w<2 | x2w::X1_FORM>(a, W, grid, s);
+    else launch_x2w<1 | x2w::X1_FORM>(a, W, grid, s);
+  } else if (q.groups == 2) {
+    launch_x2w<2>(a, W, grid, s);
+  } else {
+    launch_x2w<1>(a, W, grid, s);
+  }
+  STK_CHECK_LAUNCH();
+  // measured (tools/bench_x2d.py, kernel + reduce, us, old -> new): 32 slabs 118.5 -> 117.0 / 55.1 -> 51.1, 64: 74.4 -> 72.3, 16: 206.0 ->
+  // 201.8, 8: 44.8 -> 39.7, but 128 slabs 124.1 -> 130.8 (1152 four-byte loads per thread): the coalesced form up to 64 slabs
+  if (q.splits <= 64)
+    hipLaunchKernelGGL(splitk_reduce9_kernel, dim3((unsigned)stk_cdiv((long)Cout * Cin, 256L)), dim3(256), 0, s, ws, dw, (long)Cout * Cin,
+                       q.splits, q.slab, alpha);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stk_ew_grid((q.slab + 3) / 4)), dim3(256), 0, s, ws, dw, q.slab, q.splits,
+                       q.slab, alpha, 0, Cout, Cin, 9);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
 }
+
+int stk_conv2d_wgrad_pl_f32(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
+                            float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream) {
+  return stk_conv2d_wgrad_pl_wgs_f32(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, 0, stream);
+}
+
+/* ... with the number of workgroups its K split fills chosen by the caller (0 = the library's default for a launch that shares the chip
+ * with another stream; <= 1024).  Same result up to the summation order of the slabs. */
+int stk_conv2d_wgrad_pl_wgs_f32(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
+                                float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs, void* stream) {
+  return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, wgs, stream, false);
+}
+
 int stk_conv2d_wgrad_pl_f16x1(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
                               float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream) {
   return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, 0, stream, true);
 }
+
 int stk_conv2d_wgrad_pl_wgs_f16x1(const void* xpl, const float* xrec, const void* dypl, const float* dyrec, float* dw,
                                   float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cin, int Cout, int wgs,
                                   void* stream) {
   return wgrad_pl_impl(xpl, xrec, dypl, dyrec, dw, alpha, ws, ws_bytes, N, H, W, Cin, Cout, wgs, stream, true);
 }
-int stk_conv2d_wgrad_amax_f16x1(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, int w_layout,
-                                float alpha, float* ws, long ws_bytes, int N, int H, int W, int Cout, int OH, int OW, int KH,
-                                int KW, int stride, int pad, const float* amax, int have, void* stream) {
-  return wgrad_amax_impl(x1, C1, x2, C2, dy, dw, w_layout, alpha, ws, ws_bytes, N, H, W, Cout, OH, OW, KH, KW, stride, pad, amax,
-                         have, stream, true);
+
+/* ---- planning queries, prepared weights, scratch sizes ------------------------------------------------------------------ */
+/* which kernel family a call with full scratch takes: 0/1 = f32-input MFMA with 64/128 tiles, 3 = f32-input all-taps weight
+ * gradient, 4 = thin-side streaming kernels, 5 = the split path (fp16 two-way split; 2 is never returned: a retired family).
+ * dir: 0 fwd, 1 dgrad, 2 wgrad. */
+int stk_conv2d_variant(int dir, int C1, int C2, int N, int H, int W, int Cout, int OH, int OW, int KH, int KW,
+                       int stride, int pad, int w_layout) {
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, OH, OW, KH, KW, stride, pad)) return -1;
+  const int Cin = C1 + C2;
+  p.w_layout = w_layout;
+  if (dir == 0) {
+    const long Ng = (long)N * p.OHW;
+    if (thin::geometry_ok(p) && ((C2 == 0 && Cin <= 4) || Cout <= 4)) return 4;
+    if (fwd_split_plan(p).ok) return 5;
+    return use_big_tile(Cout, Ng, 1) && !(p.taps == 1 && w_layout == 0 && (Cin % 8)) ? 1 : 0;
+  }
+  if (dir == 1) {
+    const long Ng = (long)N * p.HW;
+    if (thin::geometry_ok(p) && Cout <= 4) return 4;
+    if (dgrad_split_plan(p).ok) return 5;
+    return use_big_tile(Cin, Ng, 1) && !(p.taps == 1 && w_layout == 1 && (Cout % 8)) ? 1 : 0;
+  }
+  if (thin::geometry_ok(p) && ((C2 == 0 && Cin <= 4) || Cout <= 4)) return 4;
+  if (split_wgrad_plan(C1, C2, N, Cout, H, W, OH, OW, KH, KW, stride, pad).ok) return 5;
+  const bool can9 = stride == 1 && pad == 1 && C2 == 0 && OH == H && OW == W && w_layout == 0;
+  const WgradPlan q = wgrad_plan(Cin, N, Cout, OH, OW, KH, KW, can9);
+  return q.mode9 ? 3 : q.big;
+}
+
+/* Prepared weights (x2::wp_bytes: a 256-byte header of partial |w| maxima, then the two fp16 planes in the A-tile layout of
+ * conv_x2.h), so that a caller whose weights change
+ * once per optimizer step -- or never, in a sampling loop -- prepares them once instead of once per call.
+ * dir: 0 forward, 1 data gradient.  Bytes are 0 for shapes whose call does not take the split kernel. */
+long stk_conv2d_wp_bytes(int dir, int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
+  if (dir != 0 && dir != 1) return 0;
+  if (stk_conv2d_variant(dir, C1, C2, N, H, W, Cout, H, W, KH, KW, stride, pad, 0) != 5) return 0;
+  const int Cin = C1 + C2;
+  return dir == 0 ? x2::wp_bytes(Cout, Cin, KH * KW) : x2::wp_bytes(Cin, Cout, KH * KW);
+}
+
+/* Host-side fill of one descriptor; returns the number of (row, k) work items of this layer (the caller passes the
+ * maximum over its table to stk_conv2d_wprep_batch) or a negative error.  wp must be 256-byte aligned. */
+long stk_conv2d_wp_desc(int dir, const float* w, int w_layout, int Cin, int Cout, int KH, int KW, void* wp,
+                        StkWprepDesc* out) {
+  if (!w || !wp || !out || (dir != 0 && dir != 1) || (w_layout != 0 && w_layout != 1) || Cin <= 0 || Cout <= 0 ||
+      (KH * KW != 9 && KH * KW != 1) || (w_layout == 1 && KH * KW != 1) || ((uintptr_t)wp & 255))
+    return STK_EINVAL;
+  ConvP p = {};
+  p.Cin = Cin; p.Cout = Cout; p.taps = KH * KW; p.w_layout = w_layout;
+  long sm, sk;
+  split_weight_strides(p, dir, sm, sk);
+  out->w = w; out->wp = wp; out->sm = sm; out->sk = sk;
+  out->M = dir ? Cin : Cout; out->Kc = dir ? Cout : Cin; out->Mpad = x2::pad128(out->M); out->taps = p.taps;
+  out->flip = dir; out->reserved = 0;
+  return (long)out->Mpad * out->Kc;
+}
+
+int stk_conv2d_wprep_batch(const StkWprepDesc* descs_dev, int n, long max_items, void* stream) {
+  static_assert(sizeof(StkWprepDesc) == sizeof(x2::WprepDesc), "descriptor layout");
+  if (!descs_dev || n <= 0 || max_items <= 0 || n > 65535) return STK_EINVAL;
+  const dim3 grid((unsigned)stk_cdiv(max_items, 256L), (unsigned)n);
+  const x2::WprepDesc* d = reinterpret_cast<const x2::WprepDesc*>(descs_dev);
+  hipLaunchKernelGGL(x2::wamax_kernel, dim3(x2::WPART, (unsigned)n), dim3(256), 0, (hipStream_t)stream, d, x2::WprepDesc{});
+  hipLaunchKernelGGL(x2::wprep_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, x2::WprepDesc{});
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+long stk_conv2d_fwd_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
+  return split_ws(fwd_split_plan(p), Cout, C1 + C2, p.taps).bytes;      // (a plane-operand call runs the same plan)
+}
+
+long stk_conv2d_dgrad_ws_bytes(int C1, int C2, int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
+  ConvP p = {};
+  if (fill_common(p, N, H, W, C1, C2, Cout, H, W, KH, KW, stride, pad)) return 0;
+  return split_ws(dgrad_split_plan(p), C1 + C2, Cout, p.taps).bytes;    // (a plane-operand call runs the same plan)
+}
+
+long stk_conv2d_wgrad_ws_bytes(int C1, int C2, int N, int Cout, int OH, int OW, int KH, int KW) {
+  const WgradPlan a = wgrad_plan(C1 + C2, N, Cout, OH, OW, KH, KW, true);
+  const WgradPlan b = wgrad_plan(C1 + C2, N, Cout, OH, OW, KH, KW, false);
+  const SplitWgradPlan x = split_wgrad_plan(C1, C2, N, Cout, OH, OW, OH, OW, KH, KW, 1, KH == 3 ? 1 : 0);
+  const long na = (long)a.splits * a.slab, nb = (long)b.splits * b.slab, nx = x.ok ? (long)x.splits * x.slab : 0;
+  long m = na > nb ? na : nb;
+  if (C2 == 0 && C1 <= 4) { const long t = (long)thin::wgrad_slabs(N, (long)OH * OW, Cout) * Cout * C1 * KH * KW; m = t > m ? t : m; }
+  if (Cout <= 4) { const long t = (long)thin::wgrad_slabs(N, (long)OH * OW, C1 + C2) * Cout * (C1 + C2) * KH * KW; m = t > m ? t : m; }
+  return (m > nx ? m : nx) * 4 + 256 + 256 + 3L * x2::NPART * 4;      // + partial maxima of dy, x1, x2
 }
 
 int stk_gemm_f32(const float* A, long sam, long sak, long sab, const float* B, long sbk, long sbn, long sbb, float* C,

@@ -24,9 +24,9 @@ namespace pl {
 
 using x2::HEADER;
 using x2::NPART;
-using x3::KC;
-using x3::PITCH;
-using x3::PLANE;
+using x2::KC;
+using x2::PITCH;
+using x2::PLANE;
 
 inline long plane_bytes(int N, int C, int HW) { return (long)N * ((C + 31) / 32) * HW * 64; }
 

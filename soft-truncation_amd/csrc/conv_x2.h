@@ -1,11 +1,12 @@
 // conv_x2.h -- forward / data-gradient convolution (3x3 pad 1 and 1x1, stride 1) on the fp16 matrix pipe with a TWO-way
-// operand split ("x2"), for gfx950.  Included by conv.hip inside its anonymous namespace, after conv_x3.h, whose tile
-// geometry, buffer-load helpers and K order it shares.
+// operand split ("x2"), for gfx950, and what the split kernels share: tile geometry, the activation-operand descriptor (Src),
+// raw buffer loads, the fp32 row loaders of the weight gradients and the sizing helpers.  Included by conv.hip inside its
+// anonymous namespace; conv_pl.h, conv_x2d.h and conv_x2w.h follow it and build on namespace x2.
 //
 // Why: the split kernels are limited by the matrix pipe's power-limited clock, i.e. by the number of MFMAs.  An fp32
 // value is, to 2^-24 relative, the sum of two fp16 values (11 + 11 significand bits, round to nearest), so
 //     a*b = a0*b0 + (a0*b1 + a1*b0) + O(2^-22 |ab|)
-// needs THREE fp16 MFMAs where the bf16 three-way split of conv_x3.h needs six (8 + 8 + 8 bits).  fp16 has only 5
+// needs THREE fp16 MFMAs where a bf16 three-way split needs six (8 + 8 + 8 bits).  fp16 has only 5
 // exponent bits, so each operand tensor is first multiplied by the power of two that puts its largest magnitude in
 // [2^13, 2^14) -- exact, and undone exactly in the epilogue.  An element more than 2^-16 below its tensor's maximum
 // loses (part of) its second term to fp16's subnormal range; its error then stays below 2^-39 of that maximum.
@@ -15,20 +16,47 @@
 // Scales: the weights' |w| maximum is taken when they are prepared (wamax -> 256-byte header of the prepared block); an
 // activation tensor's |x| maximum comes from amax_partial_kernel, launched by the conv call itself: 256 partial maxima
 // that every workgroup of the consumer reduces on its own, so there is no finishing launch and no host round trip.
+//
+// K is ordered (32-channel group, tap, channel in group): a 32-wide k chunk is one tap and 32 consecutive channels,
+// so the tap (hence the halo test and the pixel shift) is uniform over the chunk and a thread's 16 loads differ only
+// by a scalar channel-plane offset; and the nine chunks of a channel group follow each other, so the nine shifted
+// reads of the same 32 x (128 + halo) activation patch hit L1 / L2.
 #pragma once
 
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
 
 namespace x2 {
 
-using x3::KC;
-using x3::PITCH;
-using x3::PLANE;
+constexpr int KC = 32;
+constexpr int PITCH = 80;              // bytes per LDS row: 32 fp16 + 16 bytes of padding
+constexpr int PLANE = 128 * PITCH;     // one split plane of one operand
 constexpr int OPER = 2 * PLANE;
 constexpr int LDS_BYTES = 2 * OPER;    // 40960
 constexpr int NPART = 256;             // partial maxima per activation tensor
 constexpr int HEADER = 256;            // bytes in front of the planes of a prepared block: WPART partial |w| maxima
+
+struct Src {             // the activation operand: channel-concat of two NCHW tensors
+  const float* s1; const float* s2; int S1, S2;
+  const unsigned short* wp; int Mpad; int Kc;     // prepared weights, padded row count, channels (= S1 + S2)
+  int taps;                                       // 9 (3x3, pad 1) or 1 (1x1)
+  const unsigned char* pl; long pl_stride;        // pre-split activation planes (conv_pl.h) and bytes per plane, or null
+};
+
+// All global reads of the split kernels are raw BUFFER loads: a wave-uniform resource (tensor base + size in SGPRs), one
+// 32-bit per-lane byte offset and a scalar offset per load, so a chunk's loads cost no per-load address VALU; and a read
+// outside the tensor returns 0 instead of faulting, which is how halo lanes are zeroed (offset bit 31 set) and why
+// a shifted 16-pixel run may start one element before / end one element after its tensor.
+// (Buffer offsets are 32-bit: the host side keeps these kernels to tensors below 2 GB.)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
+}
+
+inline int pad128(int v) { return (v + 127) / 128 * 128; }
 
 // part[b] = max |x| over block b's grid-stride share (any n; 16-byte path when aligned).  1024 threads per block and two
 // independent 16-byte loads per thread and trip: with 256 x 256 threads the pass ran at 2.6 TB/s, latency-bound.
@@ -105,7 +133,7 @@ __device__ __forceinline__ float lo_part(float v) { return v - (float)(_Float16)
 
 // ---- weight preparation ---------------------------------------------------------------------------------------------
 // A prepared block = [HEADER bytes: partial |w| maxima][2 planes: Wp[split][k / 32][tap][row (pad 128)][k % 32] fp16 of scale*W],
-// W(row, k, tap) indexed as in x3::wprep_kernel.  WprepDesc == StkWprepDesc (include/stk.h); wp points at the header.
+// W(row, k, tap) = w[row * sm + k * sk + tap] (taps reversed when flip).  WprepDesc == StkWprepDesc (include/stk.h); wp points at the header.
 struct WprepDesc {
   const float* w; unsigned char* wp; long sm, sk; int M, Kc, Mpad, taps, flip, reserved;
 };
@@ -172,9 +200,15 @@ __global__ __launch_bounds__(256) void wprep_kernel(const WprepDesc* __restrict_
     out[plane + o] = __builtin_bit_cast(unsigned short, h1);
   }
 }
-inline long wp_bytes(int M, int Kc, int taps) { return HEADER + 2L * taps * x3::pad128(M) * Kc * 2; }
+inline long wp_bytes(int M, int Kc, int taps) { return HEADER + 2L * taps * pad128(M) * Kc * 2; }
 
-// ---- loaders (same slicing contract as conv_x3.h: st(g) of a chunk precedes ld(g) of the next one) -------------------
+// ---- loaders ---------------------------------------------------------------------------------------------------------
+// Staging is cut into slices so that a kernel can place slices between its MFMAs (the hipcc scheduler, left alone, runs
+// the whole staging phase first and the MFMAs after it).  A loader provides
+//     st(g, tile)        slice g of "registers of the current chunk -> LDS"
+//     ld(g, ...)         slice g of "global -> registers for chunk c"
+// and st(g) of a chunk always precedes ld(g) of the next one, so a register is reloaded only after its slice consumed it.
+//
 // 16 fp32 values of one LDS row -> two fp16 planes.  Slices 0..7 convert one pair each, 8..11 write one 16-byte piece.
 // X1 (the one-product forward of include/stk_fp16.h): the hi plane only -- one rounding, no lo residual.
 template <bool X1>
@@ -199,11 +233,11 @@ using Split16 = Split16X<false>;
 struct WpLoader {        // four 16-byte pieces per chunk: split j>>1, row (tid>>2) + 64 (j&1), segment tid&3
   __amdgpu_buffer_rsrc_t rs; unsigned voff, plane2, chunk2; int row, seg;
   u32x4 r[4];
-  __device__ __forceinline__ void init(const x3::Src& q, int m0, int tid) {
+  __device__ __forceinline__ void init(const Src& q, int m0, int tid) {
     row = tid >> 2; seg = tid & 3;
     plane2 = (unsigned)q.taps * q.Mpad * q.Kc * 2u;
     chunk2 = (unsigned)q.Mpad * KC * 2u;
-    rs = x3::make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + HEADER, 2L * plane2);
+    rs = make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + HEADER, 2L * plane2);
     voff = ((unsigned)(m0 + row) * KC + seg * 8) * 2u;
   }
   __device__ __forceinline__ void ld(int g, int c) {
@@ -216,17 +250,17 @@ struct WpLoader {        // four 16-byte pieces per chunk: split j>>1, row (tid>
   }
 };
 
-// activations, lanes along pixels; a thread holds 16 channels of one tap-shifted pixel (x3::ActLoader's addressing)
+// activations, lanes along pixels; a thread holds 16 channels of one tap-shifted pixel
 template <bool DUAL, int TAPS, bool X1>
 struct ActLoaderT {
   __amdgpu_buffer_rsrc_t rs1, rs2;
   int nl, kg, tb1, tb2; unsigned mask; float scale;
   float r[16]; Split16X<X1> sp;
-  __device__ __forceinline__ void init(const ConvP& p, const x3::Src& q, int n0, int tid, float s) {
+  __device__ __forceinline__ void init(const ConvP& p, const Src& q, int n0, int tid, float s) {
     nl = tid & 127;
     kg = __builtin_amdgcn_readfirstlane(tid >> 7);      // which 16 of the chunk's 32 channels
-    rs1 = x3::make_rsrc(q.s1, (long)p.N * q.S1 * p.HW * 4);
-    rs2 = x3::make_rsrc(q.s2, (long)p.N * (DUAL ? q.S2 : q.S1) * p.HW * 4);
+    rs1 = make_rsrc(q.s1, (long)p.N * q.S1 * p.HW * 4);
+    rs2 = make_rsrc(q.s2, (long)p.N * (DUAL ? q.S2 : q.S1) * p.HW * 4);
     mask = 0; tb1 = 0; tb2 = 0; scale = s;
     const int n = n0 + nl;
     if (n < p.N * p.HW) {
@@ -243,7 +277,7 @@ struct ActLoaderT {
     }
   }
   // slices 8..23 load one channel each (its register was consumed by conversion slice (g - 8) / 2 <= 7)
-  __device__ __forceinline__ void ld(int g, const ConvP& p, const x3::Src& q, int c) {
+  __device__ __forceinline__ void ld(int g, const ConvP& p, const Src& q, int c) {
     if (g < 8) return;
     const int cc = TAPS == 9 ? c / 9 : c, tap = c - cc * TAPS;   // scalar: chunk = (32-channel group, tap), tap fastest
     const int ci0 = cc * KC + kg * 16;
@@ -253,7 +287,7 @@ struct ActLoaderT {
     const unsigned dead = (((mask >> tap) & 1u) ^ 1u) << 31;     // halo lanes: outside the buffer -> 0
     const int shift = TAPS == 9 ? (tap / 3 - 1) * p.W + (tap % 3 - 1) : 0;
     const unsigned vo = (unsigned)(((first ? tb1 : tb2) + shift) * 4) | dead;
-    r[g - 8] = x3::bload(rs, vo, so + (unsigned)(g - 8) * p.HW * 4u);
+    r[g - 8] = bload(rs, vo, so + (unsigned)(g - 8) * p.HW * 4u);
   }
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp.st(g, r, scale, t, nl, kg * 16); }
 };
@@ -269,7 +303,7 @@ template <bool DUAL, int TAPS> struct ActLoader16 : ActLoaderT<DUAL, TAPS, true>
 // X1 (EP = OneProduct<..>, include/stk_fp16.h): only the hi(w) hi(x) MFMAs of each half chunk (4 of 12) are issued, with an
 // ActLoader16 (no lo plane) as BL.
 template <class BL, class EP, int WPS = 2>       // WPS: waves per SIMD the register allocation must admit
-__global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
+__global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                    int nchunks_total, int chunks_per_split, const float* __restrict__ xpart,
                                                    int nxpart) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
@@ -308,8 +342,9 @@ __global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, x3::Src q, int 
   const unsigned char* a_rd = As + (wm0 + fc) * PITCH + fk * 16;
   const unsigned char* b_rd = Bs + (wn0 + fc) * PITCH + fk * 16;
 
-  // Pipeline as in x3::gemm_kernel (LDS single-buffered, two barriers per chunk); with 12 MFMAs per half chunk each
-  // MFMA of the second half carries TWO staging slices.
+  // Pipeline: LDS single-buffered, two barriers per chunk.  Chunk c + 1 waits in registers while the first half of chunk c
+  // is multiplied; behind the second half it goes to LDS and chunk c + 2's loads are issued -- each of those 12 MFMAs
+  // carries TWO of the 24 staging slices.
 #define STK_X2_FRAGS(KK)                                                                               \
   _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int s = 0; s < 2; ++s) {         \
     a[i][s] = *reinterpret_cast<const halfx8*>(a_rd + s * PLANE + i * 32 * PITCH + (KK) * 32);          \
@@ -372,21 +407,157 @@ __global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, x3::Src q, int 
   }
 }
 
-// ---- 3x3 weight gradient, three taps per workgroup, on the two-way split ---------------------------------------------
-// x3::wgrad3_kernel (same tiling, same loads, same slab layout) with both operands scaled and split into two fp16
-// terms: 18 instead of 36 MFMAs per wave and half chunk.  The loaders are x3's with the splitter replaced.
+// The fp32 row loaders of the weight gradients (addressing only; RowsA / RowsBT add the split and the LDS store).
+// Operands: rows = channels, k = pixels (contiguous in NCHW).  Thread (row = tid>>1, half = tid&1) holds the
+// 16 consecutive pixels k0 + 16*half .. +15 of its channel, shifted by the tap for the x operand.  Requires W a
+// power of two >= 4 and H*W a power of two >= 16; SEG = min(W, 16): a 16-pixel run is 16 / SEG whole row segments.
+// With a concat input the first source must hold a multiple of 32 channels (a wave's 32 rows share one tensor).
+template <bool SHIFT, bool DUAL, int SEG>
+struct RowsLoader {
+  static_assert(SEG == 16 || SEG == 8 || SEG == 4, "row segment of a 16-pixel run");
+  static constexpr int NSEG = 16 / SEG;
+  __amdgpu_buffer_rsrc_t rs;
+  int rowoff;             // element offset of this thread's channel plane inside image 0 of its tensor
+  int bstride;            // elements between images in this thread's tensor
+  int row, half, dy, dx; bool rowok; unsigned okm;
+  float r[16];
+  __device__ __forceinline__ void init(const ConvP& p, const Src&, int o0, int tid, int zb) {
+    row = tid >> 1; half = tid & 1; okm = 0;
+    dy = SHIFT ? zb / 3 - 1 : 0; dx = SHIFT ? zb % 3 - 1 : 0;     // (a 1x1 layer passes the centre tap, zb = 4)
+    const int ch = o0 + row;
+    if (SHIFT) {                                   // x: channel of the concat input
+      rowok = ch < p.Cin;
+      const int c = rowok ? ch : 0;
+      const bool first = !DUAL || __builtin_amdgcn_readfirstlane(o0 + (tid >> 6) * 32) < p.C1;   // wave-uniform
+      rs = first ? make_rsrc(p.x1, (long)p.N * p.C1 * p.HW * 4) : make_rsrc(p.x2, (long)p.N * p.C2 * p.HW * 4);
+      rowoff = (first ? c : (c >= p.C1 ? c - p.C1 : 0)) * p.HW;
+      bstride = (first ? p.C1 : p.C2) * p.HW;
+    } else {                                       // dy: output channel
+      rowok = ch < p.Cout;
+      rs = make_rsrc(p.dy, (long)p.N * p.Cout * p.HW * 4);
+      rowoff = (rowok ? ch : 0) * p.HW;
+      bstride = p.Cout * p.HW;
+    }
+  }
+  // slice 14 computes the next run's mask and offsets, slices 15..19 issue its loads (all 16 registers were
+  // consumed by the conversion slices 0..7); the mask in use by those slices is replaced at slice 14.
+  unsigned os[NSEG], og[NSEG];      // byte offsets of the first element / of elements 1.. of each row segment
+  __device__ __forceinline__ void ld(int g, const ConvP& p, const Src&, int c) {
+    if (g == 14) {
+      const int k = c * KC + half * 16;              // first pixel of the run (global pixel index)
+      const bool kin = rowok && k < p.N * p.HW;      // N*H*W is a multiple of 16: a run is inside or outside as a whole
+      const int b = k >> p.ohw_shift, hw = k & (p.HW - 1);
+      const int y = hw >> p.ow_shift, x0 = hw & (p.W - 1);
+      unsigned m = 0;
+      if (!SHIFT) {
+        m = 0xffffu;
+      } else if (SEG == 16) {                        // one row segment of a row of >= 16 pixels
+        const bool yok = (unsigned)(y + dy) < (unsigned)p.H;
+        m = yok ? 0xffffu : 0u;
+        if (dx < 0 && x0 == 0) m &= ~1u;
+        if (dx > 0 && x0 + 16 == p.W) m &= ~0x8000u;
+      } else {                                       // NSEG whole rows of SEG pixels
+#pragma unroll
+        for (int sgi = 0; sgi < NSEG; ++sgi)
+          if ((unsigned)(y + sgi + dy) < (unsigned)p.H) m |= ((1u << SEG) - 1u) << (sgi * SEG);
+        constexpr unsigned FIRST = SEG == 8 ? 0x0101u : 0x1111u;
+        if (dx < 0) m &= ~FIRST;
+        if (dx > 0) m &= ~(FIRST << (SEG - 1));
+      }
+      okm = kin ? m : 0u;
+      // The run is contiguous in memory, but its element offsets may be negative where they are masked: column -1
+      // of the first row of the tensor (the first element of a segment), or whole leading segments when the row
+      // above the image is addressed.  A negative voffset plus an immediate is NOT wrapped back into the buffer by
+      // the range check, so each segment is read as two pieces -- its first element and the rest -- each from its
+      // own offset clamped at 0 (a clamped piece is entirely masked), immediates only inside a piece.  The offsets
+      // are made opaque because hipcc otherwise rewrites max(o + 1, 0) * 4 + imm as max(o, -1) * 4 + (imm + 4),
+      // i.e. back into the negative-base form.  A run that ends past the tensor reads 0 there (range check).
+      const int o = (kin ? b * bstride + rowoff + hw : 0) + dy * p.W + dx;
+#pragma unroll
+      for (int sgi = 0; sgi < NSEG; ++sgi) {
+        os[sgi] = (unsigned)(max(o + sgi * SEG, 0) * 4);
+        og[sgi] = (unsigned)(max(o + sgi * SEG + 1, 0) * 4);
+        asm volatile("" : "+v"(os[sgi]), "+v"(og[sgi]));
+      }
+    } else if (g == 15) {
+#pragma unroll
+      for (int sgi = 0; sgi < NSEG; ++sgi) r[sgi * SEG] = bload(rs, os[sgi], 0);
+    } else if (g >= 16 && g < 20) {
+      // the 16 - NSEG remaining elements in four slices: quarter q of every segment's tail
+      const int q = g - 16;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int sgi = j / SEG, e = j % SEG;                     // element e >= 1 of segment sgi
+        if (e >= 1 && ((e - 1) * 4) / (SEG - 1) == q) r[j] = bload(rs, og[sgi] + (unsigned)(e - 1) * 4u, 0);
+      }
+    }
+  }
+};
+
+// ---- 3x3 weight gradient, three taps per workgroup -------------------------------------------------------------------
+// A workgroup owns one kernel ROW (kh) of a 128(co) x 64(ci) block of dw: the three taps kw = 0, 1, 2 read the same x pixels
+// shifted by one, so a thread loads its 8-pixel run plus one pixel on each side ONCE, splits those 10 values once and writes
+// the three shifted windows to LDS; the dy tile is staged once for all three taps.  Both operands are scaled and split into
+// two fp16 terms: 18 MFMAs per wave and half chunk.
+//   A tile  [2 planes][128 co][32 px]            RowsA (unshifted dy rows)
+//   B tiles [3 taps][2 planes][64 ci][32 px]     Rows3: thread (row = tid >> 2, quarter = tid & 3) owns pixels 8q .. 8q + 7
+// Waves: 2 (co halves of 64 rows = 2 MFMA tiles) x 2 (ci halves of 32 = 1 MFMA tile); accumulators acc[2][3 taps].
+// Requires W a power of two >= 8 (an 8-pixel run stays inside one image row), H*W a power of two >= 32.
 constexpr int W3_BPLANE = 64 * PITCH;
 constexpr int W3_BTAP = 2 * W3_BPLANE;
 constexpr int W3_LDS = OPER + 3 * W3_BTAP;       // 20480 + 30720 = 51200 bytes
 
-struct RowsA : x3::RowsLoader<false, false, 16> {          // dy: 16 consecutive pixels of one output channel
+// Rows3's addressing: the x run of 8 pixels plus the one on each side, for the three taps of kernel row kh
+template <bool DUAL>
+struct Rows3Loader {
+  float r[10];             // elements -1 .. 8  (first: the member layout steers wgrad3_kernel's schedule)
+  __amdgpu_buffer_rsrc_t rs;
+  int rowoff, bstride, row, quarter, dy; bool rowok;
+  unsigned okm;            // bit e + 1: element e (-1 .. 8) of the current run is valid
+  unsigned om, o0, o8;
+  __device__ __forceinline__ void init(const ConvP& p, int n0, int tid, int kh) {
+    row = tid >> 2; quarter = tid & 3; dy = kh - 1; okm = 0;
+    const int ch = n0 + row;
+    rowok = ch < p.Cin;
+    const int c = rowok ? ch : 0;
+    const bool first = !DUAL || __builtin_amdgcn_readfirstlane(n0 + (tid >> 6) * 16) < p.C1;   // wave-uniform
+    rs = first ? make_rsrc(p.x1, (long)p.N * p.C1 * p.HW * 4) : make_rsrc(p.x2, (long)p.N * p.C2 * p.HW * 4);
+    rowoff = (first ? c : (c >= p.C1 ? c - p.C1 : 0)) * p.HW;
+    bstride = (first ? p.C1 : p.C2) * p.HW;
+  }
+  // slice 14: mask and offsets of the next run; 15: the two halo elements; 16, 17: the eight pixels of the run
+  __device__ __forceinline__ void ld(int g, const ConvP& p, int c) {
+    if (g == 14) {
+      const int k = c * KC + quarter * 8;
+      const bool kin = rowok && k < p.N * p.HW;
+      const int b = k >> p.ohw_shift, hw = k & (p.HW - 1);
+      const int y = hw >> p.ow_shift, x0 = hw & (p.W - 1);
+      unsigned m = (unsigned)(y + dy) < (unsigned)p.H ? 0x3ffu : 0u;
+      if (x0 == 0) m &= ~1u;                       // column -1
+      if (x0 + 8 == p.W) m &= ~0x200u;             // column W
+      okm = kin ? m : 0u;
+      // offsets clamped at 0 and opaque, pieces [-1], [0..7], [8]: see RowsLoader
+      const int o = (kin ? b * bstride + rowoff + hw : 0) + dy * p.W;
+      om = (unsigned)(max(o - 1, 0) * 4); o0 = (unsigned)(max(o, 0) * 4); o8 = (unsigned)(max(o + 8, 0) * 4);
+      asm volatile("" : "+v"(om), "+v"(o0), "+v"(o8));
+    } else if (g == 15) {
+      r[0] = bload(rs, om, 0);
+      r[9] = bload(rs, o8, 0);
+    } else if (g == 16 || g == 17) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[1 + (g - 16) * 4 + j] = bload(rs, o0 + (unsigned)((g - 16) * 4 + j) * 4u, 0);
+    }
+  }
+};
+
+struct RowsA : RowsLoader<false, false, 16> {          // dy: 16 consecutive pixels of one output channel
   Split16 sp2; float scale;
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp2.st(g, r, scale, t, row, half * 16, okm); }
 };
 
 template <bool DUAL>
-struct Rows3 : x3::Rows3Loader<DUAL> {                     // x: the 10-pixel run of one input channel, three windows
-  using B = x3::Rows3Loader<DUAL>;
+struct Rows3 : Rows3Loader<DUAL> {                     // x: the 10-pixel run of one input channel, three windows
+  using B = Rows3Loader<DUAL>;
   _Float16 hh[2][10]; float scale;
   // slices 0..4 split two elements each, 5..10 pack + write one (tap, plane) window each
   __device__ __forceinline__ void st(int g, unsigned char* t) {
@@ -435,7 +606,7 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(ConvP p, int tiles_m, int t
   const int c_begin = zs * chunks_per_split;
   const int c_last = min(nchunks_total, c_begin + chunks_per_split) - 1;
 
-  x3::Src q = {};
+  Src q = {};
   RowsA al;
   Rows3<DUAL> bl;
   al.init(p, q, m0, tid, 4); al.scale = sa;
@@ -525,15 +696,15 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(ConvP p, int tiles_m, int t
   }
 }
 
-// ---- per-tap weight gradient (1x1 layers, 3x3 on 4-wide maps) on the two-way split --------------------------------------
-// x3::gemm_kernel<RowsLoader, RowsLoader, EpWgrad> with both operands scaled and split into two fp16 terms: 12 instead
-// of 24 MFMAs per 16-k step and ~6 instead of ~10 conversion VALU per element.  With half the MFMAs the conversions no
-// longer hide behind the second half-chunk alone, so a chunk's work is laid out over both halves: the split of chunk
+// ---- per-tap weight gradient (1x1 layers, 3x3 on 4-wide maps) ------------------------------------------------------------
+// One 128 x 128 tile of one tap per workgroup, rows = output channels (dy), columns = input channels (x), k = pixels; both
+// operands scaled and split into two fp16 terms: 12 MFMAs per 16-k step.  With so few MFMAs the conversions do not hide
+// behind one half-chunk alone, so a chunk's work is laid out over both halves: the split of chunk
 // c + 1 (registers only) and the load issue of chunk c + 2 ride on the MFMAs of kk = 0, the eight LDS stores on those of
 // kk = 1 (after the barrier that retires the reads of chunk c).
 template <bool DUAL, int SEG, bool X1>
-struct RowsBT : x3::RowsLoader<true, DUAL, SEG> {          // x: 16 consecutive (tap-shifted) pixels of one input channel
-  using B = x3::RowsLoader<true, DUAL, SEG>;
+struct RowsBT : RowsLoader<true, DUAL, SEG> {          // x: 16 consecutive (tap-shifted) pixels of one input channel
+  using B = RowsLoader<true, DUAL, SEG>;
   Split16X<X1> sp2; float scale;
   __device__ __forceinline__ void st(int g, unsigned char* t) { sp2.st(g, B::r, scale, t, B::row, B::half * 16, B::okm); }
 };
@@ -541,7 +712,7 @@ template <bool DUAL, int SEG> struct RowsB : RowsBT<DUAL, SEG, false> {};
 template <bool DUAL, int SEG> struct RowsB16 : RowsBT<DUAL, SEG, true> {};     // hi plane only (OneProduct weight gradient)
 
 // Unshifted rows (dy always; x of a 1x1 layer): the thread's 16 consecutive pixels are one aligned 64-byte run, read as
-// four 16-byte loads.  (x3::RowsLoader reads a run element by element because a tap shift breaks the alignment and needs
+// four 16-byte loads.  (RowsLoader reads a run element by element because a tap shift breaks the alignment and needs
 // a per-element mask; with 32 such loads per thread and chunk, each touching 64 separate 64-byte segments, the per-tap
 // kernel was bound by address processing: 54 us for the 256 -> 256 layer at 16 x 16 against ~6 us of MFMAs.)
 template <bool IS_X, bool DUAL, bool X1>
@@ -549,25 +720,25 @@ struct RowsUT {
   __amdgpu_buffer_rsrc_t rs;
   int rowoff, bstride, row, half; bool rowok; unsigned voff;
   float r[16]; Split16X<X1> sp2; float scale;
-  __device__ __forceinline__ void init(const ConvP& p, const x3::Src&, int o0, int tid, int) {
+  __device__ __forceinline__ void init(const ConvP& p, const Src&, int o0, int tid, int) {
     row = tid >> 1; half = tid & 1; voff = 0x80000000u;
     const int ch = o0 + row;
     if (IS_X) {
       rowok = ch < p.Cin;
       const int c = rowok ? ch : 0;
       const bool first = !DUAL || __builtin_amdgcn_readfirstlane(o0 + (tid >> 6) * 32) < p.C1;   // wave-uniform
-      rs = first ? x3::make_rsrc(p.x1, (long)p.N * p.C1 * p.HW * 4) : x3::make_rsrc(p.x2, (long)p.N * p.C2 * p.HW * 4);
+      rs = first ? make_rsrc(p.x1, (long)p.N * p.C1 * p.HW * 4) : make_rsrc(p.x2, (long)p.N * p.C2 * p.HW * 4);
       rowoff = (first ? c : (c >= p.C1 ? c - p.C1 : 0)) * p.HW;
       bstride = (first ? p.C1 : p.C2) * p.HW;
     } else {
       rowok = ch < p.Cout;
-      rs = x3::make_rsrc(p.dy, (long)p.N * p.Cout * p.HW * 4);
+      rs = make_rsrc(p.dy, (long)p.N * p.Cout * p.HW * 4);
       rowoff = (rowok ? ch : 0) * p.HW;
       bstride = p.Cout * p.HW;
     }
   }
   // slice 14: the run's byte offset (bit 31 = outside: the loads return 0); slices 15..18: one 16-byte load each
-  __device__ __forceinline__ void ld(int g, const ConvP& p, const x3::Src&, int c) {
+  __device__ __forceinline__ void ld(int g, const ConvP& p, const Src&, int c) {
     if (g == 14) {
       const int k = c * KC + half * 16;
       const bool kin = rowok && k < p.N * p.HW;
@@ -611,7 +782,7 @@ __global__ __launch_bounds__(256) void wgemm_kernel(ConvP p, int M, int Nn, int 
   const int c_begin = zs * chunks_per_split;
   const int c_last = min(nchunks_total, c_begin + chunks_per_split) - 1;
 
-  x3::Src q = {};
+  Src q = {};
   AL al; BL bl;
   al.init(p, q, m0, tid, 4); al.scale = sa;
   bl.init(p, q, n0, tid, taps_z == 1 ? 4 : zb); bl.scale = sb;

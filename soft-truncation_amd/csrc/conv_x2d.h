@@ -20,7 +20,7 @@
 
 namespace x2d {
 
-using x3::KC;
+using x2::KC;
 typedef __attribute__((address_space(3))) void lds_void;
 
 template <int TN>
@@ -52,7 +52,7 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* 
 // a chunk covers 64 k with the same DMA, barrier and fragment-read counts and issues 4 instead of 6 MFMAs per tile;
 // nchunks_total counts channel-group PAIRS.  An odd group count leaves the last pair's second slot to the dead-offset DMA of zeros.
 template <int TAPS, int TN, class EP, int NBUF = 1, int ABL = 0>
-__global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
+__global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x2::Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                       int nchunks_total, int chunks_per_split,
                                                       const float* __restrict__ xpart, int nxpart) {
   using G = Geo<TN>;
@@ -80,10 +80,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
   // A: prepared weights, [split][k / 32][tap][row (Mpad)][32] fp16 behind the header; wave w stages rows 32 w .. 32 w + 31
   const unsigned a_plane2 = (unsigned)q.taps * q.Mpad * q.Kc * 2u;
   const unsigned a_chunk2 = (unsigned)q.Mpad * KC * 2u;
-  const __amdgpu_buffer_rsrc_t a_rs = x3::make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + x2::HEADER, 2L * a_plane2);
+  const __amdgpu_buffer_rsrc_t a_rs = x2::make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + x2::HEADER, 2L * a_plane2);
   const unsigned a_voff = (unsigned)(m0 + 32 * wid + (lane >> 2)) * 64u + seg_src;
   // B: planes [split][n][cb][pixel][32]; wave w stages rows (TN / 4) w .. + TN / 4 - 1 in blocks of 16
-  const __amdgpu_buffer_rsrc_t b_rs = x3::make_rsrc(q.pl, 2L * q.pl_stride);
+  const __amdgpu_buffer_rsrc_t b_rs = x2::make_rsrc(q.pl, 2L * q.pl_stride);
   const unsigned b_ps = (unsigned)q.pl_stride;
   const int Cb = q.Kc >> 5;
   unsigned b_base[G::BBLK], b_mask[G::BBLK];
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x3::Src q, int M,
 // X1 (EP = OneProduct<..>): the one-product form of gemm_kernel above -- the halo tile's two split slots hold split 0 of
 // channel groups 2 cc and 2 cc + 1, and `ngroups` counts group PAIRS.
 template <int W, class EP, int NB>
-__global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, int M, int Nn, int tiles_m, int tiles_n,
+__global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x2::Src q, int M, int Nn, int tiles_m, int tiles_n,
                                                            int ngroups, const float* __restrict__ xpart, int nxpart) {
   constexpr int TN = 128, R = TN / W, TP = W + 2, HR = (R + 2) * TP, NI = (HR + 15) / 16, HRP = NI * 16;
   constexpr bool X1 = is_x1<EP>::value;
@@ -273,9 +273,9 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x3::Src q, i
   const unsigned seg_src = (unsigned)((lane & 3) ^ ((lane >> 4) & 3)) * 16u;
   const unsigned a_plane2 = (unsigned)q.taps * q.Mpad * q.Kc * 2u;
   const unsigned a_chunk2 = (unsigned)q.Mpad * KC * 2u;
-  const __amdgpu_buffer_rsrc_t a_rs = x3::make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + x2::HEADER, 2L * a_plane2);
+  const __amdgpu_buffer_rsrc_t a_rs = x2::make_rsrc(reinterpret_cast<const unsigned char*>(q.wp) + x2::HEADER, 2L * a_plane2);
   const unsigned a_voff = (unsigned)(m0 + 32 * wid + (lane >> 2)) * 64u + seg_src;
-  const __amdgpu_buffer_rsrc_t b_rs = x3::make_rsrc(q.pl, 2L * q.pl_stride);
+  const __amdgpu_buffer_rsrc_t b_rs = x2::make_rsrc(q.pl, 2L * q.pl_stride);
   const unsigned b_ps = (unsigned)q.pl_stride;
   // halo tile rows of this lane: instruction i = wid + 4 k covers LDS rows 16 i .. 16 i + 15, lane -> row 16 i + lane / 4
   const int Cb = q.Kc >> 5;

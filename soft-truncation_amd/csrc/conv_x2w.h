@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
   const int c_last = min(a.nchunks_total, c_begin + a.chunks_per_split) - 1;
 
   // ---- DMA sources ----------------------------------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t a_rs = x3::make_rsrc(a.dypl, 2L * a.dy_ps);
-  const __amdgpu_buffer_rsrc_t b_rs = x3::make_rsrc(a.xpl, 2L * a.x_ps);
+  const __amdgpu_buffer_rsrc_t a_rs = x2::make_rsrc(a.dypl, 2L * a.dy_ps);
+  const __amdgpu_buffer_rsrc_t b_rs = x2::make_rsrc(a.xpl, 2L * a.x_ps);
   const int piece = (lane & 3) * 16;
   // dy tile of this wave's block: slot s = 16 j + lane / 4 = (row r, column c) holds map pixel (y0 + r, x0 + c - 1)
   int a_rel[A_INSTR], a_c[A_INSTR];

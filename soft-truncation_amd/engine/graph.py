@@ -339,7 +339,7 @@ class Conv(Op):
 
   def _kind(self, lib, direction):
     """Kernel label for the profiler: direction, taps and the kernel family csrc/conv.hip picks for this shape
-    (t64 / t128 = f32-input MFMA tiles, x3 = bf16 three-way split, x2 = fp16 two-way split)."""
+    (t64 / t128 = f32-input MFMA tiles, thin = streaming kernels of a <= 4 channel side, x2 = the fp16 two-way split)."""
     key = '_kind_' + direction
     k = getattr(self, key, None)
     if k is None:

@@ -8,7 +8,7 @@ in the split itself shows too.  Every launch runs twice and must repeat bit for 
 order); forward and data-gradient cases run once more on weights prepared by stk_conv2d_wprep_batch, which must give the
 same bits.  Errors are max|got - ref| / max|ref|, printed per case with -s, bounded by tests/_tolerances.py.
 
-Launch forms (csrc/conv.hip launch_x3 / STK_PL_LAUNCH, x2w::plan):
+Launch forms (csrc/conv.hip split_plan / launch_split / split_gemm, x2w::plan):
   h16 / h32 / h64   x2d::gemm_halo_kernel<W>: 3x3, >= 192 tiles of 128 x 128 (no K split), W in {16, 32, 64}
   g9 / g1           x2d::gemm_kernel<9 | 1>: un-split, other widths / 1x1 (Conv2d and NIN layouts)
   ks                the K-split EpSlab form + the slab sum (< 192 tiles)

@@ -510,8 +510,12 @@ def test_conv_prepared_weights(hip_lib, case):
   shape = (C1, C2, N, H, W, Cout, K, K, stride, pad)
   fb = max(int(lib.conv2d_fwd_ws_bytes(*shape)), int(lib.conv2d_dgrad_ws_bytes(*shape)))
   nb = [int(lib.conv2d_wp_bytes(direction, *shape)) for direction in (0, 1)]
-  assert (nb[0] > 0) == (int(lib.conv2d_variant(0, C1, C2, N, H, W, Cout, OH, OW, K, K, stride, pad, layout)) in (2, 5))
-  assert (nb[1] > 0) == (int(lib.conv2d_variant(1, C1, C2, N, H, W, Cout, OH, OW, K, K, stride, pad, layout)) in (2, 5))
+  assert (nb[0] > 0) == (int(lib.conv2d_variant(0, C1, C2, N, H, W, Cout, OH, OW, K, K, stride, pad, layout)) == 5)
+  assert (nb[1] > 0) == (int(lib.conv2d_variant(1, C1, C2, N, H, W, Cout, OH, OW, K, K, stride, pad, layout)) == 5)
+  # the block layout the kernels read: a 256-byte header, then two fp16 planes of taps x pad128(M) x Kc
+  for direction, (M, Kc) in enumerate(((Cout, Cin), (Cin, Cout))):
+    if nb[direction]:
+      assert nb[direction] == 256 + 2 * K * K * ((M + 127) // 128 * 128) * Kc * 2, (direction, nb[direction])
   fws = torch.full((fb // 4 + 64,), float('nan'), device=d)
   blocks, descs, items = [], [], 0
   for direction in (0, 1):

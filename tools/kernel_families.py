@@ -25,7 +25,7 @@ FAMILIES = [   # (family, regex on the kernel name), first match wins
   ('dgrad planes x2d (halo / gemm)', r'x2d::gemm(_halo)?_kernel<.*?::EpDgrad\b'),
   ('fwd fp32 operands x2::gemm_kernel', r'x2::gemm_kernel<.*?::EpFwd\b'),
   ('dgrad fp32 operands x2::gemm_kernel', r'x2::gemm_kernel<.*?::EpDgrad\b'),
-  ('other convolution kernels (f32-input tiles, thin, wprep, slab sums, planes)', r'conv|thin|wprep|wamax|slab|splitk|split_planes|igemm|x3::|gemm'),
+  ('other convolution kernels (f32-input tiles, thin, wprep, slab sums, planes)', r'conv|thin|wprep|wamax|slab|splitk|split_planes|igemm|gemm'),
   ('GroupNorm', r'gn_'),
   ('attention', r'attn'),
   ('everything else', r'.'),

@@ -15,7 +15,7 @@ extra = sys.argv[2] if len(sys.argv) > 2 else ''      # e.g. '--workload celeba6
 
 
 def short(n):
-  n = re.sub(r'\(anonymous namespace\)::|igemm::|void |x3::', '', n)      # x2:: is kept: it tells the two gemm_kernel families apart
+  n = re.sub(r'\(anonymous namespace\)::|igemm::|void ', '', n)      # x2:: is kept: it tells the two gemm_kernel families apart
   n = re.sub(r'Cfg<(\d+), (\d+), (\d+)>', r'C\1', n)
   return n.split('(')[0][:90]
 
