@@ -6,6 +6,7 @@
 // 256 B aligned and H*W is a multiple of 16), with a scalar path otherwise; grids are capped at
 // 8 blocks per CU and grid-stride the rest.
 #include "common.h"
+#include "stk_blocks.h"
 
 // A product that must be ROUNDED before it is used (torch evaluates a * x + b as two kernels): HIP's __fmul_rn is a plain
 // product the compiler may contract into an fma; an empty asm on the value is an optimisation barrier it cannot see through.
@@ -297,6 +298,24 @@ __global__ void fourier_embedding_kernel(const float* __restrict__ x, const floa
     const float p = x[b] * W[j] * 2.f * 3.14159265358979323846f;
     out[(long)b * 2 * nf + j] = sinf(p);
     out[(long)b * 2 * nf + nf + j] = cosf(p);
+  }
+}
+
+// d/dx of the Gaussian Fourier features, one 256-thread block per sample, from the forward's own sin / cos values:
+// dx[b] = beta dx[b] + 2 pi sum_j W_j (dy[b,j] cos p_bj - dy[b,nf+j] sin p_bj)
+__global__ __launch_bounds__(256) void fourier_embedding_bwd_kernel(const float* __restrict__ W, const float* __restrict__ y,
+                                                                    const float* __restrict__ dy, float* __restrict__ dx,
+                                                                    float beta, int nf) {
+  __shared__ float red[8];
+  const int b = blockIdx.x;
+  const float* yb = y + (long)b * 2 * nf;
+  const float* gb = dy + (long)b * 2 * nf;
+  float acc[1] = {0.f};
+  for (int j = threadIdx.x; j < nf; j += 256) acc[0] += W[j] * (gb[j] * yb[nf + j] - gb[nf + j] * yb[j]);
+  block_sum<1>(acc, red);
+  if (threadIdx.x == 0) {
+    const float g = 2.f * 3.14159265358979323846f * acc[0];
+    dx[b] = beta == 0.f ? g : beta * dx[b] + g;
   }
 }
 
@@ -625,6 +644,14 @@ int stk_fourier_embedding_f32(const float* x, const float* W, float* out, int B,
   if (!x || !W || !out || B <= 0 || nf <= 0) return STK_EINVAL;
   hipLaunchKernelGGL(fourier_embedding_kernel, dim3(stk_ew_grid((long)B * nf)), dim3(256), 0, S(stream), x, W, out,
                      B, nf);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+int stk_fourier_embedding_bwd_f32(const float* W, const float* y, const float* dy, float* dx, float beta, int B, int nf,
+                                  void* stream) {
+  if (!W || !y || !dy || !dx || B <= 0 || nf <= 0) return STK_EINVAL;
+  hipLaunchKernelGGL(fourier_embedding_bwd_kernel, dim3(B), dim3(256), 0, S(stream), W, y, dy, dx, beta, nf);
   STK_CHECK_LAUNCH();
   return STK_OK;
 }

@@ -50,7 +50,7 @@ def _arena(n, device):
   if _POISON:
     t.fill_(float('nan'))
   return t
-from .flat import FlatParams
+from .flat import FlatParams, flat_owner
 from .graph import Conv, Graph, Runtime
 
 
@@ -397,13 +397,38 @@ class _NetFn(torch.autograd.Function):
     # estimators of likelihood.py) never reaches the anchor's accumulation node; .backward() does.  Without them the
     # weight / bias / affine gradients are neither computed nor added into p.grad -- as in the reference, where autograd
     # only walks the branches that were asked for.
-    pg = True
-    try:
-      pg = bool(torch._C._will_engine_execute_node(ctx.ex._anchor_acc))
-    except Exception:      # API absent, or the anchor itself is among autograd.grad's inputs
-      pg = True
-    gx = ctx.ex.run_backward(ctx.c, gout, param_grads=pg)
+    gx = ctx.ex.run_backward(ctx.c, gout, param_grads=_wants_param_grads(ctx.ex._anchor_acc))
     return None, None, None, (gx if ctx.need_xgrad else None), None, None
+
+
+def _wants_param_grads(anchor_acc):
+  """Does the running backward pass reach the parameters?  (the AccumulateGrad node of an executor's anchor stands for them)"""
+  try:
+    return bool(torch._C._will_engine_execute_node(anchor_acc))
+  except Exception:        # API absent, or the anchor itself is among autograd.grad's inputs
+    return True
+
+
+class _ModuleFn(torch.autograd.Function):
+  """One stand-alone module evaluation (ModuleExecutor.apply) as one autograd node: N tensor inputs, one output.  Returns the
+  gradients of the inputs that need one; the parameter gradients go into the flat gradient buffer (and so into p.grad) only
+  when the backward pass reaches the parameters, as for the whole network (_NetFn)."""
+
+  @staticmethod
+  def forward(ctx, ex, names, training, anchor, *inputs):
+    mask = tuple(bool(m) for m in ctx.needs_input_grad[4:])
+    out, c = ex.run_module_forward(names, inputs, mask, training, with_backward=True)
+    ctx.ex, ctx.c = ex, c
+    ex._awaiting.add(c)
+    return out
+
+  @staticmethod
+  def backward(ctx, gout):
+    if ctx.c.released:
+      raise RuntimeError('module backward called twice on the same forward; the engine frees activations after the '
+                         'first backward')
+    grads = ctx.ex.run_backward(ctx.c, gout, param_grads=_wants_param_grads(ctx.ex._anchor_acc))
+    return (None, None, None, None) + tuple(grads)
 
 
 class Executor:
@@ -656,17 +681,26 @@ class Executor:
     else:
       precision = self.mode
     prog = self.program(B, H, W, need_xgrad, precision)
+    inputs = {'x': x, 'emb': emb_in}
+    if sigma is not None:
+      inputs['sigma'] = sigma
+    return self._launch_forward(prog, inputs, training, with_backward, flat)
+
+  def _uses_dropout(self):
+    return self.model._uses_dropout()
+
+  def _launch_forward(self, prog, inputs, training, with_backward, flat, window=False):
+    """Copy `inputs` (graph input key -> tensor) in, run the forward of `prog` (eagerly or as a hipGraph replay) and return
+    (a copy of the output, the context a backward needs).  `window`: the eager launches run inside the launch window."""
     c = prog.acquire()
     g = prog.graph
-    self._copy_in(c, 'x', x)
-    self._copy_in(c, 'emb', emb_in)
-    if sigma is not None:
-      self._copy_in(c, 'sigma', sigma)
+    for key, value in inputs.items():
+      self._copy_in(c, key, value)
     self._prepare_weights(prog, with_backward)
     if with_backward and prog.gn_table is None and getattr(g, 'gn_folds', None):
       prog.build_gn_folds(flat.grad.data_ptr())          # allocation + upload: never inside a hipGraph capture
     seed = 0
-    if training and self.model._uses_dropout():
+    if training and self._uses_dropout():
       seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     c.uses += 1
     done = False
@@ -681,8 +715,9 @@ class Executor:
         c.rt = self._runtime(c, training, 0, c.seed_t.data_ptr(), with_backward)
     if not done:
       rt = self._runtime(c, training, seed, None, with_backward)
-      for op in g.ops:
-        op.forward(rt)
+      with _launch_window(window and _LIB_ONLY and self.lib.is_device):
+        for op in g.ops:
+          op.forward(rt)
       c.rt = rt
     o = g.output
     out = c.act[o.off:o.off + o.numel].view(o.shape).clone()
@@ -765,12 +800,18 @@ class Executor:
           op.backward(rt)
         rt.flush_folds()
         rt.join_side()
-    gx = None
-    xin = g.inputs['x']
-    if xin.needs_grad:
-      gx = c.gact[xin.goff:xin.goff + xin.numel].view(xin.shape).clone()
+    gx = self._input_grads(c)
     prog.release(c)
     return gx
+
+  def _input_grad(self, c, key):
+    t = c.prog.graph.inputs[key]
+    if not t.needs_grad:
+      return None
+    return c.gact[t.goff:t.goff + t.numel].view(t.shape).clone()
+
+  def _input_grads(self, c):
+    return self._input_grad(c, 'x')
 
   def _hand_over(self, rt, hook, ranges):
     """Issue the all-reduce of finished buckets behind BOTH streams of the backward without making either wait for the other."""
@@ -836,5 +877,113 @@ class Executor:
     if torch.is_grad_enabled():
       return _NetFn.apply(self, training, self._anchor, x, emb_in, sigma)
     out, c = self.run_forward(x, emb_in, sigma, training, False, flat=self.flat)
+    c.prog.release(c)
+    return out
+
+
+def _device_error(backend, device, what):
+  return RuntimeError(f'backend {backend} cannot run {what} on {device}: the score network and its blocks run on the HIP '
+                      f'kernels only (no CPU / PyTorch fallback)')
+
+
+class ModuleExecutor(Executor):
+  """Programs of one module that is not a whole NCSNpp (a building block called on its own, models/layerspp.py).
+
+  The module declares named tensor inputs; ``emit(g, **inputs)`` builds its graph from the graph tensors of those inputs and
+  returns the output.  Programs are cached per (input names, input shapes, inputs that need a gradient); the hipGraph
+  captures, prepared weights and the weight-gradient side stream work as for the model.
+
+  Parameters are never moved away from a layout that holds them: a block of a model whose engine has bound it plans against
+  that model's FlatParams (its offsets, its gradient buffer) and leaves the model's programs valid.  A free-standing block
+  gets a FlatParams of its own; when a model later lays the same parameters out again, the model's layout wins and the
+  block re-plans against it on its next call."""
+
+  def __init__(self, module, emit, backend=None):
+    super().__init__(module, backend=backend)
+    self.emit = emit
+
+  def _uses_dropout(self):
+    return any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in self.model.modules())
+
+  def _own_groups(self):
+    groups = []
+    for mod in self.model.modules():
+      if hasattr(mod, 'qkv_params'):              # AttnBlockpp: q / k / v interleaved as for the model (NCSNpp._flat_groups)
+        ws, bs = mod.qkv_params()
+        groups += [('cols', ws), bs]
+    return tuple(groups)
+
+  def ensure_flat(self, device=None):
+    params = list(self.model.parameters())
+    if params:
+      device = params[0].device
+    if self.lib.is_device != (device.type == 'cuda'):
+      raise _device_error(self.lib.backend, device, f'a {type(self.model).__name__}')
+    if params:
+      flat = flat_owner(params)                   # the bound model's layout, or this block's own one
+      if flat is None:
+        flat = FlatParams(params, device, groups=self._own_groups())
+    elif self.flat is not None and self.flat.device == device:
+      flat = self.flat
+    else:
+      flat = FlatParams([], device)
+    if flat is not self.flat:
+      self.flat = flat
+      self.programs.clear()
+    if self._anchor is None or self._anchor.device != device:
+      self._anchor = torch.zeros((), dtype=torch.float32, device=device, requires_grad=True)
+      with torch.enable_grad():
+        self._anchor_acc = self._anchor.view_as(self._anchor).grad_fn.next_functions[0][0]
+    if not flat.grads_bound():
+      flat.rebind_grads()
+    return flat
+
+  def module_program(self, names, shapes, mask):
+    key = (names, shapes, mask)
+    prog = self.programs.get(key)
+    if prog is None:
+      g = Graph(self.flat, self.lib)
+      ins = {n: g.input(n, s, needs_grad=m) for n, s, m in zip(names, shapes, mask)}
+      out = self.emit(g, **ins)
+      g.finalize(out, self.lib)
+      for n, t in ins.items():
+        if t.needs_grad and t.seen == 0:
+          raise NotImplementedError(f'{type(self.model).__name__}: no kernel computes the gradient with respect to input '
+                                    f'{n!r}')
+      prog = self.programs[key] = Program(g, self.flat.device)
+    return prog
+
+  def run_module_forward(self, names, inputs, mask, training, with_backward):
+    flat = self.flat
+    with stk_lib.device_guard(flat.device):
+      prog = self.module_program(names, tuple(tuple(t.shape) for t in inputs), mask)
+      return self._launch_forward(prog, dict(zip(names, inputs)), training, with_backward, flat, window=True)
+
+  def _input_grads(self, c):
+    return tuple(self._input_grad(c, n) for n in c.prog.graph.inputs)
+
+  def apply(self, **inputs):
+    """Differentiable evaluation of the module on the named fp32 tensors (None = input absent)."""
+    names = tuple(n for n, t in inputs.items() if t is not None)
+    tensors = []
+    device = next(iter(self.model.parameters()), inputs[names[0]]).device
+    for n in names:
+      t = inputs[n]
+      if t.device.type != 'cuda' and self.lib.is_device:
+        raise _device_error(self.lib.backend, t.device, f'{type(self.model).__name__} input {n!r}')
+      if t.device != device:
+        raise RuntimeError(f'{type(self.model).__name__}: input {n!r} is on {t.device}, the module on {device}')
+      if t.dtype != torch.float32:
+        raise ValueError(f'{type(self.model).__name__}: input {n!r} is {t.dtype}; the blocks run in fp32 only')
+      tensors.append(t.contiguous())
+    self.ensure_flat(device)
+    training = self.model.training
+    if torch.is_grad_enabled():
+      mask = tuple(bool(t.requires_grad) for t in tensors)
+      prog = self.module_program(names, tuple(tuple(t.shape) for t in tensors), mask)
+      if prog.graph.output.needs_grad:
+        return _ModuleFn.apply(self, names, training, self._anchor, *tensors)
+    mask = (False,) * len(tensors)
+    out, c = self.run_module_forward(names, tensors, mask, training, with_backward=False)
     c.prog.release(c)
     return out

@@ -112,6 +112,15 @@ class FlatParams:
       return None
     return ent[0]
 
+  def holds(self, params):
+    """True when every parameter of `params` has a slot in this layout and its data still aliases it."""
+    base = self.data.data_ptr()
+    for p in params:
+      slot = self._slot.get(id(p))
+      if slot is None or p.data_ptr() != base + 4 * slot[0]:
+        return False
+    return True
+
   def offset_of(self, p):
     o, _, tr = self._slot[id(p)]
     return o, tr
@@ -189,4 +198,14 @@ def flat_of(params, full=True):
     if len(params) != len(owner.params) and len(params) != len(owner._grad_ptrs):
       # neither the model's parameters nor its trainable ones: a partial list cannot be stepped as one flat range
       return None
+  return owner
+
+
+def flat_owner(params):
+  """The FlatParams whose buffers hold all of ``params`` right now (a bound model's layout, or a block's own one), else None.
+  A stand-alone block plans against it instead of laying its parameters out anew, which would move them away from it."""
+  params = list(params)
+  owner = getattr(params[0], '_stk_flat', None) if params else None
+  if owner is None or not owner.holds(params):
+    return None
   return owner

@@ -720,21 +720,30 @@ class TimestepEmbedding(Op):
 
 
 class FourierEmbedding(Op):
-  """GaussianFourierProjection (models/layerspp.py:45-54); W is frozen (requires_grad=False)."""
+  """GaussianFourierProjection (models/layerspp.py:45-54); W is frozen (requires_grad=False).  The network's noise level
+  needs no gradient; a stand-alone projection's input may (include/stk_blocks.h)."""
 
   def __init__(self, g, x, W, name='temb.fourier'):
     self.x, self.W = x, W
     self.nf = W.shape[0]
-    self.y = g.new((x.shape[0], 2 * self.nf), needs_grad=False, name=name)
+    self.y = g.new((x.shape[0], 2 * self.nf), needs_grad=x.needs_grad, name=name)
+    if x.needs_grad:
+      if not getattr(g.lib, 'has_blocks', False):
+        raise NotImplementedError(f'backend {getattr(g.lib, "backend", None)} does not export include/stk_blocks.h: no '
+                                  f'input gradient for the Gaussian Fourier features')
+      self.inputs = (x,)
 
   def forward(self, rt):
     rt.lib.fourier_embedding_f32(rt.v(self.x), rt.v(self.W), rt.v(self.y), self.x.shape[0], self.nf, rt.stream)
 
   def backward(self, rt):
-    pass
+    gx = rt.g(self.x)
+    if gx is not None:
+      rt.lib.fourier_embedding_bwd_f32(rt.v(self.W), rt.v(self.y), rt.g(self.y), gx, self.b(self.x), self.x.shape[0], self.nf,
+                                       rt.stream)
 
   def bwd_launches(self):
-    return False
+    return self.x.needs_grad
 
 
 class Affine(Op):

@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h and
-include/stk_fp16_train.h).
+"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
+include/stk_fp16_train.h and include/stk_blocks.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -126,6 +126,11 @@ SIGNATURES_FP16_TRAIN = {
   'stk_conv2d_wgrad_pl_wgs_f16x1': SIGNATURES['stk_conv2d_wgrad_pl_wgs_f32'],
   'stk_conv2d_wgrad_amax_f16x1': SIGNATURES['stk_conv2d_wgrad_amax_f32'],
 }
+# include/stk_blocks.h: gradients only the stand-alone building blocks need.  Bound like SIGNATURES_FP16, when present;
+# `StkLib.has_blocks` says whether they are (a graph that needs one on a library without them is refused when it is planned).
+SIGNATURES_BLOCKS = {
+  'stk_fourier_embedding_bwd_f32': [P, P, P, P, F, I, I, S],
+}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -159,6 +164,7 @@ class StkLib:
         setattr(self, name[4:], self._checked(name, fn))
     self.has_fp16 = self._bind_optional(SIGNATURES_FP16, 'include/stk_fp16.h')
     self.has_fp16_train = self._bind_optional(SIGNATURES_FP16_TRAIN, 'include/stk_fp16_train.h')
+    self.has_blocks = self._bind_optional(SIGNATURES_BLOCKS, 'include/stk_blocks.h')
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 

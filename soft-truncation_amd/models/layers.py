@@ -41,6 +41,42 @@ def act_code(config):
   return ACT_CODES[name]
 
 
+def act_code_of(act):
+  """The kernels' code for an activation MODULE (a block's ``self.act``): the four that ``get_act`` builds, with its
+  parameters.  Anything else raises NotImplementedError -- it is not emulated outside the kernels."""
+  if type(act) is nn.SiLU:
+    return ACT_CODES['swish']
+  if type(act) is nn.ReLU:
+    return ACT_CODES['relu']
+  if type(act) is nn.LeakyReLU and act.negative_slope == 0.2:
+    return ACT_CODES['lrelu']
+  if type(act) is nn.ELU and act.alpha == 1.0:
+    return ACT_CODES['elu']
+  raise NotImplementedError(f'activation {act!r} has no kernel: the blocks run SiLU, ReLU, LeakyReLU(0.2) and ELU '
+                            f'(layers.get_act)')
+
+
+class EagerBlock:
+  """Mixin of the building blocks that can be called on their own: ``forward`` hands its tensors to a
+  engine.executor.ModuleExecutor, which plans ``_emit_eager(g, **inputs)`` once per input signature and runs it on the
+  same HIP kernels, with the same planner choices, as the whole network.  There is no PyTorch / CPU path."""
+
+  def set_backend(self, backend):
+    """Test hook: run the block on another implementation of include/stk.h (NCSNpp.set_backend)."""
+    self.__dict__['_stk_backend'] = backend
+    self.__dict__.pop('_stk_engine', None)
+
+  def engine(self):
+    ex = self.__dict__.get('_stk_engine')
+    if ex is None:
+      from ..engine.executor import ModuleExecutor
+      ex = self.__dict__['_stk_engine'] = ModuleExecutor(self, self._emit_eager, backend=self.__dict__.get('_stk_backend'))
+    return ex
+
+  def _eager(self, **inputs):
+    return self.engine().apply(**inputs)
+
+
 # fan used as the denominator of the variance, per `mode` (models/layers.py:68-76)
 _FAN = {'fan_in': lambda fi, fo: fi, 'fan_out': lambda fi, fo: fo, 'fan_avg': lambda fi, fo: (fi + fo) / 2}
 
@@ -128,7 +164,7 @@ def conv_emit(g, conv, x1, x2=None, **kw):
   return g.conv(x1, x2, conv.weight, conv.bias, w_layout=0, stride=conv.stride[0], pad=conv.padding[0], **kw)
 
 
-class NIN(nn.Module):
+class NIN(EagerBlock, nn.Module):
   """1x1 'network in network' layer with an [in, out] weight (models/layers.py:546-555)."""
 
   def __init__(self, in_dim, num_units, init_scale=0.1):
@@ -138,3 +174,9 @@ class NIN(nn.Module):
 
   def emit(self, g, x1, x2=None, **kw):
     return g.conv(x1, x2, self.W, self.b, w_layout=1, stride=1, pad=0, **kw)
+
+  def _emit_eager(self, g, x):
+    return self.emit(g, x)
+
+  def forward(self, x):
+    return self._eager(x=x)

@@ -7,6 +7,9 @@ the bias / time-embedding / residual / (1/sqrt 2) epilogues, channel concatenati
 materialised (GroupNorm and the convs read two sources), and the 46 ``Dense_0`` projections are
 evaluated as one GEMM by the caller (``temb`` below is that shared [B, sum Cout] tensor plus this
 block's column offset).
+
+Called on their own (``forward``), the blocks plan the same ``emit`` as a graph of their own and run it on the same kernels
+(engine/executor.ModuleExecutor); a residual block's ``temb`` then goes through its own Dense_0.
 """
 import numpy as np
 import os
@@ -24,31 +27,49 @@ NIN = layers.NIN
 default_init = layers.default_init
 
 
-def _graph_only(name):
-  raise RuntimeError(f'{name} is evaluated as part of the planned score-network graph (NCSNpp.forward); '
-                     f'it has no eager PyTorch path')
+EagerBlock = layers.EagerBlock
 
 
-class FixedFouriereProjection(nn.Module):
+def _emit_res_eager(blk, g, x, temb=None):
+  """A residual block on its own: ``temb`` [B, temb_dim] goes through act -> Dense_0 into Conv_0's epilogue (column 0 of
+  its own [B, out_ch] projection) instead of the model's stacked projection of all blocks."""
+  g.act_code = layers.act_code_of(blk.act)
+  proj = None
+  if temb is not None:
+    proj = g.linear(g.silu(temb, name='temb.act'), blk.Dense_0.weight, blk.Dense_0.bias, name='temb.dense')
+  return blk.emit(g, x, None, proj, 0)
+
+
+class FixedFouriereProjection(EagerBlock, nn.Module):
   """Fixed Fourier input features (models/layerspp.py:31-43); ``model.fourier_feature`` is False
   in every shipped config."""
 
+  def _emit_eager(self, g, x):
+    from ..engine import graph as G
+    return g.add(G.FixedFourier(g, x))
+
   def forward(self, x):
-    _graph_only('FixedFouriereProjection')
+    return self._eager(x=x)
 
 
-class GaussianFourierProjection(nn.Module):
+class GaussianFourierProjection(EagerBlock, nn.Module):
   """Gaussian Fourier embedding of the noise level; frozen ``W`` (models/layerspp.py:45-54)."""
 
   def __init__(self, embedding_size=256, scale=1.0):
     super().__init__()
     self.W = nn.Parameter(torch.randn(embedding_size) * scale, requires_grad=False)
 
+  def _emit_eager(self, g, x):
+    from ..engine import graph as G
+    if self.W.requires_grad:
+      raise NotImplementedError('GaussianFourierProjection: the kernels treat W as frozen (requires_grad=False)')
+    return g.add(G.FourierEmbedding(g, x, g.param(self.W)))
+
   def forward(self, x):
-    _graph_only('GaussianFourierProjection')
+    return self._eager(x=x)
 
 
-class Combine(nn.Module):
+class Combine(EagerBlock, nn.Module):
   """Combine a skip branch: conv1x1(x) then cat / sum with y (models/layerspp.py:57-72)."""
 
   def __init__(self, dim1, dim2, method='cat'):
@@ -64,11 +85,14 @@ class Combine(nn.Module):
       return g.add(G.Concat(g, layers.conv_emit(g, self.Conv_0, x, name=name + '.conv'), y, name=name))
     raise ValueError(f'Method {self.method} not recognized.')
 
+  def _emit_eager(self, g, x, y):
+    return self.emit(g, x, y)
+
   def forward(self, x, y):
-    _graph_only('Combine')
+    return self._eager(x=x, y=y)
 
 
-class AttnBlockpp(nn.Module):
+class AttnBlockpp(EagerBlock, nn.Module):
   """Single-head self-attention over the H*W positions (models/layerspp.py:75-104)."""
 
   def __init__(self, channels, skip_rescale=False, init_scale=0.):
@@ -110,11 +134,14 @@ class AttnBlockpp(nn.Module):
       o = g.add(AttentionCore(g, q, k, v, name=name))
     return self.NIN_3.emit(g, o, res=x, out_div=SQRT2 if self.skip_rescale else 1.0, name=name + '.out')
 
+  def _emit_eager(self, g, x):
+    return self.emit(g, x)
+
   def forward(self, x):
-    _graph_only('AttnBlockpp')
+    return self._eager(x=x)
 
 
-class Upsample(nn.Module):
+class Upsample(EagerBlock, nn.Module):
   """models/layerspp.py:107-139."""
 
   def __init__(self, in_ch=None, out_ch=None, with_conv=False, fir=False, fir_kernel=(1, 3, 3, 1)):
@@ -142,11 +169,14 @@ class Upsample(nn.Module):
       return uds.emit_upsample_2d(g, x, self.fir_kernel, factor=2, name=name)
     return self.Conv2d_0.emit(g, x, res=res, out_div=out_div, name=name)
 
+  def _emit_eager(self, g, x):
+    return self.emit(g, x)
+
   def forward(self, x):
-    _graph_only('Upsample')
+    return self._eager(x=x)
 
 
-class Downsample(nn.Module):
+class Downsample(EagerBlock, nn.Module):
   """models/layerspp.py:142-176."""
 
   def __init__(self, in_ch=None, out_ch=None, with_conv=False, fir=False, fir_kernel=(1, 3, 3, 1)):
@@ -177,11 +207,14 @@ class Downsample(nn.Module):
       return uds.emit_downsample_2d(g, x, self.fir_kernel, factor=2, name=name)
     return self.Conv2d_0.emit(g, x, res=res, out_div=out_div, name=name)
 
+  def _emit_eager(self, g, x):
+    return self.emit(g, x)
+
   def forward(self, x):
-    _graph_only('Downsample')
+    return self._eager(x=x)
 
 
-class ResnetBlockDDPMpp(nn.Module):
+class ResnetBlockDDPMpp(EagerBlock, nn.Module):
   """DDPM residual block (models/layerspp.py:179-222)."""
 
   def __init__(self, act, in_ch, out_ch=None, temb_dim=None, conv_shortcut=False, dropout=0.1,
@@ -223,11 +256,13 @@ class ResnetBlockDDPMpp(nn.Module):
     return layers.conv_emit(g, self.Conv_1, h, res=xs, out_div=SQRT2 if self.skip_rescale else 1.0,
                             name=name + '.conv1')
 
+  _emit_eager = _emit_res_eager
+
   def forward(self, x, temb=None):
-    _graph_only('ResnetBlockDDPMpp')
+    return self._eager(x=x, temb=temb)
 
 
-class ResnetBlockBigGANpp(nn.Module):
+class ResnetBlockBigGANpp(EagerBlock, nn.Module):
   """BigGAN residual block with optional FIR / naive up- or down-sampling
   (models/layerspp.py:225-287)."""
 
@@ -277,5 +312,7 @@ class ResnetBlockBigGANpp(nn.Module):
     return layers.conv_emit(g, self.Conv_1, h, res=xs, out_div=SQRT2 if self.skip_rescale else 1.0,
                             name=name + '.conv1')
 
+  _emit_eager = _emit_res_eager
+
   def forward(self, x, temb=None):
-    _graph_only('ResnetBlockBigGANpp')
+    return self._eager(x=x, temb=temb)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import layers
 from ..engine import graph as G
 from ..engine import lib as stk_lib
 from ..op import upfirdn2d
@@ -199,7 +200,7 @@ def emit_naive_downsample_2d(g, x, name='down'):
   return g.add(G.ResampleNaive(g, x, False, name))
 
 
-class Conv2d(nn.Module):
+class Conv2d(layers.EagerBlock, nn.Module):
   """Conv2d with fused FIR up/down-sampling (models/up_or_down_sampling.py:23-56)."""
 
   def __init__(self, in_ch, out_ch, kernel, up=False, down=False, resample_kernel=(1, 3, 3, 1),
@@ -229,3 +230,9 @@ class Conv2d(nn.Module):
       return g.conv(h, None, self.weight, bias, w_layout=0, stride=2, pad=0, res=res, out_div=out_div, name=name)
     return g.conv(x, None, self.weight, bias, w_layout=0, stride=1, pad=self.kernel // 2, res=res,
                   out_div=out_div, name=name)
+
+  def _emit_eager(self, g, x):
+    return self.emit(g, x)
+
+  def forward(self, x):
+    return self._eager(x=x)
