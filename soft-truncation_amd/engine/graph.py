@@ -900,8 +900,13 @@ class AttentionCore(Op):
   `qkv`, the channel slices [0,C), [C,2C), [2C,3C) of ONE [B,3C,H,W] tensor (the stacked projection of
   AttnBlockpp.emit), read and differentiated in place through a batch stride of 3 C T.
 
-  Shapes the library's fused kernels take (stk_attention_ok: every shipped config) run as one launch per direction pair
-  with no [B,T,T] matrix in memory; the rest as batched GEMMs around stk_softmax_*.  STK_ATTN_FUSED=0 forces the latter."""
+  Three forms, chosen when the op is planned:
+    * shapes the library's short fused kernels take (stk_attention_ok, T <= 256: every shipped config) run as one launch
+      per direction pair with no [B,T,T] matrix in memory;
+    * otherwise, where the library has include/stk_attention_long.h and stk_attention_long_ok holds, the streaming
+      kernels: lse / delta vectors and the fp16 planes of q, k, v, dO in the workspace, no [B,T,T] matrix either;
+    * the rest as batched GEMMs around stk_softmax_* with the score and probability matrices in the arena.
+  STK_ATTN_FUSED=0 forces the GEMM form everywhere."""
 
   def __init__(self, g, q, k, v, name='attn', qkv=None):
     self.qkv = qkv
@@ -918,9 +923,11 @@ class AttentionCore(Op):
     self.bs = (3 if qkv is not None else 1) * C * self.T       # floats between consecutive images of q / k / v
     self.scale = float(int(C) ** (-0.5))
     lib = g.lib
-    self.fused = bool(lib is not None and os.environ.get('STK_ATTN_FUSED', '1') != '0' and hasattr(lib, 'attention_ok') and
-                      int(lib.attention_ok(B, C, self.T)))
-    if self.fused:
+    allowed = lib is not None and os.environ.get('STK_ATTN_FUSED', '1') != '0'
+    self.fused = bool(allowed and hasattr(lib, 'attention_ok') and int(lib.attention_ok(B, C, self.T)))
+    self.long = bool(allowed and not self.fused and getattr(lib, 'has_attention_long', False) and
+                     int(lib.attention_long_ok(B, C, self.T)))
+    if self.fused or self.long:
       self.lse = g.new((B, self.T), needs_grad=False, name=name + '.lse')
       self.delta = g.new((B, self.T), needs_grad=False, name=name + '.delta')
       self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
@@ -951,6 +958,10 @@ class AttentionCore(Op):
       rt.timed('attention.fwd.x2', self.flops, lib.attention_fwd_f32, q, k, v, bs, rt.v(self.o),
                rt.v(self.lse), rt.v(self.rec), B, C, T, self.scale, rt.stream)
       return
+    if self.long:
+      rt.timed('attention_long.fwd.x2', self.flops, lib.attention_long_fwd_f32, q, k, v, bs, rt.v(self.o),
+               rt.v(self.lse), rt.v(self.rec), B, C, T, self.scale, rt.ws, rt.ws_bytes, rt.stream)
+      return
     # S[b][t][t'] = sum_c Q[b][c][t] K[b][c][t']
     lib.gemm_f32(q, 1, T, bs, k, T, 1, bs, rt.v(self.s), T, 1, T * T,
                  None, 0, T, T, C, B, 1.0, 0.0, rt.stream)
@@ -979,6 +990,13 @@ class AttentionCore(Op):
                gs, B, C, T, self.scale, rt.stream)
       return
     gs = bs if self.qkv is not None else C * T
+    if self.long:
+      # a gradient nobody asked for is passed as NULL: the kernels skip it
+      rt.timed('attention_long.bwd.x2', 2.0 * self.flops, lib.attention_long_bwd_f32, q, k, v, bs, rt.v(self.o), go,
+               rt.v(self.lse), rt.v(self.rec), rt.v(self.delta), gq, bq if gq is not None else 0.0,
+               gk, bk if gk is not None else 0.0, gv, bv if gv is not None else 0.0,
+               gs, B, C, T, self.scale, rt.ws, rt.ws_bytes, rt.stream)
+      return
     dp = rt.v(self.s)   # S is dead after the forward softmax: reuse it for dP, then dS
     # dP[b][t][t'] = sum_c dO[b][c][t] V[b][c][t']
     lib.gemm_f32(go, 1, T, C * T, v, T, 1, bs, dp, T, 1, T * T,
@@ -995,6 +1013,8 @@ class AttentionCore(Op):
                    None, 0, C, T, T, B, 1.0, bk, rt.stream)
 
   def ws_bytes(self, lib):
+    if self.long:
+      return int(lib.attention_long_ws_bytes(self.B, self.C, self.T))
     return 3 * 4 * self.B * self.C * self.T if (self.fused and self.qkv is None) else 0
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
-include/stk_fp16_train.h and include/stk_blocks.h).
+include/stk_fp16_train.h, include/stk_blocks.h and include/stk_attention_long.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -131,9 +131,20 @@ SIGNATURES_FP16_TRAIN = {
 SIGNATURES_BLOCKS = {
   'stk_fourier_embedding_bwd_f32': [P, P, P, P, F, I, I, S],
 }
+# include/stk_attention_long.h: the streaming attention core for maps above 16 x 16.  Bound like SIGNATURES_FP16, when
+# present; `StkLib.has_attention_long` says whether they are (AttentionCore plans the GEMM form without them).  _ok and
+# _ws_bytes are queries, not launches: they are bound unchecked, _ws_bytes returning a long.
+SIGNATURES_ATTN_LONG = {
+  'stk_attention_long_ok': [I, I, I],
+  'stk_attention_long_ws_bytes': [I, I, I],
+  'stk_attention_long_fwd_f32': [P, P, P, L, P, P, P, I, I, I, F, P, L, S],
+  'stk_attention_long_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, F, P, L, S],
+}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
+_RESTYPE_ATTN_LONG = {'stk_attention_long_ws_bytes': c_long}
+_NO_CHECK_ATTN_LONG = set(_RESTYPE_ATTN_LONG) | {'stk_attention_long_ok'}
 _NO_CHECK = set(_RESTYPE) | {'stk_version', 'stk_conv2d_variant', 'stk_conv2d_pl_ok', 'stk_gn_fwd_pl_fused', 'stk_conv2d_wgrad_pl_ok', 'stk_attention_ok', 'stk_gn_bwd_out_ok', 'stk_conv2d_pl_ksplit', 'stk_conv2d_pl_halo'}
 
 
@@ -165,19 +176,23 @@ class StkLib:
     self.has_fp16 = self._bind_optional(SIGNATURES_FP16, 'include/stk_fp16.h')
     self.has_fp16_train = self._bind_optional(SIGNATURES_FP16_TRAIN, 'include/stk_fp16_train.h')
     self.has_blocks = self._bind_optional(SIGNATURES_BLOCKS, 'include/stk_blocks.h')
+    self.has_attention_long = self._bind_optional(SIGNATURES_ATTN_LONG, 'include/stk_attention_long.h',
+                                                  restype=_RESTYPE_ATTN_LONG, unchecked=_NO_CHECK_ATTN_LONG)
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 
-  def _bind_optional(self, table, header):
-    """Bind the entries of an optional header: all of them or none (a partial table raises StkMissingError)."""
+  def _bind_optional(self, table, header, restype=None, unchecked=()):
+    """Bind the entries of an optional header: all of them or none (a partial table raises StkMissingError).
+    restype: name -> ctypes result type of the entries that do not return an int status; unchecked: names bound as raw
+    functions (queries whose result is not a status)."""
     present = [name for name in table if hasattr(self._cdll, name)]
     if present and len(present) != len(table):
       raise StkMissingError(f'{self.path} exports only part of {header}: {present}')
     for name in present:
       fn = getattr(self._cdll, name)
       fn.argtypes = table[name]
-      fn.restype = c_int
-      setattr(self, name[4:], self._checked(name, fn))
+      fn.restype = (restype or {}).get(name, c_int)
+      setattr(self, name[4:], fn if name in unchecked else self._checked(name, fn))
     return bool(present)
 
   def _checked(self, name, fn):
