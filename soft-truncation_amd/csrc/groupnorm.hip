@@ -8,9 +8,16 @@
 //  * The input may be the channel-concat of two tensors (the skip connections of the up path,
 //    models/ncsnpp.py:368); the concat is never materialised: a group is at most two contiguous
 //    segments, one in each source.
-//  * Statistics use shifted sums (shift = first element of the group) so that a single pass gives
-//    mean and variance without the cancellation of E[x^2]-E[x]^2; wave64 shuffles reduce inside a
-//    wave, LDS across the 4 waves.
+//  * Statistics are the corrected two-pass form: mean0 = sum(x) / L, then c0 = sum(x - mean0) and
+//    c1 = sum((x - mean0)^2) give mean = mean0 + c0 / L and var = c1 / L - (c0 / L)^2.  Every term of c1 is a square of
+//    a deviation from (almost) the mean, so nothing cancels whatever the data: a large offset (mean >> std), one
+//    outlier anywhere in the group -- the first element included, which a one-pass sum shifted by that element does
+//    not survive: rstd was off by 1e-4 .. 2e-2 there -- constant groups (c0 restores the mean to its last bit, var = 0
+//    exactly), groups of any scale.  The register-resident kernels make both passes over registers, each wave about
+//    its own mean and the waves merged like the chunks below (gn_stats_regs: one barrier, no memory traffic), the looping kernel reads the group once more (out of L2), and the split path keeps
+//    a (mean, M2) pair per 4096-float chunk, computed the same way, and merges the chunks by
+//    M2 = sum M2_k + 4096 sum (mean_k - mean)^2 -- again non-negative terms only.  tests/_gn_cases.py holds every one
+//    of these sites to 2e-5 per (sample, group) against float64.  Wave64 shuffles reduce inside a wave, LDS across waves.
 //  * The normalisation pass re-reads the group right after the statistics pass; a group is
 //    16 KB - 1 MB, so the second read is served by the XCD's 4 MB L2 / the 256 MB Infinity Cache
 //    rather than HBM (algorithmic traffic: one read + one write of the tensor).
@@ -127,6 +134,79 @@ __device__ __forceinline__ float act_slope_f(int act, float u) {
   return 1.f;
 }
 
+// block_sum (common.h) without its closing barrier: `red` must not be written again before the kernel's next barrier.  The two
+// reductions of the two-pass statistic use two LDS arrays, so a kernel has the two barriers the one-pass form had.
+template <int NV>
+__device__ __forceinline__ void block_sum_once(float (&v)[NV], float* red) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[i * nw + wid] = v[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    float s = 0.f;
+    for (int w = 0; w < nw; ++w) s += red[i * nw + w];
+    v[i] = s;
+  }
+}
+
+// mean / rstd from the centred sums c0 = sum(x - mean0), c1 = sum((x - mean0)^2) of the corrected two-pass statistic
+__device__ __forceinline__ void gn_finish(float mean0, float c0, float c1, float inv_l, float eps, float& mean, float& rstd) {
+  const float dm = c0 * inv_l;                         // mean - mean0: what rounding left in mean0
+  mean = mean0 + dm;
+  rstd = 1.f / sqrtf(fmaxf(c1 * inv_l - dm * dm, 0.f) + eps);
+}
+
+// The statistic of NITEMS float4 per thread held in registers (item k of a thread is valid when threadIdx.x + k * blockDim.x <
+// L4; invalid items are zero), with ONE barrier: every wave centres its second pass on its own mean -- shuffles only -- and the
+// waves' (count, mean, M2) are merged by the pairwise formula, M2 = sum M2_w + n_w (mean_w - mean)^2, the mean of the wave
+// means corrected like any other.  Returns the mean and M2 = sum (x - mean)^2 of the L = 4 L4 elements.  red: 3 * waves floats.
+template <int NITEMS>
+__device__ __forceinline__ void gn_stats_regs(const float4 (&v)[NITEMS], int L4, float inv_l, float* red, float& mean, float& m2) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  float t = 0.f;
+  int cnt = 0;                                           // valid items of this wave: lanes are consecutive items, no shuffle needed
+#pragma unroll
+  for (int k = 0; k < NITEMS; ++k) {
+    t += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+    cnt += min(max(L4 - (int)(wid * 64 + k * blockDim.x), 0), 64);
+  }
+  t = wave_sum(t);
+  const float fc = 4.f * (float)cnt;
+  const float rc = fc > 0.f ? 1.f / fc : 0.f;
+  const float m0 = t * rc;
+  float c0 = 0.f, c1 = 0.f;
+#pragma unroll
+  for (int k = 0; k < NITEMS; ++k) {
+    if ((int)(threadIdx.x + k * blockDim.x) >= L4) continue;
+    const float d0 = v[k].x - m0, d1 = v[k].y - m0, d2 = v[k].z - m0, d3 = v[k].w - m0;
+    c0 += (d0 + d1) + (d2 + d3);
+    c1 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  }
+  c0 = wave_sum(c0); c1 = wave_sum(c1);
+  if (lane == 0) {
+    const float dm = c0 * rc;
+    red[wid] = fc; red[nw + wid] = m0 + dm; red[2 * nw + wid] = fmaxf(c1 - c0 * dm, 0.f);
+  }
+  __syncthreads();
+  float sm = 0.f;
+  for (int w = 0; w < nw; ++w) sm += red[w] * red[nw + w];
+  const float mean0 = sm * inv_l;
+  float e0 = 0.f, e1 = 0.f;
+  for (int w = 0; w < nw; ++w) {
+    const float d = red[nw + w] - mean0, nd = red[w] * d;
+    e0 += nd;
+    e1 += __fmaf_rn(nd, d, red[2 * nw + w]);
+  }
+  const float dm = e0 * inv_l;
+  mean = mean0 + dm;
+  m2 = fmaxf(e1 - e0 * dm, 0.f);
+}
+
 // ---- forward ------------------------------------------------------------------------------------
 // Register-resident forward for groups of up to 16384 elements (every group of the 32x32 / 64x64 networks): a thread
 // keeps its <= 4 float4 of the group, so the group is read ONCE (the looping kernel below reads it for the statistics
@@ -134,32 +214,25 @@ __device__ __forceinline__ float act_slope_f(int act, float u) {
 template <int IPT>
 __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __restrict__ y, float* __restrict__ mean_out,
                                                            float* __restrict__ rstd_out, float eps) {
-  __shared__ float red[32];
+  __shared__ float red[48];
   const int ng = blockIdx.x;
   const int n = ng / a.G, g = ng - n * a.G;
   Seg seg[2];
   group_segments(a, n, g, seg);
   const int L = a.cpg * a.HW, L4 = L >> 2, n0 = seg[0].len >> 2;
-  const float shift = seg[0].len ? seg[0].p[0] : seg[1].p[0];
   const float4* p0 = reinterpret_cast<const float4*>(seg[0].p);
   const float4* p1 = reinterpret_cast<const float4*>(seg[1].p);
   float4 v[IPT];
-  float s[2] = {0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < IPT; ++k) {
     const int idx = threadIdx.x + k * blockDim.x;
-    v[k] = make_float4(shift, shift, shift, shift);
+    v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (idx < L4) v[k] = idx < n0 ? p0[idx] : p1[idx - n0];
-    const float d0 = v[k].x - shift, d1 = v[k].y - shift, d2 = v[k].z - shift, d3 = v[k].w - shift;
-    s[0] += (d0 + d1) + (d2 + d3);
-    s[1] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
   }
-  block_sum<2>(s, red);
   const float inv_l = 1.f / (float)L;
-  const float md = s[0] * inv_l;                       // mean - shift
-  const float var = fmaxf(s[1] * inv_l - md * md, 0.f);
-  const float mean = shift + md;
-  const float rstd = 1.f / sqrtf(var + eps);
+  float mean, m2;
+  gn_stats_regs<IPT>(v, L4, inv_l, red, mean, m2);
+  const float rstd = 1.f / sqrtf(m2 * inv_l + eps);
   if (threadIdx.x == 0) {
     mean_out[ng] = mean;
     rstd_out[ng] = rstd;
@@ -193,14 +266,31 @@ __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __re
 template <int VEC>
 __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict__ y, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, float eps) {
-  __shared__ float red[16];
+  __shared__ float red0[4], red[16];
   const int ng = blockIdx.x;
   const int n = ng / a.G, g = ng - n * a.G;
   Seg seg[2];
   group_segments(a, n, g, seg);
   const int L = a.cpg * a.HW;
-  const float shift = seg[0].len ? seg[0].p[0] : seg[1].p[0];
 
+  float t[1] = {0.f};
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const float* p = seg[q].p;
+    const int len = seg[q].len;
+    if (VEC == 4) {
+      const float4* p4 = reinterpret_cast<const float4*>(p);
+      for (int i = threadIdx.x; i < (len >> 2); i += 256) {
+        const float4 v = p4[i];
+        t[0] += (v.x + v.y) + (v.z + v.w);
+      }
+    } else {
+      for (int i = threadIdx.x; i < len; i += 256) t[0] += p[i];
+    }
+  }
+  block_sum_once<1>(t, red0);
+  const float inv_l = 1.f / (float)L;
+  const float mean0 = t[0] * inv_l;
   float s[2] = {0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -210,24 +300,21 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict
       const float4* p4 = reinterpret_cast<const float4*>(p);
       for (int i = threadIdx.x; i < (len >> 2); i += 256) {
         const float4 v = p4[i];
-        const float d0 = v.x - shift, d1 = v.y - shift, d2 = v.z - shift, d3 = v.w - shift;
+        const float d0 = v.x - mean0, d1 = v.y - mean0, d2 = v.z - mean0, d3 = v.w - mean0;
         s[0] += (d0 + d1) + (d2 + d3);
         s[1] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
       }
     } else {
       for (int i = threadIdx.x; i < len; i += 256) {
-        const float d = p[i] - shift;
+        const float d = p[i] - mean0;
         s[0] += d;
         s[1] += d * d;
       }
     }
   }
-  block_sum<2>(s, red);
-  const float inv_l = 1.f / (float)L;
-  const float md = s[0] * inv_l;                       // mean - shift
-  const float var = fmaxf(s[1] * inv_l - md * md, 0.f);
-  const float mean = shift + md;
-  const float rstd = 1.f / sqrtf(var + eps);
+  block_sum_once<2>(s, red);
+  float mean, rstd;
+  gn_finish(mean0, s[0], s[1], inv_l, eps, mean, rstd);
   if (threadIdx.x == 0) {
     mean_out[ng] = mean;
     rstd_out[ng] = rstd;
@@ -495,52 +582,63 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
 // ---- large groups: one (sample, group) split over many workgroups -------------------------------------------
 // A 256x256 map at batch 4 has only N*G = 128 groups of 1 MB each: one workgroup per group leaves half the chip
 // idle and streams each group serially (measured 689 us for a 134 MB backward).  Here a workgroup owns one CHUNK
-// (GN_CHUNK consecutive elements of one channel); a first kernel writes per-chunk partial sums, the second one
-// folds the partials of its group in a fixed order and streams its chunk.  Partials: part[((n*C + c)*Sc + k)*2 + {0,1}].
+// (GN_CHUNK consecutive elements of one channel); a first kernel writes per-chunk partials, the second one
+// folds the partials of its group in a fixed order and streams its chunk.  Partials: part[((n*C + c)*Sc + k)*2 + {0,1}]
+// (forward: the chunk's mean and M2 = sum (x - mean)^2; backward: two plain sums).
 constexpr int GN_CHUNK = 4096;       // floats: 4 float4 per thread
 
 __device__ __forceinline__ const float* gn_chan(const GnArgs& a, int n, int c) {
   return c < a.C1 ? a.x1 + ((long)n * a.C1 + c) * a.HW : a.x2 + ((long)n * a.C2 + (c - a.C1)) * a.HW;
 }
 
-// forward statistics: shifted sums (shift = first element of the group) of one chunk
+// forward statistics of one chunk, held in registers: its mean and M2 by the corrected two-pass form (header)
 __global__ __launch_bounds__(256) void gn_split_stats_kernel(GnArgs a, float* __restrict__ part, int Sc) {
-  __shared__ float red[16];
+  __shared__ float red[12];
   const int k = blockIdx.x % Sc, nc = blockIdx.x / Sc;
-  const int C = a.C1 + a.C2, n = nc / C, c = nc - n * C, g = c / a.cpg;
-  const float shift = gn_chan(a, n, g * a.cpg)[0];
+  const int C = a.C1 + a.C2, n = nc / C, c = nc - n * C;
   const float4* p4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + (long)k * GN_CHUNK);
-  float s[2] = {0.f, 0.f};
+  float4 v[GN_CHUNK / 1024];
 #pragma unroll
-  for (int i = 0; i < GN_CHUNK / 1024; ++i) {
-    const float4 v = p4[threadIdx.x + 256 * i];
-    const float d0 = v.x - shift, d1 = v.y - shift, d2 = v.z - shift, d3 = v.w - shift;
-    s[0] += (d0 + d1) + (d2 + d3);
-    s[1] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  for (int i = 0; i < GN_CHUNK / 1024; ++i) v[i] = p4[threadIdx.x + 256 * i];
+  float mean, m2;
+  gn_stats_regs<GN_CHUNK / 1024>(v, GN_CHUNK / 4, 1.f / (float)GN_CHUNK, red, mean, m2);
+  if (threadIdx.x == 0) { part[(long)blockIdx.x * 2] = mean; part[(long)blockIdx.x * 2 + 1] = m2; }
+}
+
+// mean / rstd of a group from the (mean, M2) of its K equal chunks, in a fixed order: mean = mean of the chunk means (corrected
+// the same way), M2 = sum M2_k + GN_CHUNK sum (mean_k - mean)^2
+__device__ __forceinline__ void gn_fold_chunks(const float* __restrict__ part, long pbase, int K, float eps, float* red0, float* red,
+                                               float& mean, float& rstd) {
+  float t[1] = {0.f};
+  for (int i = threadIdx.x; i < K; i += 256) t[0] += part[(pbase + i) * 2];
+  block_sum_once<1>(t, red0);
+  const float inv_k = 1.f / (float)K;
+  const float mean0 = t[0] * inv_k;
+  float s[2] = {0.f, 0.f};
+  for (int i = threadIdx.x; i < K; i += 256) {
+    const float d = part[(pbase + i) * 2] - mean0;
+    s[0] += d;
+    s[1] += __fmaf_rn((float)GN_CHUNK * d, d, part[(pbase + i) * 2 + 1]);
   }
-  block_sum<2>(s, red);
-  if (threadIdx.x == 0) { part[(long)blockIdx.x * 2] = s[0]; part[(long)blockIdx.x * 2 + 1] = s[1]; }
+  block_sum_once<2>(s, red);
+  const float dm = s[0] * inv_k;
+  mean = mean0 + dm;
+  const float var = fmaxf(s[1] * inv_k * (1.f / (float)GN_CHUNK) - dm * dm, 0.f);
+  rstd = 1.f / sqrtf(var + eps);
 }
 
 __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float* __restrict__ part, int Sc,
                                                            float* __restrict__ y, float* __restrict__ mean_out,
                                                            float* __restrict__ rstd_out, float eps) {
-  __shared__ float red[16];
+  __shared__ float red0[4], red[16];
   // chunks in the REVERSE of the order the statistics kernel read them in: what that pass read last is still in the
   // Infinity Cache (256 MB) -- in the same order a tensor of about that size evicts each piece just before its reuse
   const int bid = gridDim.x - 1 - blockIdx.x;
   const int k = bid % Sc, nc = bid / Sc;
   const int C = a.C1 + a.C2, n = nc / C, c = nc - n * C, g = c / a.cpg;
-  const float shift = gn_chan(a, n, g * a.cpg)[0];
   // fold the cpg * Sc partials of the group (fixed order inside block_sum)
-  float s[2] = {0.f, 0.f};
-  const long pbase = ((long)n * C + g * a.cpg) * Sc;
-  for (int i = threadIdx.x; i < a.cpg * Sc; i += 256) { s[0] += part[(pbase + i) * 2]; s[1] += part[(pbase + i) * 2 + 1]; }
-  block_sum<2>(s, red);
-  const float inv_l = 1.f / ((float)a.cpg * (float)a.HW);
-  const float md = s[0] * inv_l;
-  const float var = fmaxf(s[1] * inv_l - md * md, 0.f);
-  const float mean = shift + md, rstd = 1.f / sqrtf(var + eps);
+  float mean, rstd;
+  gn_fold_chunks(part, ((long)n * C + g * a.cpg) * Sc, a.cpg * Sc, eps, red0, red, mean, rstd);
   if (threadIdx.x == 0 && k == 0 && c == g * a.cpg) { mean_out[n * a.G + g] = mean; rstd_out[n * a.G + g] = rstd; }
   unsigned long long seed = a.seed;
   if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
@@ -747,8 +845,6 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
   const int q = tid & 3;                  // 8-channel piece (constant per thread: T % 4 == 0)
   const int gb = 32 / a.cpg;              // groups in this block
   const int g_lo = (8 * q) / a.cpg, g_hi = (8 * q + 4) / a.cpg;
-  // shifted sums (shift = first element of the group), as in gn_fwd_flat_kernel
-  const float sh_lo = src[(long)(g_lo * a.cpg) * a.HW], sh_hi = src[(long)(g_hi * a.cpg) * a.HW];
 
   // scale of the planes: |y| <= (max|gamma| sqrt(L - 1) + max|beta|) / (1 - p)
   float gm = 0.f, bm = 0.f;
@@ -764,20 +860,13 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[k][j] = src[(long)(8 * q + j) * a.HW + px];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d0 = v[k][j] - sh_lo, d1 = v[k][4 + j] - sh_hi;
-      s[0] += d0; s[1] += d0 * d0; s[2] += d1; s[3] += d1 * d1;
-    }
+    for (int j = 0; j < 4; ++j) { s[0] += v[k][j]; s[2] += v[k][4 + j]; }
   }
+  // first pass of the corrected two-pass statistic (header), over registers: plain sums of the lo / hi halves.
   // lanes with equal q (lane bits 0..1) -> xor-shuffle over lane bits 2..5
 #pragma unroll
-  for (int o = 4; o < 64; o <<= 1)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] += __shfl_xor(s[i], o, 64);
-  if (lane < 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[(wave * 4 + lane) * 4 + i] = s[i];
-  }
+  for (int o = 4; o < 64; o <<= 1) { s[0] += __shfl_xor(s[0], o, 64); s[2] += __shfl_xor(s[2], o, 64); }
+  if (lane < 4) { red[(wave * 4 + lane) * 4] = s[0]; red[(wave * 4 + lane) * 4 + 2] = s[2]; }
   if (xmax1) {
     // by-product for the block's 1x1 shortcut convolution, which reads the same source tensors as fp32 operands of the
     // split kernels: max |x| of this block, by atomic maximum into the 256-slot scale record of its source (zeroed by the
@@ -797,18 +886,46 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
     float* rec = c0 < a.C1 ? xmax1 : xmax2;
     if (rec) atomicMax(reinterpret_cast<unsigned*>(rec) + (blockIdx.x & 255), __float_as_uint(m));
   }
+  const float inv_l = 1.f / ((float)a.cpg * (float)a.HW);
   if (tid < gb) {
     // pieces of group `tid`, in a fixed order: (q', half) with (8 q' + 4 half) / cpg == tid, over all waves
+    float s0 = 0.f;
+    for (int qq = 0; qq < 4; ++qq)
+      for (int h = 0; h < 2; ++h)
+        if ((8 * qq + 4 * h) / a.cpg == tid)
+          for (int w = 0; w < nw; ++w) s0 += red[(w * 4 + qq) * 4 + 2 * h];
+    gst[2 * tid] = s0 * inv_l;                           // mean0
+  }
+  __syncthreads();
+  {
+    // second pass: centred sums about mean0 of the lo / hi groups
+    const float m0_lo = gst[2 * g_lo], m0_hi = gst[2 * g_hi];
+    s[0] = s[1] = s[2] = s[3] = 0.f;
+#pragma unroll
+    for (int k = 0; k < PASSES; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d0 = v[k][j] - m0_lo, d1 = v[k][4 + j] - m0_hi;
+        s[0] += d0; s[1] += d0 * d0; s[2] += d1; s[3] += d1 * d1;
+      }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[i] += __shfl_xor(s[i], o, 64);
+    if (lane < 4) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[(wave * 4 + lane) * 4 + i] = s[i];
+    }
+  }
+  __syncthreads();
+  if (tid < gb) {
     float s0 = 0.f, s1 = 0.f;
     for (int qq = 0; qq < 4; ++qq)
       for (int h = 0; h < 2; ++h)
         if ((8 * qq + 4 * h) / a.cpg == tid)
           for (int w = 0; w < nw; ++w) { s0 += red[(w * 4 + qq) * 4 + 2 * h]; s1 += red[(w * 4 + qq) * 4 + 2 * h + 1]; }
-    const float inv_l = 1.f / ((float)a.cpg * (float)a.HW);
-    const float shift = src[(long)(tid * a.cpg) * a.HW];
-    const float md = s0 * inv_l;
-    const float var = fmaxf(s1 * inv_l - md * md, 0.f);
-    const float mean = shift + md, rstd = 1.f / sqrtf(var + eps);
+    float mean, rstd;
+    gn_finish(gst[2 * tid], s0, s1, inv_l, eps, mean, rstd);
     gst[2 * tid] = mean; gst[2 * tid + 1] = rstd;
     const int g = (c0 / a.cpg) + tid;
     mean_out[n * a.G + g] = mean;
@@ -892,31 +1009,30 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
 // pl::split_planes_kernel -- a workgroup per (sample, 32-channel block, 128-pixel tile), all element-wise work done on
 // the float4 (four consecutive pixels of one channel = one dropout RNG quad) before the tile goes through LDS for the
 // transposition to [pixel][32 channels].  x is read twice, the second time out of the Infinity Cache.
+template <int IPT>
 __global__ __launch_bounds__(256) void gn_stats_kernel(GnArgs a, float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                        float eps, float sqrt_lm1, float* __restrict__ rec) {
-  __shared__ float red[16];
+  __shared__ float red[12], redb[8];
   const int ng = blockIdx.x;
   const int n = ng / a.G, g = ng - n * a.G;
   Seg seg[2];
   group_segments(a, n, g, seg);                          // whole groups per source (C1 % cpg == 0): one segment is empty
   const float* p = seg[0].len ? seg[0].p : seg[1].p;
-  const int L = a.cpg * a.HW, L4 = L >> 2;
-  const float shift = p[0];
+  const int L = a.cpg * a.HW, L4 = L >> 2;                // L <= 16384: the group stays in registers between the two passes
   const float4* p4 = reinterpret_cast<const float4*>(p);
-  float s[2] = {0.f, 0.f};
-  for (int i = threadIdx.x; i < L4; i += 256) {
-    const float4 v = p4[i];
-    const float d0 = v.x - shift, d1 = v.y - shift, d2 = v.z - shift, d3 = v.w - shift;
-    s[0] += (d0 + d1) + (d2 + d3);
-    s[1] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  float4 v[IPT];
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < L4) v[k] = p4[i];
   }
-  block_sum<2>(s, red);
   const float inv_l = 1.f / (float)L;
-  const float md = s[0] * inv_l;
-  const float var = fmaxf(s[1] * inv_l - md * md, 0.f);
-  const float rstd_v = 1.f / sqrtf(var + eps);
+  float mean_v, m2;
+  gn_stats_regs<IPT>(v, L4, inv_l, red, mean_v, m2);
+  const float rstd_v = 1.f / sqrtf(m2 * inv_l + eps);
   if (threadIdx.x == 0) {
-    mean_out[ng] = shift + md;
+    mean_out[ng] = mean_v;
     rstd_out[ng] = rstd_v;
   }
   if (rec && ng == 0) {                                  // the planes' scale record: a-priori bound of |y| (gn_bound_kernel)
@@ -924,10 +1040,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GnArgs a, float* __restri
     float gm = 0.f, bm = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) { gm = fmaxf(gm, fabsf(a.gamma[c])); bm = fmaxf(bm, fabsf(a.beta[c])); }
     gm = wave_max(gm); bm = wave_max(bm);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = gm; red[4 + (threadIdx.x >> 6)] = bm; }
+    if ((threadIdx.x & 63) == 0) { redb[threadIdx.x >> 6] = gm; redb[4 + (threadIdx.x >> 6)] = bm; }
     __syncthreads();
-    gm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    bm = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    gm = fmaxf(fmaxf(redb[0], redb[1]), fmaxf(redb[2], redb[3]));
+    bm = fmaxf(fmaxf(redb[4], redb[5]), fmaxf(redb[6], redb[7]));
     rec[threadIdx.x] = threadIdx.x == 0 ? __fmaf_rn(gm, sqrt_lm1, bm) * a.keep_scale : 0.f;
   }
 }
@@ -936,19 +1052,13 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GnArgs a, float* __restri
 __global__ __launch_bounds__(256) void gn_fold_stats_kernel(GnArgs a, const float* __restrict__ part, int Sc,
                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                             float eps) {
-  __shared__ float red[16];
+  __shared__ float red0[4], red[16];
   const int ng = blockIdx.x;
   const int n = ng / a.G, g = ng - n * a.G;
   const int C = a.C1 + a.C2;
-  const float shift = gn_chan(a, n, g * a.cpg)[0];
-  float s[2] = {0.f, 0.f};
-  const long pbase = ((long)n * C + g * a.cpg) * Sc;
-  for (int i = threadIdx.x; i < a.cpg * Sc; i += 256) { s[0] += part[(pbase + i) * 2]; s[1] += part[(pbase + i) * 2 + 1]; }
-  block_sum<2>(s, red);
-  const float inv_l = 1.f / ((float)a.cpg * (float)a.HW);
-  const float md = s[0] * inv_l;
-  const float var = fmaxf(s[1] * inv_l - md * md, 0.f);
-  if (threadIdx.x == 0) { mean_out[ng] = shift + md; rstd_out[ng] = 1.f / sqrtf(var + eps); }
+  float mean, rstd;
+  gn_fold_chunks(part, ((long)n * C + g * a.cpg) * Sc, a.cpg * Sc, eps, red0, red, mean, rstd);
+  if (threadIdx.x == 0) { mean_out[ng] = mean; rstd_out[ng] = rstd; }
 }
 
 constexpr int AP_PIX = 128;
@@ -1150,7 +1260,11 @@ static int gn_fwd_pl_impl(const float* x1, int C1, const float* x2, int C2, cons
     const float sq = gn_bound_sqrt((long)a.cpg * HW);
     hipStream_t s = (hipStream_t)stream;
     if ((long)a.cpg * HW <= 16384) {
-      hipLaunchKernelGGL(gn_stats_kernel, dim3(N * G), dim3(256), 0, s, a, mean, rstd, eps, sq, rec);
+      const int ipt = stk_cdiv((int)(((long)a.cpg * HW) >> 2), 256);
+#define STK_GN_STATS(IPT) hipLaunchKernelGGL((gn_stats_kernel<IPT>), dim3(N * G), dim3(256), 0, s, a, mean, rstd, eps, sq, rec)
+      if (ipt <= 1) STK_GN_STATS(1); else if (ipt <= 2) STK_GN_STATS(2); else if (ipt <= 4) STK_GN_STATS(4);
+      else if (ipt <= 8) STK_GN_STATS(8); else STK_GN_STATS(16);
+#undef STK_GN_STATS
     } else {
       if (!ws) return STK_EINVAL;
       const int Sc = HW / GN_CHUNK;
