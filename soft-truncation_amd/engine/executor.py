@@ -277,7 +277,7 @@ class Program:
 
   def build_gn_folds(self, gparam_base):
     g = self.graph
-    if not getattr(g, 'gn_folds', None):
+    if not g.gn_folds:
       return
     self.gnpart = _arena(g.gnpart_size, self.device)
     base = self.gnpart.data_ptr()
@@ -618,7 +618,7 @@ class Executor:
     if c.pl is not None:
       rt.pl = c.pl.data_ptr()
       rt.dypl = rt.pl + prog.graph.pl_bytes
-      if with_backward and self.use_side and self.lib.is_device and getattr(prog.graph, 'own_dypl', False):
+      if with_backward and self.use_side and self.lib.is_device and prog.graph.own_dypl:
         if self._side is None or self._side.device != flat.device:
           self._side = SideStream(flat.device)
         if prog.ws2 is None:
@@ -697,7 +697,7 @@ class Executor:
     for key, value in inputs.items():
       self._copy_in(c, key, value)
     self._prepare_weights(prog, with_backward)
-    if with_backward and prog.gn_table is None and getattr(g, 'gn_folds', None):
+    if with_backward and prog.gn_table is None and g.gn_folds:
       prog.build_gn_folds(flat.grad.data_ptr())          # allocation + upload: never inside a hipGraph capture
     seed = 0
     if training and self._uses_dropout():

@@ -178,10 +178,14 @@ class Op:
   """Base class.  Subclasses list `inputs` (Tensors whose gradients they may write)."""
   inputs = ()
 
-  def plan_backward(self):
+  def grad_inputs(self):
+    """The inputs whose gradients this op's backward writes (Graph._grad_writers, plan_backward)."""
+    return self.inputs
+
+  def plan_backward(self, lib):
     """Called in backward order: fix beta (0 = overwrite, 1 = accumulate) per gradient target."""
     self.beta = {}
-    for t in self.inputs:
+    for t in self.grad_inputs():
       if t is None or not t.needs_grad or t.space != 'act':
         continue
       if id(t) in self.beta:
@@ -275,20 +279,8 @@ class GroupNormAct(Op):
       rt.defer_fold(self.fold_index)
     adder = self.add_from
     if cons is not None or adder is not None:
-      dsum = dtemb = damax = add = None
-      out_scale = add_scale = 1.0
-      tstride = 0
-      if cons is not None:
-        assert rt.gn_table, 'the by-products of the GroupNorm backward ride on the batched folds'
-        out_scale = 1.0 / cons.out_div
-        if cons.bsum_index is not None and rt.param_grads:
-          dsum = rt.gnpart + 4 * cons.bsum_off
-          rt.defer_fold(cons.bsum_index)
-        if cons.temb is not None and cons.temb.needs_grad:
-          dtemb, tstride = rt.g(cons.temb) + 4 * cons.temb_col, cons.temb_stride
-        damax = rt.v(cons.dy_peer.amax if cons.dy_peer is not None else cons.amax) + 4 * 512
-      if adder is not None:
-        add, add_scale = rt.g(adder.y), 1.0 / adder.out_div
+      out_scale, dsum, dtemb, tstride, damax = cons.dy_targets(rt) if cons is not None else (1.0, None, None, 0, None)
+      add, add_scale = (rt.g(adder.y), 1.0 / adder.out_div) if adder is not None else (None, 1.0)
       rt.lib.gn_bwd_out_f32(rt.g(self.y), rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, rt.v(self.gamma), rt.v(self.beta_t),
                             rt.v(self.mean), rt.v(self.rstd), rt.g(self.x1), self.b(self.x1), rt.g(self.x2),
                             self.b(self.x2) if self.x2 is not None else 0.0, dgamma, dbeta, ws, self.N, self.HW, self.G,
@@ -334,7 +326,38 @@ class Conv(Op):
     self.inputs = (x1, x2, res)
     # algorithmic FLOPs of one launch (1 MAC = 2 FLOP); identical for fwd, dgrad and wgrad
     self.flops = 2.0 * N * OH * OW * Cout * (C1 + C2) * KH * KW
+    # prepared weights (include/stk.h "Prepared weights"): byte offsets of this layer's forward / data-gradient blocks in the
+    # program's arena (plan_wp); None = this direction of this shape prepares nothing
+    self.wp_off = (None, None)
+    # planes (include/stk.h "Planes"), decided by plan_planes
+    self.pl_fwd = False       # the forward call reads x1 as planes
+    self.pl_dgrad = False     # the data-gradient call reads dy as planes (made here, into the context's scratch)
+    self.pl_wgrad = False     # the weight-gradient call reads x1 AND dy as planes (3x3 layers whose forward does)
+    self.x_rec_own = False    # x1's scale record is this layer's amax[0:256] (so the weight gradient may reuse it)
+    self.dypl_off = None      # byte offset of this layer's own dy planes in the planes arena (side-stream weight gradients)
+    # links to other ops; each Graph._plan_* pass sets both ends of its link in one statement
+    # _plan_shared_dy: `res` is the output of a shortcut convolution nobody else reads, so d(res) = dy / out_div gets no tensor
+    self.dy_peer = None       # that shortcut convolution: it differentiates from THIS layer's dy
+    self.dy_from = None       # on the shortcut: the reverse link
+    self.peer_planes = None   # on the shortcut: its data gradient reads the planes of dy that dy_from made -- 'own' = dy_from
+    #                           keeps them (two streams), 'scratch' = the context's scratch still holds them (it runs right after)
+    # _plan_dy_producers: a GroupNorm is the only reader of y, so its backward writes dy last and leaves the sums and |dy| behind
+    self.dy_prod = None       # that GroupNorm (GroupNormAct.dy_cons is the reverse link; it asks dy_targets where to write)
+    self.bsum_off = None      # partial-sum slot of the bias gradient it leaves (this layer's and its peer's)
+    self.bsum_index = None    # ... and the fold-table entry of that slot
+    # _plan_res_via: `res` is the block input x of out = (x + h) / out_div, which the block's first GroupNorm normalises
+    self.res_via = None       # that GroupNorm: its backward adds d(out) / out_div into d(x), this layer does not touch d(res)
+    self.x_from = None        # _plan_x_records: the GroupNorm whose forward leaves this layer's |x1| / |x2| records behind
 
+  def grad_inputs(self):
+    """d(res) is not written by this layer when the shortcut peer differentiates from dy itself (dy_peer) or the block's
+    first GroupNorm adds it on the way (res_via)."""
+    if self.dy_peer is not None or self.res_via is not None:
+      return (self.x1, self.x2)
+    return self.inputs
+
+  # stk_conv2d_variant (include/stk.h) -> label: 0 / 1 = f32-input MFMA with 64 / 128 tiles, 3 = f32-input all-taps weight
+  # gradient, 4 = streaming kernel of a <= 4 channel side, 5 = the fp16 two-way split
   _VARIANT = {0: 't64', 1: 't128', 3: 't128', 4: 'thin', 5: 'x2'}
 
   def _kind(self, lib, direction):
@@ -360,15 +383,14 @@ class Conv(Op):
       k = self._kind(lib, direction) + 'p'
       if direction == 'wgrad':
         k += f'.w{min(self.W, 32)}'
-      elif hasattr(lib, 'conv2d_pl_ksplit'):
+      else:
         d = 0 if direction == 'fwd' else 1
-        c2 = 0 if d == 0 else self.C2
-        if int(lib.conv2d_pl_ksplit(d, self.C1, c2, self.N, self.H, self.W, self.Cout, self.KH, self.KW)) > 1:
+        shape = (d, self.C1, 0 if d == 0 else self.C2, self.N, self.H, self.W, self.Cout, self.KH, self.KW)
+        hw = int(lib.conv2d_pl_halo(*shape))
+        if int(lib.conv2d_pl_ksplit(*shape)) > 1:
           k += '.k'
-        elif hasattr(lib, 'conv2d_pl_halo'):
-          hw = int(lib.conv2d_pl_halo(d, self.C1, c2, self.N, self.H, self.W, self.Cout, self.KH, self.KW))
-          if hw:
-            k += f'.h{hw}'
+        elif hw:
+          k += f'.h{hw}'
       setattr(self, key, k)
     return k
 
@@ -379,10 +401,6 @@ class Conv(Op):
     """True when this layer's forward is a split form, i.e. has a one-product twin (include/stk_fp16.h) in the fp16 mode;
     the thin-side, f32-input-tile and strided forms run as in fp32."""
     return self.pl_fwd or self._kind(lib, 'fwd').endswith('.x2')
-
-  # prepared weights (include/stk.h "Prepared weights"): byte offsets of this layer's blocks in the program's arena,
-  # assigned by Graph.finalize; None = this direction of this shape prepares nothing
-  wp_off = (None, None)
 
   def plan_wp(self, lib, offset):
     """Reserve the forward / data-gradient blocks at `offset`; returns the new end of the arena."""
@@ -401,35 +419,6 @@ class Conv(Op):
   def _wp(self, rt, direction):
     off = self.wp_off[direction]
     return rt.wp + off if (rt.wp and off is not None) else None
-
-  # shared output gradient (Graph._plan_shared_dy): this layer's residual input `res` is the output of a shortcut
-  # convolution nobody else reads, so d(res) = dy / out_div needs no tensor of its own -- `dy_peer` is that convolution
-  # (it differentiates from THIS layer's dy with the factor folded into alpha); `dy_from` is the reverse link
-  dy_peer = None
-  dy_from = None
-  # Graph._plan_dy_producers: the GroupNorm that reads this layer's output (and is its only reader) -- its backward leaves
-  # this layer's bias / time-embedding sums and |dy| record behind; dyrec = that record (zeroed once per backward),
-  # bsum_off / bsum_index = the partial-sum slot and fold-table entry of the bias gradient
-  dy_prod = None
-  bsum_off = None
-  bsum_index = None
-  # Graph._plan_res_via: this layer's residual input `res` is the block input x of out = (x + h) / out_div, and x is also
-  # what the block's first GroupNorm normalises: that layer's backward adds d(out) / out_div into d(x) on the way
-  # (stk_gn_bwd_out_f32 dx1_add), so this layer's backward does not touch d(res)
-  res_via = None
-  x_from = None        # Graph._plan_x_records: the GroupNorm whose forward leaves this layer's |x1| / |x2| records behind
-  # Graph._plan_shared_dy: a 1x1 shortcut convolution differentiates from its peer's output gradient -- and that gradient
-  # already exists as planes (the peer's 3x3 data / weight gradient made them): its data gradient reads THOSE through the LDS-
-  # DMA kernel instead of splitting the fp32 tensor again in its loader.  'own' = the peer keeps its dy planes (two streams),
-  # 'scratch' = the context's shared scratch, still holding them when this layer's backward runs right after the peer's
-  peer_planes = None
-
-  # planes (include/stk.h "Planes"): decided by Graph.finalize
-  dypl_off = None      # byte offset of this layer's own dy planes in the planes arena (side-stream weight gradients)
-  pl_fwd = False       # the forward call reads x1 as planes
-  pl_dgrad = False     # the data-gradient call reads dy as planes (made here, into the context's scratch)
-  pl_wgrad = False     # the weight-gradient call reads x1 AND dy as planes (3x3 layers whose forward does)
-  x_rec_own = False    # x1's scale record is this layer's amax[0:256] (so the weight gradient may reuse it)
 
   def plan_planes(self, g, lib):
     same = self.stride == 1 and self.OH == self.H and self.OW == self.W and self.pad == self.KH // 2
@@ -452,7 +441,7 @@ class Conv(Op):
     if needs_dx and self.KH == 3 and int(lib.conv2d_pl_ok(1, self.C1, self.C2, *dims)):
       self.pl_dgrad = True
     if (self.pl_fwd and self.KH == 3 and self.w_layout == 0 and self.w.needs_grad and
-        os.environ.get('STK_PLANES_WGRAD', '1') != '0' and hasattr(lib, 'conv2d_wgrad_pl_ok') and
+        os.environ.get('STK_PLANES_WGRAD', '1') != '0' and
         int(lib.conv2d_wgrad_pl_ok(self.N, self.H, self.W, self.C1, self.Cout))):
       self.pl_wgrad = True
     if self.pl_dgrad or self.pl_wgrad:
@@ -462,158 +451,157 @@ class Conv(Op):
         self.dypl_off = g.pl_bytes
         g.pl_bytes += nb
 
-  def plan_backward(self):
-    if self.dy_peer is not None or self.res_via is not None:      # d(res) is not written here: do not count this op as a writer
-      saved, self.inputs = self.inputs, (self.x1, self.x2)
-      Op.plan_backward(self)
-      self.inputs = saved
+  def plan_backward(self, lib):
+    """Beta of the gradient targets, and everything about this layer's backward that the plan fixes (the links are final)."""
+    Op.plan_backward(self, lib)
+    src, peer, prod = self.dy_from, self.dy_peer, self.dy_prod
+    self._dy_of = src if src is not None else self          # the layer whose output gradient this one differentiates from
+    self._alpha = 1.0 / self.out_div / (src.out_div if src is not None else 1.0)
+    # who sums the bias / time-embedding gradient and measures |dy|: the GroupNorm backward that wrote dy last | the peer's
+    # pass (dy_from's 'dual') | this layer's one pass for itself and its peer | this layer's own pass
+    self._sums = 'gn' if prod is not None else 'peer' if src is not None else 'dual' if peer is not None else 'own'
+    # with a peer, the GroupNorm backward leaves the one record both layers read in the peer's buffer
+    self._rec_in = peer if (prod is not None and peer is not None) else self
+    self._temb_grad = self.temb is not None and self.temb.needs_grad
+    self._res_grad = self.res is not None and self.res.needs_grad and any(t is self.res for t in self.grad_inputs())
+    # data gradient: plane operands (the peer's planes of dy, or this layer's own) or fp32 ones, which take the |dy| record
+    # somebody left behind (_rec) or measure (_wp); the label of a split form gets '.f16' in the fp16 training mode
+    dx = any(t is not None and t.needs_grad and t.goff is not None for t in (self.x1, self.x2))
+    self._dy_planes = dx and self.pl_dgrad                  # this layer splits dy for its own data gradient
+    if not dx:
+      self._dgrad = None
+    elif (src is not None and self.peer_planes is not None) or self.pl_dgrad:
+      self._dgrad = ('conv2d_dgrad_pl', self._label_pl(lib, 'dgrad'), True)
+      self._dgrad_pl_of = src if (src is not None and self.peer_planes is not None) else self
     else:
-      Op.plan_backward(self)
+      kind = self._kind(lib, 'dgrad')
+      self._dgrad = ('conv2d_dgrad_rec' if self._sums in ('gn', 'peer') else 'conv2d_dgrad_wp', kind, kind.endswith('.x2'))
+    # weight gradient on fp32 operands: which thirds of amax are valid when it runs (include/stk.h "amax")
+    x_rec = self._kind(lib, 'fwd').endswith('.x2') and (self.x_rec_own or not self.pl_fwd)
+    dy_rec = (self._sums in ('gn', 'peer') or self._dy_planes or
+              (self._dgrad is not None and self._dgrad[0] != 'conv2d_dgrad_pl' and self._dgrad[2]))
+    self._have = int(x_rec) | 2 * int(dy_rec)
+    if self.w.needs_grad:     # (label, does it get '.f16')
+      wkind = self._kind(lib, 'wgrad')
+      self._wgrad = (self._label_pl(lib, 'wgrad'), True) if self.pl_wgrad else (wkind, wkind.endswith('.x2'))
+
+  def _dtemb(self, rt):
+    return rt.g(self.temb) + 4 * self.temb_col if self._temb_grad else None
+
+  def _dy_rec(self, rt):
+    """|dy| scale record: written by whoever measures dy, read by the planes of dy and the weight gradient."""
+    return rt.v(self._rec_in.amax) + 4 * 512
+
+  def _dypl(self, rt):
+    """Planes of this layer's dy: its own block (side-stream weight gradients) or the context's scratch."""
+    return rt.pl + self.dypl_off if self.dypl_off is not None else rt.dypl
+
+  def dy_targets(self, rt):
+    """For dy_prod, the GroupNorm backward that writes this layer's dy last: (scale of dy, bias partial sums -- their fold is
+    deferred here --, time-embedding gradient, its row stride, |dy| record)."""
+    assert rt.gn_table, 'the by-products of the GroupNorm backward ride on the batched folds'
+    fold = self.bsum_index is not None and rt.param_grads
+    if fold:
+      rt.defer_fold(self.bsum_index)
+    return (1.0 / self.out_div, rt.gnpart + 4 * self.bsum_off if fold else None, self._dtemb(rt),
+            self.temb_stride if self._temb_grad else 0, self._dy_rec(rt))
 
   def forward(self, rt):
     temb = rt.v(self.temb) + 4 * self.temb_col if self.temb is not None else None
-    f16 = rt.f16 and self.f16_form(rt.lib)
+    # fp16 mode (include/stk_fp16.h): a split form calls its one-product twin, its profiler label gets '.f16'
+    sfx, tag = ('_f16x1', '.f16') if rt.f16 and self.f16_form(rt.lib) else ('_f32', '')
+    out = (rt.v(self.w), self.w_layout, rt.v(self.bias), temb, self.temb_stride, rt.v(self.res), self.out_div, rt.v(self.y))
     if self.pl_fwd:
       t = self.x1
       if t.pl_maker is self:
         rt.make_planes(t)
-      label = self._label_pl(rt.lib, 'fwd')
-      rt.timed(label + '.f16' if f16 else label, self.flops, rt.lib.conv2d_fwd_pl_f16x1 if f16 else rt.lib.conv2d_fwd_pl_f32,
-               rt.planes(t), rt.rec(t), self.C1, rt.v(self.w), self.w_layout, rt.v(self.bias), temb, self.temb_stride,
-               rt.v(self.res), self.out_div, rt.v(self.y), self.N, self.H, self.W, self.Cout, self.KH, self.KW,
+      rt.timed(self._label_pl(rt.lib, 'fwd') + tag, self.flops, getattr(rt.lib, 'conv2d_fwd_pl' + sfx),
+               rt.planes(t), rt.rec(t), self.C1, *out, self.N, self.H, self.W, self.Cout, self.KH, self.KW,
                self._wp(rt, 0), rt.ws, rt.ws_bytes, rt.stream)
       return
-    if f16:
-      fn = rt.lib.conv2d_fwd_rec_f16x1 if self.x_from is not None else rt.lib.conv2d_fwd_wp_f16x1
-    else:
-      fn = rt.lib.conv2d_fwd_rec_f32 if self.x_from is not None else rt.lib.conv2d_fwd_wp_f32
-    rt.timed(self._kind(rt.lib, 'fwd') + ('.f16' if f16 else ''), self.flops, fn,
-             rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, rt.v(self.w), self.w_layout,
-             rt.v(self.bias), temb, self.temb_stride, rt.v(self.res), self.out_div,
-             rt.v(self.y), *self._dims(), self._wp(rt, 0), rt.v(self.amax), rt.ws, rt.ws_bytes, rt.stream)
+    stem = 'conv2d_fwd_rec' if self.x_from is not None else 'conv2d_fwd_wp'
+    rt.timed(self._kind(rt.lib, 'fwd') + tag, self.flops, getattr(rt.lib, stem + sfx),
+             rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, *out, *self._dims(), self._wp(rt, 0), rt.v(self.amax),
+             rt.ws, rt.ws_bytes, rt.stream)
 
   def backward(self, rt):
-    gy = rt.g(self.y)
-    alpha = 1.0 / self.out_div
-    lib = rt.lib
-    src = self.dy_from                          # a later layer whose output gradient, times 1 / its out_div, is ours
-    if src is not None:
-      gy = rt.g(src.y)
-      alpha = alpha / src.out_div
-    dtemb = None
-    if self.temb is not None and self.temb.needs_grad:
-      dtemb = rt.g(self.temb) + 4 * self.temb_col
-    gb = rt.g(self.bias)
-    g1, g2 = rt.g(self.x1), rt.g(self.x2)
-    gw = rt.g(self.w)
-    pl_dgrad = self.pl_dgrad and (g1 is not None or g2 is not None)
-    pl_wgrad = self.pl_wgrad and gw is not None
-    dy_rec = rt.v(self.amax) + 4 * 512           # |dy| scale record: planes of dy, reused by the weight gradient
-    rec_done = False
-    fuse_rec = (pl_dgrad or pl_wgrad) and self.Cout <= 256 and (dtemb is not None or gb is not None)
-    res_grad = self.res is not None and self.res.needs_grad
-    peer = self.dy_peer
-    if self.res_via is not None:
-      res_grad = False                           # the block's first GroupNorm adds d(out) / out_div into d(x) itself
-    if self.dy_prod is not None:
-      # the GroupNorm backward that wrote dy last left the sums (bias: batched fold; time embedding: written) and the
-      # record behind -- for the shortcut peer too, whose buffer then holds the one record both layers read
-      gb = dtemb = None
-      fuse_rec = False
-      rec_done = True
-      if peer is not None:
-        dy_rec = rt.v(peer.amax) + 4 * 512
-        res_grad = False
-    elif src is not None:
-      # the peer's pass over dy already left our bias gradient and our |dy| record behind
-      gb = dtemb = None
-      fuse_rec = False
-      rec_done = True
-    elif peer is not None:
-      # one pass over dy for both layers: sums -> both bias gradients, maxima -> both records; d(res) is never formed
-      lib.bias_grad_amax_dual_f32(gy, self.N, self.Cout, self.OH * self.OW, alpha, dtemb, self.temb_stride, gb, dy_rec,
-                                  rt.g(peer.bias), rt.v(peer.amax) + 4 * 512, rt.ws, rt.stream)
-      rec_done = True
-      res_grad = fuse_rec = False
-    if res_grad and fuse_rec and hasattr(lib, 'bias_grad_amax_res_f32'):
-      # one pass over dy: bias / time-embedding sums, the |dy| scale record AND the residual branch's gradient
-      lib.bias_grad_amax_res_f32(gy, self.N, self.Cout, self.OH * self.OW, alpha, dtemb, self.temb_stride, gb, dy_rec,
-                                 rt.g(self.res), self.b(self.res), rt.ws, rt.stream)
-      rec_done = True
-      res_grad = fuse_rec = False
-    if res_grad:
-      gr = rt.g(self.res)
-      lib.axpby_f32(gy, alpha, gr, self.b(self.res), gr, self.y.numel, rt.stream)
-    if fuse_rec:
-      # the bias gradient reads all of dy: it leaves the per-channel |dy| maxima behind as the scale record
-      lib.bias_grad_amax_f32(gy, self.N, self.Cout, self.OH * self.OW, alpha, dtemb, self.temb_stride, gb, dy_rec,
-                             rt.ws, rt.stream)
-      rec_done = True
-    elif not rec_done and (dtemb is not None or gb is not None):
-      lib.bias_grad_f32(gy, self.N, self.Cout, self.OH * self.OW, alpha, dtemb, self.temb_stride, gb,
-                        rt.ws, rt.stream)
-    # fp16 training mode (include/stk_fp16_train.h): every contraction calls its one-product twin, which runs the non-split
-    # forms exactly as the fp32 entry does; the profiler label of a split form gets '.f16'
-    sfx = '_f16x1' if rt.f16_bwd else '_f32'
-    f16 = '.f16' if rt.f16_bwd else ''
-    # data gradient first: its |dy| maxima are reused by the weight gradient (the two are independent otherwise)
-    have = 1 if self._kind(lib, 'fwd').endswith('.x2') else 0
-    if self.pl_fwd and not self.x_rec_own:
-      have = 0                                   # x1's record lives with another layer: the weight gradient measures
-    if src is not None or self.dy_prod is not None:
-      have |= 2                                  # the peer / the GroupNorm backward wrote our |dy| record
-    if pl_dgrad or pl_wgrad:
-      rec = dy_rec
-      if not rec_done:
-        lib.amax_partial_f32(gy, self.y.numel, rec, rt.stream)
-      dypl = rt.pl + self.dypl_off if self.dypl_off is not None else rt.dypl
-      lib.split_planes_f32(gy, self.N, self.Cout, self.OH * self.OW, rec, 256, dypl, rt.stream)
-      have |= 2
-    if src is not None and self.peer_planes is not None and (g1 is not None or g2 is not None):
-      # the peer's dy planes (and the record they were scaled with) serve this 1x1 data gradient too
-      ppl = rt.pl + src.dypl_off if self.peer_planes == 'own' else rt.dypl
-      rt.timed(self._label_pl(lib, 'dgrad') + f16, self.flops, getattr(lib, 'conv2d_dgrad_pl' + sfx),
-               ppl, rt.v(self.amax) + 4 * 512, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
-               g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
-               alpha, self.N, self.H, self.W, self.Cout, self.KH, self.KW, self._wp(rt, 1), rt.ws, rt.ws_bytes, rt.stream)
-    elif pl_dgrad:
-      rt.timed(self._label_pl(lib, 'dgrad') + f16, self.flops, getattr(lib, 'conv2d_dgrad_pl' + sfx),
-               dypl, rec, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
-               g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
-               alpha, self.N, self.H, self.W, self.Cout, self.KH, self.KW, self._wp(rt, 1), rt.ws, rt.ws_bytes, rt.stream)
-      have |= 2
-    elif g1 is not None or g2 is not None:
-      kind = self._kind(lib, 'dgrad')
-      rt.timed(kind + (f16 if kind.endswith('.x2') else ''), self.flops,
-               getattr(lib, ('conv2d_dgrad_rec' if (src is not None or self.dy_prod is not None) else 'conv2d_dgrad_wp') + sfx),
-               gy, rt.v(self.w), self.w_layout, g1, self.C1, self.b(self.x1),
-               g2, self.C2, self.b(self.x2) if self.x2 is not None else 0.0,
-               alpha, *self._dims(), self._wp(rt, 1), rt.v(self.amax), rt.ws, rt.ws_bytes, rt.stream)
-      if self._kind(lib, 'dgrad').endswith('.x2'):
-        have |= 2
+    """Three steps on gy, the output gradient of this layer or of the layer it shares one with (dy_from).  fp16 training
+    mode (include/stk_fp16_train.h): every contraction calls its one-product twin, which runs the non-split forms exactly
+    as the fp32 entry does; the profiler label of a split form gets '.f16'."""
+    gy = rt.g(self._dy_of.y)
+    sfx, tag = ('_f16x1', '.f16') if rt.f16_bwd else ('_f32', '')
+    self._bwd_dy(rt, gy)
+    if self._dgrad is not None:     # first: its |dy| maxima are reused by the weight gradient (the two are independent otherwise)
+      self._bwd_dgrad(rt, gy, sfx, tag)
     rt._cur = self.y.name
-    if pl_wgrad and rt.side is not None and rt.prof is None and self.dypl_off is not None:
-      rt.side_launch(getattr(lib, 'conv2d_wgrad_pl' + sfx), rt.planes(self.x1), rt.rec(self.x1), dypl, dy_rec, gw, alpha, rt.ws2,
-                     rt.ws_bytes, self.N, self.H, self.W, self.C1, self.Cout)
-    elif pl_wgrad:
-      # (on the main stream: STK_X2W_WGS_ALONE may ask for more workgroups than the side-stream launch above uses; see _X2W_WGS_ALONE)
-      rt.timed(self._label_pl(lib, 'wgrad') + f16, self.flops, getattr(lib, 'conv2d_wgrad_pl_wgs' + sfx),
-               rt.planes(self.x1), rt.rec(self.x1), dypl, dy_rec, gw, alpha, rt.ws, rt.ws_bytes,
-               self.N, self.H, self.W, self.C1, self.Cout, _X2W_WGS_ALONE, rt.stream)
-    elif gw is not None and rt.side is not None and rt.prof is None:
-      # a weight gradient is a leaf of the backward: x, dy and this layer's own records in, dw out
-      rt.side_launch(getattr(lib, 'conv2d_wgrad_amax' + sfx), rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, alpha,
-                     rt.ws2, rt.ws_bytes, *self._dims(), rt.v(self.amax), have)
-    elif gw is not None:
-      kind = self._kind(lib, 'wgrad')
-      rt.timed(kind + (f16 if kind.endswith('.x2') else ''), self.flops, getattr(lib, 'conv2d_wgrad_amax' + sfx),
-               rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, alpha,
-               rt.ws, rt.ws_bytes, *self._dims(), rt.v(self.amax), have, rt.stream)
+    gw = rt.g(self.w)
+    if gw is not None:
+      self._bwd_wgrad(rt, gy, gw, sfx, tag)
+
+  def _bwd_dy(self, rt, gy):
+    """The pass over dy: bias / time-embedding sums, the |dy| record, d(res), and dy as planes -- as few launches as the
+    plan allows (self._sums), none where a GroupNorm backward or the peer left everything behind."""
+    lib, own = rt.lib, self._sums == 'own'
+    head = (gy, self.N, self.Cout, self.OH * self.OW, self._alpha)
+    planes = self._dy_planes or (self.pl_wgrad and rt.param_grads)
+    dtemb, gb = (self._dtemb(rt), rt.g(self.bias)) if self._sums in ('own', 'dual') else (None, None)
+    sums = dtemb is not None or gb is not None
+    fuse = own and planes and self.Cout <= 256 and sums      # the pass that sums dy leaves its per-channel maxima as the record
+    if self._sums == 'dual':
+      # one pass over dy for both layers: sums -> both bias gradients, maxima -> both records; d(res) is never formed
+      peer = self.dy_peer
+      lib.bias_grad_amax_dual_f32(*head, dtemb, self.temb_stride, gb, self._dy_rec(rt), rt.g(peer.bias), peer._dy_rec(rt),
+                                  rt.ws, rt.stream)
+    elif fuse and self._res_grad:
+      lib.bias_grad_amax_res_f32(*head, dtemb, self.temb_stride, gb, self._dy_rec(rt), rt.g(self.res), self.b(self.res),
+                                 rt.ws, rt.stream)
+    else:
+      if self._res_grad:
+        gr = rt.g(self.res)
+        lib.axpby_f32(gy, self._alpha, gr, self.b(self.res), gr, self.y.numel, rt.stream)
+      if fuse:
+        lib.bias_grad_amax_f32(*head, dtemb, self.temb_stride, gb, self._dy_rec(rt), rt.ws, rt.stream)
+      elif own and sums:
+        lib.bias_grad_f32(*head, dtemb, self.temb_stride, gb, rt.ws, rt.stream)
+    if planes:
+      if own and not fuse:
+        lib.amax_partial_f32(gy, self.y.numel, self._dy_rec(rt), rt.stream)
+      lib.split_planes_f32(gy, self.N, self.Cout, self.OH * self.OW, self._dy_rec(rt), 256, self._dypl(rt), rt.stream)
+
+  def _bwd_dgrad(self, rt, gy, sfx, tag):
+    stem, label, split = self._dgrad
+    dx = (rt.v(self.w), self.w_layout, rt.g(self.x1), self.C1, self.b(self.x1),
+          rt.g(self.x2), self.C2, self.b(self.x2) if self.x2 is not None else 0.0, self._alpha)
+    if stem == 'conv2d_dgrad_pl':
+      args = (self._dgrad_pl_of._dypl(rt), self._dy_rec(rt), *dx, self.N, self.H, self.W, self.Cout, self.KH, self.KW,
+              self._wp(rt, 1))
+    else:
+      args = (gy, *dx, *self._dims(), self._wp(rt, 1), rt.v(self.amax))
+    rt.timed(label + (tag if split else ''), self.flops, getattr(rt.lib, stem + sfx), *args, rt.ws, rt.ws_bytes, rt.stream)
+
+  def _bwd_wgrad(self, rt, gy, gw, sfx, tag):
+    """A weight gradient is a leaf of the backward: on the side stream where there is one (the profiler times on the main
+    stream), with that stream's workspace."""
+    label, split = self._wgrad
+    side = rt.side is not None and rt.prof is None and (self.dypl_off is not None or not self.pl_wgrad)
+    if self.pl_wgrad:
+      # (on the main stream: STK_X2W_WGS_ALONE may ask for more workgroups than the side-stream launch uses; see _X2W_WGS_ALONE)
+      fn = getattr(rt.lib, ('conv2d_wgrad_pl' if side else 'conv2d_wgrad_pl_wgs') + sfx)
+      head = (rt.planes(self.x1), rt.rec(self.x1), self._dypl(rt), self._dy_rec(rt), gw, self._alpha)
+      tail = (rt.ws_bytes, self.N, self.H, self.W, self.C1, self.Cout) + (() if side else (_X2W_WGS_ALONE,))
+    else:
+      # x, dy and this layer's own records in, dw out
+      fn = getattr(rt.lib, 'conv2d_wgrad_amax' + sfx)
+      head = (rt.v(self.x1), self.C1, rt.v(self.x2), self.C2, gy, gw, self.w_layout, self._alpha)
+      tail = (rt.ws_bytes, *self._dims(), rt.v(self.amax), self._have)
+    if side:
+      rt.side_launch(fn, *head, rt.ws2, *tail)
+    else:
+      rt.timed(label + (tag if split else ''), self.flops, fn, *head, rt.ws, *tail, rt.stream)
 
   def ws_bytes(self, lib):
     shape = (self.C1, self.C2, self.N, self.H, self.W, self.Cout, self.KH, self.KW, self.stride, self.pad)
-    pw = int(lib.conv2d_wgrad_pl_ws_bytes(self.N, self.H, self.W, self.C1, self.Cout)) \
-        if (self.C2 == 0 and self.KH == 3 and hasattr(lib, 'conv2d_wgrad_pl_ws_bytes')) else 0
+    pw = int(lib.conv2d_wgrad_pl_ws_bytes(self.N, self.H, self.W, self.C1, self.Cout)) if (self.C2 == 0 and self.KH == 3) else 0
     return max(pw, int(lib.conv2d_wgrad_ws_bytes(self.C1, self.C2, self.N, self.Cout, self.OH, self.OW,
                                                  self.KH, self.KW)),
                int(lib.conv2d_fwd_ws_bytes(*shape)), int(lib.conv2d_dgrad_ws_bytes(*shape)),
@@ -924,7 +912,7 @@ class AttentionCore(Op):
     self.scale = float(int(C) ** (-0.5))
     lib = g.lib
     allowed = lib is not None and os.environ.get('STK_ATTN_FUSED', '1') != '0'
-    self.fused = bool(allowed and hasattr(lib, 'attention_ok') and int(lib.attention_ok(B, C, self.T)))
+    self.fused = bool(allowed and int(lib.attention_ok(B, C, self.T)))
     self.long = bool(allowed and not self.fused and getattr(lib, 'has_attention_long', False) and
                      int(lib.attention_long_ok(B, C, self.T)))
     if self.fused or self.long:
@@ -1215,18 +1203,25 @@ class Graph:
     self.dypl_bytes = 0
     # weight gradients on a side stream (engine/executor.py): every such layer keeps the planes of its output gradient
     self.own_dypl = os.environ.get('STK_WGRAD_STREAM', '1') != '0' and bool(getattr(lib, 'is_device', False))
-    if os.environ.get('STK_PLANES', '1') != '0' and hasattr(lib, 'conv2d_pl_ok'):
+    # what the passes below look up, built once: act tensor id -> the ops that read it, in forward order, and every op's
+    # position in that order (the ZeroXRecords op that _plan_x_records puts in front shifts all of them alike)
+    readers = {}
+    for op in self.ops:
+      for v in vars(op).values():
+        if isinstance(v, Tensor) and v.space == 'act' and v.producer is not op:
+          readers.setdefault(id(v), []).append(op)
+    index = {id(op): i for i, op in enumerate(self.ops)}
+    if os.environ.get('STK_PLANES', '1') != '0':
       for op in self.ops:
         if isinstance(op, Conv):
           op.plan_planes(self, lib)
-      self._plan_f32_copies(lib)
-      self._plan_x_records(lib)
-    self._plan_shared_dy(lib)
-    fold_batch = os.environ.get('STK_GN_FOLD_BATCH', '1') != '0' and hasattr(lib, 'gn_param_grad_batch')
-    if hasattr(lib, 'gn_bwd_out_f32'):
-      self._plan_res_via(lib)
-      if fold_batch:
-        self._plan_dy_producers(lib)
+      self._plan_f32_copies(lib, readers)
+      self._plan_x_records(lib, index)
+    self._plan_shared_dy(lib, readers, index)
+    fold_batch = os.environ.get('STK_GN_FOLD_BATCH', '1') != '0'
+    self._plan_res_via(lib, index)
+    if fold_batch:
+      self._plan_dy_producers(lib)
     # deferred parameter-gradient folds: a slot of [N][C][2] partial sums per GroupNorm layer (and per convolution bias
     # served by a GroupNorm backward), table entries (slot offset, dgamma offset, dbeta offset, N, C) in backward order
     # (STK_GN_FOLD_BATCH=0: every layer folds its own sums -- a debugging switch, results are bit-identical)
@@ -1255,17 +1250,16 @@ class Graph:
             self.gnpart_size += _round_up(2 * cons.N * cons.Cout)
             self.gn_folds.append((cons.bsum_off, other, own, cons.N, cons.Cout))
     for op in reversed(self.ops):
-      op.plan_backward()
+      op.plan_backward(lib)
     return self
 
-  def _plan_x_records(self, lib):
+  def _plan_x_records(self, lib, index):
     """ResnetBlockBigGANpp with a shortcut: GroupNorm_0 and the 1x1 Conv_2 read the same (two-source) block input
     (layerspp.py:256, 283).  Conv_2 takes it as fp32 operands of the split kernel and would measure |x1|, |x2| first (two
     passes); GroupNorm_0's one-pass forward -- which runs first and holds those values in registers -- leaves the maxima
     in Conv_2's amax buffer instead (stk_gn_fwd_pl_max_f32 / stk_conv2d_fwd_rec_f32; the weight gradient reuses them)."""
-    if os.environ.get('STK_X_RECORDS', '1') == '0' or not hasattr(lib, 'gn_fwd_pl_max_f32'):
+    if os.environ.get('STK_X_RECORDS', '1') == '0':
       return
-    index = {id(op): i for i, op in enumerate(self.ops)}
     found = False
     for op in self.ops:
       if not isinstance(op, Conv) or op.pl_fwd or op.x_from is not None or not op._kind(lib, 'fwd').endswith('.x2'):
@@ -1283,24 +1277,20 @@ class Graph:
     """act tensor id -> ops that write its gradient, in FORWARD order (so [0] is the last writer of the backward)."""
     w = {}
     for op in self.ops:
-      ins = op.inputs
-      if isinstance(op, Conv) and (op.dy_peer is not None or op.res_via is not None):
-        ins = (op.x1, op.x2)
       seen = set()
-      for t in ins:
+      for t in op.grad_inputs():
         if t is not None and t.space == 'act' and t.needs_grad and id(t) not in seen:
           seen.add(id(t))
           w.setdefault(id(t), []).append(op)
     return w
 
-  def _plan_res_via(self, lib):
+  def _plan_res_via(self, lib, index):
     """ResnetBlockBigGANpp without a shortcut convolution: out = (x + Conv_1(h)) / sqrt 2 with h = ... GroupNorm_0(x) ...
     (layerspp.py:256-287) is planned as Conv_1 with res = x.  d(x) receives d(out) / sqrt 2 from the skip and the
     GroupNorm_0 gradient; instead of Conv_1's backward writing the first in a pass of its own (read d(out), read-modify-
     write d(x)) the GroupNorm backward -- which writes d(x) anyway -- adds it on the way (stk_gn_bwd_out_f32 dx1_add)."""
     if os.environ.get('STK_RES_VIA', '1') == '0':
       return
-    index = {id(op): i for i, op in enumerate(self.ops)}
     for op in self.ops:
       if not isinstance(op, Conv) or op.res is None or not op.res.needs_grad or op.dy_peer is not None:
         continue
@@ -1333,7 +1323,7 @@ class Graph:
         continue
       if op.dy_from is not None or op.y is self.output or not op.y.needs_grad:
         continue
-      if op.res is not None and op.res.needs_grad and op.dy_peer is None and op.res_via is None:
+      if op.res is not None and op.res.needs_grad and op.res in op.grad_inputs():
         continue                                   # its pass over dy also writes d(res): nothing to save
       if op.bias is None and (op.temb is None or not op.temb.needs_grad):
         continue
@@ -1351,18 +1341,13 @@ class Graph:
     if any(isinstance(op, GroupNormAct) and op.dy_cons is not None for op in self.ops):
       self.ops.append(ZeroRecords(self.amax_block, len(self.conv_amax)))
 
-  def _plan_shared_dy(self, lib):
+  def _plan_shared_dy(self, lib, readers, index):
     """ResnetBlockBigGANpp with a shortcut convolution: out = (Conv_2(x) + Conv_1(h)) / sqrt 2 (layerspp.py:283-287) is
     planned as Conv_1 with res = Conv_2's output.  That output has one reader, so its gradient is just dy(Conv_1) /
     out_div: instead of writing it (one pass), measuring it (another) and summing it for Conv_2's bias (a third), Conv_1's
     own pass over dy serves both layers and Conv_2 differentiates from dy(Conv_1) directly."""
-    if os.environ.get('STK_SHARED_DY', '1') == '0' or not hasattr(lib, 'bias_grad_amax_dual_f32'):
+    if os.environ.get('STK_SHARED_DY', '1') == '0':
       return
-    readers = {}
-    for op in self.ops:
-      for v in vars(op).values():
-        if isinstance(v, Tensor) and v.space == 'act' and v.producer is not op:
-          readers.setdefault(id(v), []).append(op)
     for op in self.ops:
       if not isinstance(op, Conv) or op.res is None or not op.res.needs_grad:
         continue
@@ -1382,25 +1367,19 @@ class Graph:
         continue
       op.dy_peer, P.dy_from = P, op
       if ((P.x1.needs_grad or (P.x2 is not None and P.x2.needs_grad)) and
-          hasattr(lib, 'conv2d_pl_ok') and
           int(lib.conv2d_pl_ok(1, P.C1, P.C2, P.N, P.H, P.W, P.Cout, P.KH, P.KW, 1, P.pad))):
         if op.dypl_off is not None:
           P.peer_planes = 'own'
-        elif not self.own_dypl and self.ops.index(P) + 1 == self.ops.index(op):
+        elif not self.own_dypl and index[id(P)] + 1 == index[id(op)]:
           P.peer_planes = 'scratch'
 
-  def _plan_f32_copies(self, lib):
+  def _plan_f32_copies(self, lib, readers):
     """For every GroupNorm output that is made as planes: who still reads its fp32 NCHW copy?  A convolution whose
     forward takes planes does not; its weight gradient does unless it takes planes too.  Anything else does."""
-    readers = {}
-    for op in self.ops:
-      for v in vars(op).values():
-        if isinstance(v, Tensor) and v.space == 'act' and v.producer is not op:
-          readers.setdefault(id(v), []).append(op)
     for op in self.ops:
       if not isinstance(op, GroupNormAct) or op.y.pl_maker is not op:
         continue
-      op.fused = bool(int(lib.gn_fwd_pl_fused(op.C1, op.C2, op.HW, op.G))) if hasattr(lib, 'gn_fwd_pl_fused') else False
+      op.fused = bool(int(lib.gn_fwd_pl_fused(op.C1, op.C2, op.HW, op.G)))
       y = op.y
       fwd = bwd = y is self.output
       for r in readers.get(id(y), []):

@@ -154,7 +154,7 @@ def _engine_lib(model, batch):
   if engine is None:
     return None
   lib = engine().lib
-  if lib.is_device != batch.is_cuda or batch.dtype != torch.float32 or not hasattr(lib, 'sm_loss_fwd_f32'):
+  if lib.is_device != batch.is_cuda or batch.dtype != torch.float32:
     return None
   return lib
 

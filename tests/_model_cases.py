@@ -607,7 +607,7 @@ def two_streams_deterministic(st, lib, B=96, delays=(150000, 600000, 2000000), n
     * a neighbour stream that streams 64 MB blocks through HBM like the reduce-copy kernels of a gradient exchange
       (_CopyNeighbour), `copy_runs` times beside each of the two backward modes.
   Watch on the packed-fp32 hazard (csrc/Makefile HAZARD_FLAGS, profiles/r04_pk_hazard.txt): a build with the SLP vectoriser
-  on fails every one of these runs (tools/_probe/side_race2.py: 168 of 168)."""
+  on fails every one of these runs (the round-4 reproducer, since retired: 168 of 168)."""
   from importlib import import_module
   G = import_module('soft-truncation_amd.engine.graph')
   cfg, cfg_cpu, sde, model, ref = build_pair(st, tiny_config(st, 'wide'), lib)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from _fullsize_cases import build_full
+from _launch_trace import LibProxy
 from _model_util import build_pair, patched_rng, tiny_config
 
 pytestmark = pytest.mark.gpu
@@ -60,32 +61,18 @@ def test_fp16_evaluation_calls_the_twins(st, hip_lib):
   x = torch.randn(4, 3, 16, 16, device=cfg.device)
   t = torch.full((4,), 0.5, device=cfg.device)
   score_fn = st.models.utils.get_score_fn(cfg, sde, model, train=False, continuous=True)
-  log = []
-
-  class Recording:
-    def __init__(self, lib):
-      self._lib = lib
-
-    def __getattr__(self, name):
-      f = getattr(self._lib, name)
-      if not callable(f):
-        return f
-
-      def call(*a):
-        log.append(name)
-        return f(*a)
-      return call
+  calls = []
 
   ex.use_graphs, saved = False, ex.use_graphs          # eager launches: every call goes through the handle
-  ex.lib = Recording(hip_lib)
+  ex.lib = LibProxy(st.engine.lib, hip_lib, calls, execute=True)
   try:
     with torch.no_grad():
       score_fn(x, t)
-      f32 = list(log)
-      del log[:]
+      f32 = [n for n, _ in calls]
+      del calls[:]
       with st.models.utils.precision(model, 'fp16'):
         score_fn(x, t)
-      f16 = list(log)
+      f16 = [n for n, _ in calls]
   finally:
     ex.lib, ex.use_graphs = hip_lib, saved
   torch.cuda.synchronize()

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from _fullsize_cases import build_full
+from _launch_trace import LibProxy
 from _model_util import build_pair, make_state, patched_rng, tiny_config
 
 pytestmark = pytest.mark.gpu
@@ -99,24 +100,10 @@ def test_fp16_step_calls_only_twins_for_split_forms(st, hip_lib):
   cfg, _, sde, model, _ = _wide(st, hip_lib)
   ex = model.module.engine()
   assert ex.use_side
-  log = []
-
-  class Recording:
-    def __init__(self, lib):
-      self._lib = lib
-
-    def __getattr__(self, name):
-      f = getattr(self._lib, name)
-      if not callable(f):
-        return f
-
-      def call(*a):
-        log.append(name)
-        return f(*a)
-      return call
+  calls = []
 
   ex.use_graphs, saved = False, ex.use_graphs
-  ex.lib = Recording(hip_lib)
+  ex.lib = LibProxy(st.engine.lib, hip_lib, calls, execute=True)
   try:
     x = torch.randn(4, 3, 16, 16, device=cfg.device)
     t = torch.full((4,), 0.5, device=cfg.device)
@@ -126,6 +113,7 @@ def test_fp16_step_calls_only_twins_for_split_forms(st, hip_lib):
   finally:
     ex.lib, ex.use_graphs = hip_lib, saved
   torch.cuda.synchronize()
+  log = [n for n, _ in calls]
   used = set(log) & TWINS
   assert {'conv2d_fwd_pl_f16x1', 'conv2d_dgrad_pl_f16x1'} <= used, sorted(set(log))
   assert used & {'conv2d_wgrad_pl_f16x1', 'conv2d_wgrad_pl_wgs_f16x1'}, sorted(set(log))

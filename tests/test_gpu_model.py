@@ -223,6 +223,7 @@ def test_backward_window_launches_library_kernels_only(st, hip_lib, monkeypatch)
   if os.environ.get('STK_SELFCHECK'):
     pytest.skip('needs the HIP library')
   from importlib import import_module
+  from _launch_trace import LibProxy
   from _model_util import build_pair, make_state, patched_rng, tiny_config
   import numpy as np
   E = import_module('soft-truncation_amd.engine.executor')
@@ -243,33 +244,22 @@ def test_backward_window_launches_library_kernels_only(st, hip_lib, monkeypatch)
       return step_fn(state, batch)
 
   step()                                                  # builds the program, first (eager) use of its context
-  log = []
-
-  class Recording:
-    def __init__(self, lib):
-      self._lib = lib
-    def __getattr__(self, name):
-      f = getattr(self._lib, name)
-      if not callable(f) or name in ('backend',):
-        return f
-      def call(*a):
-        log.append((name, a[-1] if a else None))
-        return f(*a)
-      return call
+  calls = []                                              # (entry or marker, arguments): launches carry their stream last
 
   real_bwd = E.Executor._run_backward
-  monkeypatch.setattr(E.Executor, '_run_backward', lambda self, *a, **k: (log.append(('<backward>', None)), real_bwd(self, *a, **k))[1])
+  monkeypatch.setattr(E.Executor, '_run_backward', lambda self, *a, **k: (calls.append(('<backward>', ())), real_bwd(self, *a, **k))[1])
   real_begin, real_join = E.SideStream.begin, E.SideStream.join
-  monkeypatch.setattr(E.SideStream, 'begin', lambda self: (log.append(('<fork>', None)), real_begin(self))[1])
-  monkeypatch.setattr(E.SideStream, 'join', lambda self: (log.append(('<join>', None)), real_join(self))[1])
+  monkeypatch.setattr(E.SideStream, 'begin', lambda self: (calls.append(('<fork>', ())), real_begin(self))[1])
+  monkeypatch.setattr(E.SideStream, 'join', lambda self: (calls.append(('<join>', ())), real_join(self))[1])
   rec = E.LibraryKernelsOnly(record=True)
   monkeypatch.setattr(E, '_LIB_ONLY_RECORDER', rec)
-  ex.lib = Recording(hip_lib)                              # ops launch through rt.lib = the executor's library handle
+  ex.lib = LibProxy(L, hip_lib, calls, execute=True)      # ops launch through rt.lib = the executor's library handle
   try:
     step()
   finally:
     ex.lib = hip_lib
   torch.cuda.synchronize()
+  log = [(n, a[-1] if a else None) for n, a in calls]
   names = [n for n, _ in log]
   assert '<fork>' in names and '<join>' in names
   # (the forward has a fork of its own: the data-gradient weight blocks are prepared on the side stream beside it)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds variants of libstk.so for the co-residency hunt (tools/_probe/side_race2.py) into tools/_probe/build/:
+# Builds variants of libstk.so for the co-residency hunt (today: tools/_probe/watch_with_slp.py) into tools/_probe/build/:
 #   libstk_slp.so        every translation unit WITH the SLP vectoriser (packed-fp32 VALU code), as in round 3 before the flag
 #   libstk_gnslp.so      only groupnorm.hip with SLP (the kernel whose result went wrong), the rest as shipped
 #   libstk_restslp.so    everything but groupnorm.hip with SLP

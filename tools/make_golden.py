@@ -3,6 +3,7 @@
 /root/reference through oracle/refimport.py) on small seeded inputs.
 
 Run in the build container only (the reference never travels):   python tools/make_golden.py [samplers | ref_live]
+(`python tools/make_golden.py launch_trace` is the exception: it records this project's own launch plan, on any machine.)
 
 Every fixture is data: inputs (including every noise draw, made explicit) and the reference's outputs.
 No reference source is stored.  tests/test_oracle_golden.py then pins the restatements (sde_lib, losses,
@@ -346,8 +347,29 @@ def ref_live_fixture(ns):
   np.savez_compressed(os.path.join(OUT, 'ref_live.npz'), **arrays)
 
 
+def launch_trace_fixture(root=ROOT):
+  """tests/golden/launch_trace.json (tests/test_launch_trace.py): what the engine of the checkout at `root` launches, on the
+  product library (queries only: no GPU is needed) and the checker.  This one is the project's own output, not the
+  reference's.  `launch_trace <other checkout>` traces that checkout's engine with this one's helper and libraries (set
+  STK_LIBSTK to a built libstk.so if the other checkout has none): a refactor records from its parent that way."""
+  sys.path.insert(0, os.path.abspath(root))
+  import soft_truncation_amd as st
+  import _launch_trace as lt
+  assert os.path.dirname(os.path.abspath(st.__file__)) == os.path.join(os.path.abspath(root), 'soft-truncation_amd')
+  L = st.engine.lib
+  libs = {'product': L.load(), 'checker': L.load_path(os.path.join(ROOT, 'oracle', 'libstk_ref.so'))}
+  data = lt.record(st, libs, os.environ)
+  path = os.path.join(OUT, 'launch_trace.json')
+  with open(path, 'w') as f:
+    json.dump(data, f, indent=0)
+    f.write('\n')
+  print(path, os.path.getsize(path), 'bytes,', len(data), 'traces')
+
+
 def main():
   os.makedirs(OUT, exist_ok=True)
+  if len(sys.argv) > 1 and sys.argv[1] == 'launch_trace':
+    return launch_trace_fixture(*sys.argv[2:3])
   ns = refimport.load()
   if len(sys.argv) > 1 and sys.argv[1] == 'samplers':
     return samplers_fixture(ns)
