@@ -439,7 +439,9 @@ int stk_sm_loss_bwd_f32(const float* net, const float* z, const float* std, cons
  *   stk_adam_f32:   torch.optim.Adam/AdamW single-tensor update (losses.py:29-41,47-56) with the
  *                   clip_grad_norm_ coefficient min(1, max_norm/(sqrt(*sumsq)+1e-6)) applied to g on
  *                   the fly when sumsq != NULL and max_norm >= 0; g itself is rescaled in place
- *                   (as clip_grad_norm_ does).  bc1 = 1-b1^t, bc2 = 1-b2^t.
+ *                   (as clip_grad_norm_ does).  bc1 = 1-b1^t, bc2 = 1-b2^t.  The betas are rounded to fp32 at this
+ *                   interface; 1 - b2 is formed in fp32 (0.999 -> 1 - b2 = 0.0009999871).  A NaN sum of squares makes
+ *                   the coefficient, and with it every g and p, NaN, as clip_grad_norm_ does.
  *   stk_ema_f32:    s -= one_minus_decay * (s - p)      (models/ema.py:50-51)
  * ------------------------------------------------------------------------------------------ */
 int stk_sumsq_f32(const float* x, long n, float* out, float* ws, void* stream);

@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   float coef = 1.f;
   if (sumsq && a.max_norm >= 0.f) {
     coef = a.max_norm / (sqrtf(sumsq[0]) + 1e-6f);
-    coef = fminf(coef, 1.f);
+    coef = coef > 1.f ? 1.f : coef;                  // not fminf: a NaN norm must reach every gradient (stk_adam_f32)
   }
   const long stride = (long)gridDim.x * 256;
   const long n4 = n >> 2;
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void adam_kernel_scalar(float* __restrict__ p,
   float coef = 1.f;
   if (sumsq && a.max_norm >= 0.f) {
     coef = a.max_norm / (sqrtf(sumsq[0]) + 1e-6f);
-    coef = fminf(coef, 1.f);
+    coef = coef > 1.f ? 1.f : coef;                  // not fminf: a NaN norm must reach every gradient (stk_adam_f32)
   }
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) adam_one(p[i], g[i], m[i], v[i], a, coef);
@@ -289,7 +289,10 @@ __global__ __launch_bounds__(256) void adam_amsgrad_kernel(float* __restrict__ p
                                                            float* __restrict__ v, float* __restrict__ vmax, long n, AdamArgs a,
                                                            const float* __restrict__ sumsq) {
   float coef = 1.f;
-  if (sumsq && a.max_norm >= 0.f) coef = fminf(a.max_norm / (sqrtf(sumsq[0]) + 1e-6f), 1.f);
+  if (sumsq && a.max_norm >= 0.f) {
+    coef = a.max_norm / (sqrtf(sumsq[0]) + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;                  // a NaN stays (stk_adam_f32)
+  }
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     float gi = g[i] * coef;
@@ -301,7 +304,7 @@ __global__ __launch_bounds__(256) void adam_amsgrad_kernel(float* __restrict__ p
     }
     const float mi = m[i] + (gi - m[i]) * (1.f - a.b1);
     const float vi = v[i] * a.b2 + (1.f - a.b2) * gi * gi;
-    const float vm = fmaxf(vmax[i], vi);
+    const float vm = vmax[i] > vi ? vmax[i] : vi;    // torch.maximum: a NaN v reaches vmax (fmaxf would drop it)
     p[i] = pi - a.step_size * (mi / (sqrtf(vm) / a.bc2_sqrt + a.eps));
     m[i] = mi; v[i] = vi; vmax[i] = vm;
   }
@@ -429,6 +432,10 @@ int stk_sumsq_f32(const float* x, long n, float* out, float* ws, void* stream) {
   return STK_OK;
 }
 
+/* Non-finite gradients: clip_grad_norm_ multiplies every gradient by clamp(max_norm / (norm + 1e-6), max = 1), and clamp
+ * keeps a NaN, so after one NaN gradient under clipping the reference's parameters are all NaN and the run stops being
+ * silent about it.  The three kernels do the same: the coefficient is clamped with a comparison, not with fminf (which
+ * returns 1 for a NaN and would poison only the non-finite elements while training goes on). */
 int stk_adam_f32(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float weight_decay, int adamw, float bc1, float bc2, const float* sumsq, float max_norm,
                  void* stream) {
