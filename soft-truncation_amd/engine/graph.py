@@ -858,6 +858,72 @@ class UpFirDn(Op):
                              self.gpad0_x, self.gpad1_x, self.gpad0_y, self.gpad1_y, rt.stream)
 
 
+class UpConv(Op):
+  """y = (FIR(conv_transpose(x, w), taps) + bias + res) / out_div -- upsample_conv_2d, the body of Conv2d(up=True)
+  (models/up_or_down_sampling.py:72-141, with its weight reversal read as a flip of both spatial axes), on the kernels of
+  include/stk_upconv.h: a polyphase forward, a dense stride-2 data gradient and a per-tap weight gradient.  Only the
+  product library has them: on any other the operation is refused here, when the graph is planned.  The kernels are
+  fp32 in every precision mode, as every non-split layer is.
+
+  The backward applies the FIR's adjoint to dy once, into a buffer this op owns (`du`): the data gradient fills it on the
+  main stream, the weight gradient -- a leaf of the backward, on the side stream where there is one -- reads it."""
+
+  def __init__(self, g, x, w, bias, taps, pad0, res=None, out_div=1.0, name='upconv'):
+    lib = g.lib
+    if not getattr(lib, 'has_upconv', False):
+      raise NotImplementedError(f'backend {getattr(lib, "backend", None)} does not export include/stk_upconv.h: no kernel '
+                                f'computes the FIR-upsampling convolution (Conv2d(up=True), upsample_conv_2d)')
+    self.x, self.w, self.bias, self.res, self.out_div = x, w, bias, res, float(out_div)
+    N, Cin, H, W = x.shape
+    Cout, cin_w, K, KW = w.shape
+    if cin_w != Cin:
+      raise RuntimeError(f'{name}: expected input with {cin_w} channels (weight {tuple(w.shape)}), got {Cin}')
+    taps = np.asarray(taps, dtype=np.float32)
+    KT = taps.shape[0]
+    self.dims = (N, H, W, Cin, Cout, K, KT, int(pad0))
+    if K != KW or taps.shape != (KT, KT) or int(lib.upconv2d_ws_bytes(0, *self.dims[:7])) < 0:
+      raise NotImplementedError(f'{name}: include/stk_upconv.h takes 1x1 / 3x3 weights and FIR kernels of up to 4 taps, '
+                                f'got weight {tuple(w.shape)}, taps {taps.shape}')
+    self.k = g.const(taps)
+    self.y = g.new((N, Cout, 2 * H, 2 * W), name=name)
+    self.du = g.new((N, Cout, 2 * H - 2 + K, 2 * W - 2 + K), needs_grad=False, name=name + '.du')
+    self.du.producer = self
+    self.inputs = (x, res)
+    self.flops = 2.0 * N * H * W * Cout * Cin * K * K     # one product per tap and input pixel, in all three directions
+
+  def forward(self, rt):
+    rt.timed('upconv.fwd', self.flops, rt.lib.upconv2d_fwd_f32, rt.v(self.x), rt.v(self.w), rt.v(self.k), rt.v(self.bias),
+             rt.v(self.res), self.out_div, rt.v(self.y), *self.dims, rt.ws, rt.ws_bytes, rt.stream)
+
+  def backward(self, rt):
+    lib, gy, alpha = rt.lib, rt.g(self.y), 1.0 / self.out_div
+    N, H, W, _, Cout = self.dims[:5]
+    gr = rt.g(self.res)
+    if gr is not None:
+      lib.axpby_f32(gy, alpha, gr, self.b(self.res), gr, self.y.numel, rt.stream)
+    gb = rt.g(self.bias)
+    if gb is not None:
+      lib.bias_grad_f32(gy, N, Cout, 4 * H * W, alpha, None, 0, gb, rt.ws, rt.stream)
+    gx = rt.g(self.x)
+    du, have_du = rt.v(self.du), 0
+    if gx is not None:
+      rt.timed('upconv.dgrad', self.flops, lib.upconv2d_dgrad_f32, gy, rt.v(self.w), rt.v(self.k), du, 0, gx,
+               self.b(self.x), alpha, *self.dims, rt.stream)
+      have_du = 1
+    rt._cur = self.y.name
+    gw = rt.g(self.w)
+    if gw is not None:
+      head = (rt.v(self.x), gy, rt.v(self.k), du, have_du, gw, alpha, *self.dims)
+      if rt.side is not None and rt.prof is None:
+        rt.side_launch(lib.upconv2d_wgrad_f32, *head, rt.ws2, rt.ws_bytes)
+      else:
+        rt.timed('upconv.wgrad', self.flops, lib.upconv2d_wgrad_f32, *head, rt.ws, rt.ws_bytes, rt.stream)
+
+  def ws_bytes(self, lib):
+    N, Cout = self.dims[0], self.dims[4]
+    return max(int(lib.upconv2d_ws_bytes(0, *self.dims[:7])), int(lib.upconv2d_ws_bytes(2, *self.dims[:7])), 4 * N * Cout)
+
+
 class AddDiv(Op):
   """out = (a + b) / div -- skip_rescale combines (models/ncsnpp.py:340-343,400-403) and the
   plain pyramid sum (models/ncsnpp.py:396) with div = 1."""

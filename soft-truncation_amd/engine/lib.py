@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
-include/stk_fp16_train.h, include/stk_blocks.h and include/stk_attention_long.h).
+include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h and include/stk_upconv.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -140,6 +140,15 @@ SIGNATURES_ATTN_LONG = {
   'stk_attention_long_fwd_f32': [P, P, P, L, P, P, P, I, I, I, F, P, L, S],
   'stk_attention_long_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, F, P, L, S],
 }
+# include/stk_upconv.h: the FIR-upsampling convolution (Conv2d(up=True)).  Bound like SIGNATURES_FP16, when present;
+# `StkLib.has_upconv` says whether they are (engine.graph.UpConv refuses to plan without them).  _ws_bytes is a query.
+SIGNATURES_UPCONV = {
+  'stk_upconv2d_ws_bytes': [I, I, I, I, I, I, I, I],
+  'stk_upconv2d_fwd_f32': [P, P, P, P, P, F, P, I, I, I, I, I, I, I, I, P, L, S],
+  'stk_upconv2d_dgrad_f32': [P, P, P, P, I, P, F, F, I, I, I, I, I, I, I, I, S],
+  'stk_upconv2d_wgrad_f32': [P, P, P, P, I, P, F, I, I, I, I, I, I, I, I, P, L, S],
+}
+_RESTYPE_UPCONV = {'stk_upconv2d_ws_bytes': c_long}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -178,6 +187,8 @@ class StkLib:
     self.has_blocks = self._bind_optional(SIGNATURES_BLOCKS, 'include/stk_blocks.h')
     self.has_attention_long = self._bind_optional(SIGNATURES_ATTN_LONG, 'include/stk_attention_long.h',
                                                   restype=_RESTYPE_ATTN_LONG, unchecked=_NO_CHECK_ATTN_LONG)
+    self.has_upconv = self._bind_optional(SIGNATURES_UPCONV, 'include/stk_upconv.h', restype=_RESTYPE_UPCONV,
+                                          unchecked=set(_RESTYPE_UPCONV))
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 

@@ -7,8 +7,9 @@ keep the reference signatures and run on ``op.upfirdn2d`` / the C-ABI kernels.  
 functions put the same operators into the engine's planned graph, which is what the score
 network uses.
 
-``upsample_conv_2d`` (:72-141) is dead in the reference (``w[..., ::-1, ::-1]`` raises in
-PyTorch), so it raises here as well.
+``upsample_conv_2d`` (:72-141) raises in the reference (``w[..., ::-1, ::-1]`` is a negative-stride slice, which PyTorch
+rejects); what it means -- StyleGAN2's fused up-convolution, the weights flipped in both spatial axes -- runs here on the
+kernels of include/stk_upconv.h, for factor 2 and ungrouped weights.
 """
 import numpy as np
 import torch
@@ -174,9 +175,94 @@ def conv_downsample_2d(x, w, k=None, factor=2, gain=1):
   return _Conv2dNoPad.apply(x, w, factor)
 
 
+def _conv_up_taps(k, factor, gain, conv_w):
+  """FIR taps of upsample_conv_2d and the first padding of its upfirdn2d call (:138-141): pad ((p+1)//2 + factor - 1,
+  p//2 + 1), p = (len(k) - factor) - (conv_w - 1)."""
+  if k is None:
+    k = [1] * factor
+  k = _setup_kernel(k) * (gain * (factor ** 2))
+  p = (k.shape[0] - factor) - (conv_w - 1)
+  return k, (p + 1) // 2 + factor - 1
+
+
+def _upconv_lib(x, w, taps):
+  lib = _backend.get()
+  _backend.check(x, lib)
+  if not getattr(lib, 'has_upconv', False):
+    raise NotImplementedError(f'backend {lib.backend} does not export include/stk_upconv.h: no kernel computes the '
+                              f'FIR-upsampling convolution (upsample_conv_2d)')
+  N, Cin, H, W = x.shape
+  dims = (N, H, W, Cin, w.shape[0], w.shape[2], taps.shape[0])
+  if int(lib.upconv2d_ws_bytes(0, *dims)) < 0:
+    raise NotImplementedError(f'include/stk_upconv.h takes 1x1 / 3x3 weights and FIR kernels of up to 4 taps, got weight '
+                              f'{tuple(w.shape)}, taps {tuple(taps.shape)}')
+  return lib, dims
+
+
+def _upconv_ws(lib, direction, dims, device):
+  nb = int(lib.upconv2d_ws_bytes(direction, *dims))
+  return torch.empty(max(nb // 4, 64), dtype=torch.float32, device=device), nb
+
+
+class _UpConv2d(torch.autograd.Function):
+  """upfirdn2d(conv_transpose2d(x, flip(w), stride 2), taps) on the C-ABI kernels of include/stk_upconv.h (forward, data
+  gradient, weight gradient); the tensor-level counterpart of engine.graph.UpConv.  First order only."""
+
+  @staticmethod
+  def forward(ctx, x, w, taps, pad0):
+    lib, dims = _upconv_lib(x, w, taps)
+    x, w, taps = x.contiguous(), w.contiguous(), taps.contiguous()
+    y = torch.empty((dims[0], dims[4], 2 * dims[1], 2 * dims[2]), dtype=x.dtype, device=x.device)
+    ws, nb = _upconv_ws(lib, 0, dims, x.device)
+    with stk_lib.device_guard(x.device):
+      lib.upconv2d_fwd_f32(x.data_ptr(), w.data_ptr(), taps.data_ptr(), None, None, 1.0, y.data_ptr(), *dims, pad0,
+                           ws.data_ptr(), nb, stk_lib.stream_ptr(x.device))
+    ctx.save_for_backward(x, w, taps)
+    ctx.dims, ctx.pad0 = dims, pad0
+    return y
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, gy):
+    lib = _backend.get()
+    x, w, taps = ctx.saved_tensors
+    gy = gy.contiguous()
+    dims, pad0 = ctx.dims, ctx.pad0
+    N, H, W, _, Cout, K, _ = dims
+    gx = gw = None
+    du = torch.empty((N, Cout, 2 * H - 2 + K, 2 * W - 2 + K), dtype=x.dtype, device=x.device)
+    have_du = 0
+    with stk_lib.device_guard(x.device):
+      stream = stk_lib.stream_ptr(x.device)
+      if ctx.needs_input_grad[0]:
+        gx = torch.empty_like(x)
+        lib.upconv2d_dgrad_f32(gy.data_ptr(), w.data_ptr(), taps.data_ptr(), du.data_ptr(), 0, gx.data_ptr(), 0.0, 1.0,
+                               *dims, pad0, stream)
+        have_du = 1
+      if ctx.needs_input_grad[1]:
+        gw = torch.zeros_like(w)
+        ws, nb = _upconv_ws(lib, 2, dims, x.device)
+        lib.upconv2d_wgrad_f32(x.data_ptr(), gy.data_ptr(), taps.data_ptr(), du.data_ptr(), have_du, gw.data_ptr(), 1.0,
+                               *dims, pad0, ws.data_ptr(), nb, stream)
+    return gx, gw, None, None
+
+
 def upsample_conv_2d(x, w, k=None, factor=2, gain=1):
-  raise NotImplementedError('upsample_conv_2d is dead code in the reference '
-                            '(models/up_or_down_sampling.py:126 raises); not provided')
+  """Fused ``upsample_2d`` + ``conv2d`` (models/up_or_down_sampling.py:72-141): the transposed convolution of x with w at
+  stride `factor` (w flipped in both spatial axes), then the FIR filter k with padding ((p+1)//2 + factor - 1, p//2 + 1),
+  p = (len(k) - factor) - (conv_w - 1).  x [N, C, H, W], w [Cout, C, kh, kw] (kh == kw, odd) -> [N, Cout, H factor, W factor].
+  Differentiable in x and w (first order).  Factor 2 and ungrouped weights only."""
+  assert isinstance(factor, int) and factor >= 1
+  assert len(w.shape) == 4
+  _, in_c, conv_h, conv_w = w.shape
+  assert conv_w == conv_h
+  if factor != 2:
+    raise NotImplementedError(f'upsample_conv_2d: the kernels implement factor 2 (the one every config uses), got {factor}')
+  if x.shape[1] != in_c:
+    raise NotImplementedError(f'upsample_conv_2d: grouped weights are not implemented (x has {x.shape[1]} channels, w '
+                              f'takes {in_c})')
+  taps, pad0 = _conv_up_taps(k, factor, gain, conv_w)
+  return _UpConv2d.apply(x, w, torch.tensor(taps, device=x.device), pad0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -222,7 +308,9 @@ class Conv2d(layers.EagerBlock, nn.Module):
   def emit(self, g, x, res=None, out_div=1.0, name='uds_conv'):
     bias = self.bias if self.use_bias else None
     if self.up:
-      raise NotImplementedError('Conv2d(up=True) goes through upsample_conv_2d, which is dead in the reference')
+      # upsample_conv_2d (:72-141): stride-2 transposed convolution, then the FIR with pad ((p+1)//2 + 1, p//2 + 1)
+      taps, pad0 = _conv_up_taps(self.resample_kernel, 2, 1, self.kernel)
+      return g.add(G.UpConv(g, x, g.param(self.weight), g.param(bias), taps, pad0, res=res, out_div=out_div, name=name))
     if self.down:
       # conv_downsample_2d (:144-178): FIR with pad ((p+1)//2, p//2) then stride-2 conv, padding 0
       taps, pad = _conv_down_taps(self.resample_kernel, 2, 1, self.kernel)
