@@ -17,10 +17,10 @@ from . import op
 from .models import utils as _mutils  # noqa: F401
 from .models import ema, layers, layerspp, ncsnpp, up_or_down_sampling  # noqa: F401
 from . import models
-from . import likelihood, losses, sampling, sampling_lib, utils
+from . import controllable_generation, likelihood, losses, sampling, sampling_lib, utils
 
 __all__ = ['configs', 'datasets', 'sde_lib', 'op', 'models', 'likelihood', 'losses', 'sampling', 'sampling_lib', 'utils',
-           'install']
+           'controllable_generation', 'install']
 
 # name the reference's modules import under -> our module
 _REFERENCE_NAMES = {
@@ -28,6 +28,7 @@ _REFERENCE_NAMES = {
   'losses': losses,
   'likelihood': likelihood,
   'sampling': sampling,
+  'controllable_generation': controllable_generation,   # score_sde's name; the reference's fork has no such module
   'utils': utils,
   'op': op,
   'models': models,
