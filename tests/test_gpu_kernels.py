@@ -443,21 +443,21 @@ def test_conv(ref_lib, hip_lib, case, scratch):
     shape = (C1, C2, N, H, W, Cout, K, K, stride, pad)
     fb = max(int(lib.conv2d_fwd_ws_bytes(*shape)), int(lib.conv2d_dgrad_ws_bytes(*shape))) if scratch else 0
     fws = to(torch.zeros(fb // 4 + 64)) if fb else None
-    y = to(torch.zeros(N, Cout, OH, OW))
+    y = to(torch.full((N, Cout, OH, OW), float('nan')))      # overwritten, never read: starts as NaN
     call(lib, 'conv2d_fwd_f32', a1, C1, a2, C2, ww, layout, to(bias), tp, TS if use_temb else 0, to(res), div, y, *dims,
          fws, fb)
     o['y'] = y
-    y2 = to(torch.zeros(N, Cout, OH, OW))
+    y2 = to(torch.full((N, Cout, OH, OW), float('nan')))
     call(lib, 'conv2d_fwd_f32', a1, C1, a2, C2, ww, layout, None, None, 0, None, 1.0, y2, *dims, fws, fb)
     o['y_plain'] = y2
     d = to(dy)
-    dx1, dx2 = to(g1.clone()), (to(g2.clone()) if C2 else None)
+    dx1, dx2 = to(torch.full_like(g1, float('nan'))), (to(g2.clone()) if C2 else None)      # beta1 == 0: dx1 is not read
     call(lib, 'conv2d_dgrad_f32', d, ww, layout, dx1, C1, 0.0, dx2, C2, 1.0, 0.5, *dims, fws, fb)
     o['dx1'] = dx1
     if C2:
       o['dx2'] = dx2
     nbytes = int(lib.conv2d_wgrad_ws_bytes(C1, C2, N, Cout, OH, OW, K, K))
-    ws = to(torch.zeros(max(nbytes // 4, N * Cout, 64)))
+    ws = to(torch.full((max(nbytes // 4, N * Cout, 64),), float('nan')))
     dw = to(dw0.clone())
     call(lib, 'conv2d_wgrad_f32', a1, C1, a2, C2, d, dw, layout, 0.5, ws, ws.numel() * 4, *dims)
     o['dw'] = dw
@@ -751,7 +751,13 @@ def test_gemm(ref_lib, hip_lib, case):
     ct = to(C0.transpose(1, 2).contiguous().clone())     # transposed output (scm = 1)
     call(lib, 'gemm_f32', to(A), sam, sak, M * K, to(B), sbk, sbn, N * K, ct, 1, M, M * N, to(bias), bias_mode,
          M, N, K, batch, 0.75, beta)
-    return {'c': c, 'ct': ct}
+    c0 = to(torch.full_like(C0, float('nan')))            # beta == 0: C is overwritten, never read
+    call(lib, 'gemm_f32', to(A), sam, sak, M * K, to(B), sbk, sbn, N * K, c0, N, 1, M * N, to(bias), bias_mode,
+         M, N, K, batch, 0.75, 0.0)
+    ct0 = to(torch.full((batch, N, M), float('nan')))
+    call(lib, 'gemm_f32', to(A), sam, sak, M * K, to(B), sbk, sbn, N * K, ct0, 1, M, M * N, to(bias), bias_mode,
+         M, N, K, batch, 0.75, 0.0)
+    return {'c': c, 'ct': ct, 'c_beta0': c0, 'ct_beta0': ct0}
 
   compare(both(ref_lib, hip_lib, fn), 1e-4, 'gemm')
 
@@ -801,7 +807,9 @@ def test_attention(ref_lib, hip_lib, case, stacked):
   bs = 3 * C * T if stacked else C * T
 
   def fn(lib, to):
-    o, lse, rec, delta = to(torch.zeros(B, C, T)), to(torch.zeros(B, T)), to(torch.zeros(1024)), to(torch.zeros(B, T))
+    nan = float('nan')        # o, lse (forward) and delta (backward) are written before they are read
+    o, lse, delta = to(torch.full((B, C, T), nan)), to(torch.full((B, T), nan)), to(torch.full((B, T), nan))
+    rec = to(torch.zeros(1024))
     if stacked:
       qkv, g = to(torch.cat([q, k, v], 1)), to(torch.cat(g0, 1))
       ins = [qkv[0, i * C:].data_ptr() for i in range(3)]

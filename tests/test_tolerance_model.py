@@ -12,7 +12,8 @@ the split itself loses; fp32 accumulation on the device adds to it, which is wha
 import numpy as np
 import pytest
 
-from _tolerances import PL_DGRAD_RTOL, PL_FWD_RTOL, PL_WGRAD_RTOL
+from _tolerances import (F32_DGRAD_RTOL, F32_FWD_RTOL, F32_GEMM_RTOL, F32_WGRAD_RTOL, PL_DGRAD_RTOL, PL_FWD_RTOL,
+                         PL_WGRAD_RTOL)
 
 
 def _split(a):
@@ -95,3 +96,89 @@ def test_model_split_is_the_library_format():
   assert s == 2.0 ** 11 and np.abs(hi).max() == 2.0 ** 13
   xs = x.astype(np.float64) * s
   assert np.all(np.abs(hi + lo - xs) <= np.maximum(np.abs(xs) * 2.0 ** -22, 2.0 ** -25))
+
+
+# ---- the f32-operand contractions (F32_* bounds) ----------------------------------------------------------------------
+# The f32-input MFMA kernels, wgrad9_kernel and stk_gemm_f32 multiply plain fp32 values and accumulate in fp32, one k chunk
+# (36 wide for the 3x3 layers: 4 channels x 9 taps; 32 wide otherwise) after the other; a K split leaves one partial slab
+# per split, and splitk_reduce_kernel sums the slabs in fp32 in ascending order.  The model: fp32 products, summed in fp32
+# in k order inside a chunk, the chunk sums added in fp32 to the slab's accumulator, the slabs added in fp32.  It models
+# how much rounding such an order collects, not the matrix core's exact order inside an instruction.
+def _round_bits(a, bits):
+  """a rounded to `bits` significant bits (round to nearest), exponent range untouched"""
+  m, e = np.frexp(a.astype(np.float64))
+  return np.ldexp(np.round(m * 2.0 ** bits) / 2.0 ** bits, e).astype(np.float32)
+
+
+def _f32_slabs(w, x, kc, slabs):
+  """[slab, M, N] fp32 partial sums of w @ x; a slab is a whole number of k chunks, as the device plans split K"""
+  K = w.shape[1]
+  chunks = -(-K // kc)
+  per = -(-chunks // slabs) * kc
+  out = []
+  for s0 in range(0, K, per):
+    acc = np.zeros((w.shape[0], x.shape[1]), np.float32)
+    for k0 in range(s0, min(s0 + per, K), kc):
+      part = np.zeros_like(acc)
+      for k in range(k0, min(k0 + kc, s0 + per, K)):
+        part += w[:, k, None] * x[None, k, :]
+      acc += part
+    out.append(acc)
+  assert len(out) == slabs, (len(out), slabs)
+  return np.stack(out)
+
+
+def _f32_sum(slabs):
+  acc = np.zeros_like(slabs[0])
+  for s in slabs:
+    acc += s
+  return acc
+
+
+def _f32_model(w, x, kc, slabs):
+  ref = w.astype(np.float64) @ x.astype(np.float64)
+  part = _f32_slabs(w, x, kc, slabs)
+  variants = {'correct': _f32_sum(part),
+              'operands at 11 bits': _f32_sum(_f32_slabs(_round_bits(w, 11), _round_bits(x, 11), kc, slabs))}
+  if w.shape[1] % kc:
+    variants['last k of the ragged chunk dropped'] = _f32_sum(_f32_slabs(w[:, :-1], x[:-1], kc, slabs))
+  if slabs > 1:
+    variants['slab dropped'] = _f32_sum(part[:-1])
+    variants['slab counted twice'] = _f32_sum(np.concatenate([part, part[-1:]]))
+  scale = np.abs(ref).max()
+  return {k: float(np.abs(v.astype(np.float64) - ref).max() / scale) for k, v in variants.items()}
+
+
+# (bound, accumulation length K, k chunk, K-split slabs): the lengths of the cases of tests/test_gpu_f32_contractions.py
+F32_MODEL_CASES = [
+  ('fwd', F32_FWD_RTOL, 27, 36, 1),          # 3 -> 48 at stride 2
+  ('fwd', F32_FWD_RTOL, 207, 36, 1),         # 23 -> 128
+  ('fwd', F32_FWD_RTOL, 4608, 36, 1),        # 512 -> 32
+  ('dgrad', F32_DGRAD_RTOL, 27, 36, 1),
+  ('dgrad', F32_DGRAD_RTOL, 207, 36, 1),
+  ('dgrad', F32_DGRAD_RTOL, 4608, 36, 1),
+  ('gemm', F32_GEMM_RTOL, 33, 32, 1),
+  ('gemm', F32_GEMM_RTOL, 512, 32, 1),
+  ('wgrad', F32_WGRAD_RTOL, 8 * 1024, 32, 16),   # wgrad9_kernel<32>: K = N OH OW = 8192 in 16 slabs
+  ('wgrad', F32_WGRAD_RTOL, 19 * 256, 32, 9),    # wgrad9_kernel<16>: 4864 in 9 slabs, the last short
+  ('wgrad', F32_WGRAD_RTOL, 32 * 64, 32, 4),     # wgrad9_kernel<8>
+  ('wgrad', F32_WGRAD_RTOL, 15 * 144, 32, 4),    # 128-wide generic kernel: 2160, not a multiple of the chunk
+]
+
+
+@pytest.mark.parametrize('case', F32_MODEL_CASES, ids=lambda c: f'{c[0]}_K{c[2]}_kc{c[3]}_s{c[4]}')
+def test_f32_bound_separates_correct_accumulation_from_mutations(case):
+  """Each F32_* bound sits between fp32 accumulation done right (<= 1/3 of it) and what a kernel could plausibly get
+  wrong (>= 5x): the last element of a ragged K lost, a K-split slab not summed or summed twice, operands that went
+  through a half-precision mantissa.  Loosening a bound to the old 1e-4 fails here, without a GPU."""
+  what, bound, K, kc, slabs = case
+  rng = np.random.default_rng(K + slabs)
+  M, Nc = 48, 40
+  w = rng.standard_normal((M, K)).astype(np.float32) / np.float32(np.sqrt(K))
+  x = rng.standard_normal((K, Nc)).astype(np.float32)
+  err = _f32_model(w, x, kc, slabs)
+  print(what, K, {k: f'{v:.2e}' for k, v in err.items()})
+  assert err['correct'] <= bound / 3, (err['correct'], bound)
+  for k, v in err.items():
+    if k != 'correct':
+      assert v >= 5 * bound, (k, v, bound)
