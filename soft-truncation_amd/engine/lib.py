@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
-include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h, include/stk_upconv.h and include/stk_impute.h).
+include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h, include/stk_upconv.h, include/stk_impute.h and include/stk_solver.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -155,6 +155,11 @@ _RESTYPE_UPCONV = {'stk_upconv2d_ws_bytes': c_long}
 SIGNATURES_IMPUTE = {
   'stk_impute_f32': [P, P, P, P, P, P, P, P, P, P, I, I, L, I, I, S],
 }
+# include/stk_solver.h: the update of the DPM-Solver++ samplers.  Bound like SIGNATURES_FP16, when present;
+# `StkLib.has_solver` says whether it is (dpm_solver refuses to build a sampler without it).
+SIGNATURES_SOLVER = {
+  'stk_dpm_update_f32': [P, P, P, F, F, F, F, F, F, F, P, P, L, S],
+}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -196,6 +201,7 @@ class StkLib:
     self.has_upconv = self._bind_optional(SIGNATURES_UPCONV, 'include/stk_upconv.h', restype=_RESTYPE_UPCONV,
                                           unchecked=set(_RESTYPE_UPCONV))
     self.has_impute = self._bind_optional(SIGNATURES_IMPUTE, 'include/stk_impute.h')
+    self.has_solver = self._bind_optional(SIGNATURES_SOLVER, 'include/stk_solver.h')
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 

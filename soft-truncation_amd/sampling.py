@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import sde_lib
+from . import dpm_solver, sde_lib
 from .engine import rk45
 from .models import utils as mutils
 from .models.utils import from_flattened_numpy, get_score_fn, to_flattened_numpy
@@ -304,7 +304,8 @@ def _denoiser(config, sde, probability_flow):
 
 
 def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
-  """``sampling_fn(model) -> (samples, nfe)`` for ``config.sampling.method`` (sampling.py:80-125)."""
+  """``sampling_fn(model) -> (samples, nfe)`` for ``config.sampling.method`` (sampling.py:80-125): 'pc', 'ode', or
+  'dpm_solver' (dpm_solver.py; its options are ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip``)."""
   s = config.sampling
   kind = s.method.lower()
   precision = mutils.sampling_precision(config)
@@ -321,6 +322,11 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
                           n_steps=s.n_steps_each, probability_flow=s.probability_flow,
                           continuous=config.training.continuous, denoise=s.noise_removal, eps=eps,
                           device=config.device, precision=precision)
+  if kind == 'dpm_solver':
+    steps, order, skip, clip = dpm_solver.sampling_options(config)
+    return dpm_solver.get_dpm_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=steps,
+                                      order=order, skip=skip, denoise=s.noise_removal, clip=clip, eps=eps,
+                                      device=config.device, precision=precision)
   raise ValueError(f"Sampler name {s.method} unknown.")
 
 
