@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
-include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h, include/stk_upconv.h, include/stk_impute.h and include/stk_solver.h).
+include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h, include/stk_upconv.h, include/stk_impute.h, include/stk_solver.h and include/stk_adaptive.h).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -160,6 +160,15 @@ SIGNATURES_IMPUTE = {
 SIGNATURES_SOLVER = {
   'stk_dpm_update_f32': [P, P, P, F, F, F, F, F, F, F, P, P, L, S],
 }
+# include/stk_adaptive.h: the three passes of the adaptive-step SDE sampler.  Bound like SIGNATURES_FP16, when present;
+# `StkLib.has_adaptive` says whether they are (adaptive_sde refuses to build a sampler without them).  _ws_bytes is a query.
+SIGNATURES_ADAPTIVE = {
+  'stk_sde_ws_bytes': [I, L],
+  'stk_sde_stage_f32': [P, P, P, P, P, P, I, L, S],
+  'stk_sde_heun_error_f32': [P, P, P, P, P, P, F, F, P, P, L, I, L, S],
+  'stk_sde_commit_f32': [P, P, P, P, P, P, F, F, F, P, L, P, P, P, P, I, L, S],
+}
+_RESTYPE_ADAPTIVE = {'stk_sde_ws_bytes': c_long}
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
@@ -202,6 +211,8 @@ class StkLib:
                                           unchecked=set(_RESTYPE_UPCONV))
     self.has_impute = self._bind_optional(SIGNATURES_IMPUTE, 'include/stk_impute.h')
     self.has_solver = self._bind_optional(SIGNATURES_SOLVER, 'include/stk_solver.h')
+    self.has_adaptive = self._bind_optional(SIGNATURES_ADAPTIVE, 'include/stk_adaptive.h', restype=_RESTYPE_ADAPTIVE,
+                                            unchecked=set(_RESTYPE_ADAPTIVE))
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import dpm_solver, sde_lib
+from . import adaptive_sde, dpm_solver, sde_lib
 from .engine import rk45
 from .models import utils as mutils
 from .models.utils import from_flattened_numpy, get_score_fn, to_flattened_numpy
@@ -305,7 +305,8 @@ def _denoiser(config, sde, probability_flow):
 
 def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   """``sampling_fn(model) -> (samples, nfe)`` for ``config.sampling.method`` (sampling.py:80-125): 'pc', 'ode', or
-  'dpm_solver' (dpm_solver.py; its options are ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip``)."""
+  'dpm_solver' (dpm_solver.py; its options are ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip``) or 'adaptive'
+  (adaptive_sde.py; ``config.sampling.adaptive_rtol / adaptive_atol / adaptive_h_init / adaptive_safety / adaptive_exponent``)."""
   s = config.sampling
   kind = s.method.lower()
   precision = mutils.sampling_precision(config)
@@ -327,6 +328,11 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
     return dpm_solver.get_dpm_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=steps,
                                       order=order, skip=skip, denoise=s.noise_removal, clip=clip, eps=eps,
                                       device=config.device, precision=precision)
+  if kind == 'adaptive':
+    rtol, atol, h_init, safety, exponent = adaptive_sde.sampling_options(config)
+    return adaptive_sde.get_adaptive_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, rtol=rtol,
+                                             atol=atol, h_init=h_init, safety=safety, exponent=exponent,
+                                             denoise=s.noise_removal, eps=eps, device=config.device, precision=precision)
   raise ValueError(f"Sampler name {s.method} unknown.")
 
 
