@@ -38,7 +38,6 @@ import torch
 from . import sde_lib
 from .engine import lib as stk_lib
 from .models import utils as mutils
-from .op import _backend
 
 RTOL = 0.01
 ATOL_CENTERED, ATOL_UNCENTERED = 0.0078, 0.0039          # 2 / 256 for data in [-1, 1], 1 / 256 for data in [0, 1]
@@ -47,11 +46,8 @@ MAX_ITERS = 10000
 
 
 def _library():
-  lib = _backend.get()
-  if not lib.has_adaptive:
-    raise NotImplementedError(f'{lib.path} ({lib.backend}) does not implement include/stk_adaptive.h: the adaptive SDE sampler '
-                              f'needs stk_sde_stage_f32, stk_sde_heun_error_f32 and stk_sde_commit_f32 (there is no other path)')
-  return lib
+  return mutils.require('has_adaptive', 'stk_adaptive.h', 'stk_sde_stage_f32, stk_sde_heun_error_f32 and stk_sde_commit_f32',
+                        'the adaptive SDE sampler needs')
 
 
 def default_atol(config):
@@ -114,9 +110,7 @@ def adaptive_sample(score_fn, x, sde, rtol=RTOL, atol=ATOL_CENTERED, h_init=H_IN
   (their sum is below `iterations` for a sample that finished early), ``info['E']`` the error norms of the last iteration.
   RuntimeError when some sample has not reached `eps` after `max_iters` iterations."""
   lib = _library()
-  _backend.check(x, lib)
-  if x.dtype != torch.float32 or not x.is_contiguous():
-    raise ValueError(f'x must be a contiguous float32 tensor (it is updated in place), got {x.dtype}, strides {x.stride()}')
+  mutils.check_inplace_state(x, lib)
   eps, T = float(np.float32(eps)), float(np.float32(sde.T))
   _check_options(rtol, atol, h_init, safety, exponent, eps, T, max_iters)
   B, dev = x.shape[0], x.device
@@ -137,12 +131,12 @@ def adaptive_sample(score_fn, x, sde, rtol=RTOL, atol=ATOL_CENTERED, h_init=H_IN
     if iterations >= max_iters:
       raise RuntimeError(f'the adaptive sampler has not reached eps = {eps!r} after max_iters = {max_iters} iterations')
     z = torch.randn_like(x)
-    s1 = _score(score_fn, x, t, lib)
+    s1 = mutils.checked_score(score_fn, x, t, lib)
     t_next = next_time(t, h, eps)
     with stk_lib.device_guard(dev):
       lib.sde_stage_f32(x.data_ptr(), None, s1.data_ptr(), z.data_ptr(), stage_rows(sde, t, h).data_ptr(), x1.data_ptr(), B, n,
                         stream)
-    s2 = _score(score_fn, x1, t_next, lib)
+    s2 = mutils.checked_score(score_fn, x1, t_next, lib)
     with stk_lib.device_guard(dev):
       lib.sde_heun_error_f32(x.data_ptr(), x1.data_ptr(), x1_prev.data_ptr(), s2.data_ptr(), z.data_ptr(),
                              heun_rows(sde, t_next, h).data_ptr(), atol, rtol, x2.data_ptr(), ws.data_ptr(), ws_bytes, B, n,
@@ -157,14 +151,6 @@ def adaptive_sample(score_fn, x, sde, rtol=RTOL, atol=ATOL_CENTERED, h_init=H_IN
   return x, iterations, dict(accepted=accepted, rejected=rejected, E=E, t=t)
 
 
-def _score(score_fn, x, t, lib):
-  score = score_fn(x, t)
-  _backend.check(score, lib)
-  if score.shape != x.shape or score.dtype != torch.float32:
-    raise ValueError(f'score_fn returned {score.dtype} {tuple(score.shape)} for a float32 state {tuple(x.shape)}')
-  return score.contiguous()
-
-
 def get_adaptive_sampler(config, sde, shape, inverse_scaler, rtol=RTOL, atol=None, h_init=H_INIT, safety=SAFETY,
                          exponent=EXPONENT, denoise=True, eps=1e-3, device='cuda', precision='fp32', max_iters=MAX_ITERS):
   """``adaptive_sampler(model) -> (samples, nfe)`` with ``nfe = 2 iterations (+ 1 with denoise)``: the adaptive-step sampler
@@ -175,15 +161,12 @@ def get_adaptive_sampler(config, sde, shape, inverse_scaler, rtol=RTOL, atol=Non
   lib = _library()
   atol = default_atol(config) if atol is None else atol
   _check_options(rtol, atol, h_init, safety, exponent, float(np.float32(eps)), float(np.float32(sde.T)), max_iters)
-  if precision not in mutils.PRECISIONS:
-    raise ValueError(f'precision must be one of {mutils.PRECISIONS}, got {precision!r}')
+  mutils.check_precision(precision)
   denoise_update_fn = sampling._denoiser(config, sde, probability_flow=True)
 
   def adaptive_sampler(model):
-    with torch.no_grad(), mutils.frozen_weights(model), mutils.precision(model, precision):
-      score_fn = mutils.get_score_fn(config, sde, model, train=False, continuous=config.training.continuous)
-      x = sde.prior_sampling(shape).to(device).contiguous()
-      _backend.check(x, lib)
+    with mutils.sampling_run(model, precision):
+      score_fn, x = mutils.score_and_prior(config, sde, model, shape, device, lib)
       x, iterations, _ = adaptive_sample(score_fn, x, sde, rtol=rtol, atol=atol, h_init=h_init, safety=safety,
                                          exponent=exponent, eps=eps, max_iters=max_iters)
       if denoise:
@@ -197,10 +180,6 @@ def sampling_options(config):
   """(rtol, atol, h_init, safety, exponent) of ``config.sampling.adaptive_rtol / adaptive_atol / adaptive_h_init /
   adaptive_safety / adaptive_exponent``: the paper's 0.01, 0.0078 (centered data) or 0.0039, 0.01, 0.9 and 0.9 where a key is
   absent (the reference's configs have none)."""
-  def read(key, default):
-    try:
-      return getattr(config.sampling, key)
-    except (AttributeError, KeyError):
-      return default
+  read = lambda key, default: mutils.config_option(config, 'sampling', key, default)
   return (read('adaptive_rtol', RTOL), read('adaptive_atol', default_atol(config)), read('adaptive_h_init', H_INIT),
           read('adaptive_safety', SAFETY), read('adaptive_exponent', EXPONENT))

@@ -22,7 +22,6 @@ the imputation is always fp32).  Everything runs on the device: host tensors rai
 no CPU path; a library without include/stk_impute.h is refused when the sampler is built.
 """
 import ctypes
-import functools
 
 import numpy as np
 import torch
@@ -30,7 +29,7 @@ import torch
 from .engine import lib as stk_lib
 from .models import utils as mutils
 from .op import _backend
-from .sampling import shared_corrector_update_fn, shared_predictor_update_fn, tqdm
+from .sampling import pc_updates, tqdm
 
 # upstream's decoupling matrix: orthogonal, its first column the gray axis (1, 1, 1) / sqrt(3)
 M = torch.tensor([[5.7735014e-01, -8.1649649e-01, 4.7008697e-08],
@@ -53,11 +52,7 @@ _MIX_COUPLE = (_C_INV_M, _C_I)
 
 
 def _library():
-  lib = _backend.get()
-  if not lib.has_impute:
-    raise NotImplementedError(f'{lib.path} ({lib.backend}) does not implement include/stk_impute.h: the inpainting and '
-                              f'colourisation samplers need stk_impute_f32 (there is no other path)')
-  return lib
+  return mutils.require('has_impute', 'stk_impute.h', 'stk_impute_f32', 'the inpainting and colourisation samplers need')
 
 
 def mask_form(mask, data):
@@ -197,19 +192,11 @@ def colorize_update(update_fn, sde, model, gray, x, t):
     return _half_step(lib, update_fn, sde, model, gray.contiguous(), get_mask(gray[:1]), (1, 3), x, t, _MIX_BLEND)
 
 
-def _updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous):
-  predict = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
-                              probability_flow=probability_flow, continuous=continuous, config=config)
-  correct = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
-                              n_steps=n_steps, config=config)
-  return predict, correct
-
-
 def _run(config, sde, lib, model, data, mask, form, mix, updates, inverse_scaler, denoise, eps):
   """The loop both samplers share.  The first launch is the initialisation: a = 1 and no noise give
   data mask + prior (1 - mask), in the decoupled space when `mix` is given."""
   predict, correct = updates
-  with torch.no_grad(), mutils.frozen_weights(model), mutils.precision(model, mutils.sampling_precision(config)):
+  with mutils.sampling_run(model, mutils.sampling_precision(config)):
     prior = sde.prior_sampling(data.shape).to(data.device).contiguous()
     one = _ones(data)
     x = x_mean = _impute(lib, prior, data, None, mask, form, one, one, prior, None, mix)
@@ -226,7 +213,7 @@ def get_pc_inpainter(config, sde, predictor, corrector, inverse_scaler, snr, n_s
   """``pc_inpainter(model, data, mask)``: PC sampling of the part of `data` [N,C,H,W] where `mask` is 0, given the part where
   it is 1 (a float32 mask in [0, 1] that broadcasts over batch and channels; fractional values blend)."""
   lib = _library()
-  updates = _updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
+  updates = pc_updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
   mutils.sampling_precision(config)            # a bad config.sampling.precision fails here, not in the loop
 
   def pc_inpainter(model, data, mask):
@@ -243,7 +230,7 @@ def get_pc_colorizer(config, sde, predictor, corrector, inverse_scaler, snr, n_s
                      continuous=False, denoise=True, eps=1e-5):
   """``pc_colorizer(model, gray_scale_img)``: PC sampling of the colour of a gray image given as [N,3,H,W]."""
   lib = _library()
-  updates = _updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
+  updates = pc_updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
   mutils.sampling_precision(config)
 
   def pc_colorizer(model, gray_scale_img):

@@ -1,8 +1,8 @@
 // adaptive.hip -- the three passes of the adaptive-step SDE sampler (include/stk_adaptive.h, gfx950).
 //
 // All three stream over the [B, n] state once -- stage reads 3-4 and writes 1 tensor, heun_error reads 5 and writes 1, commit
-// reads 2 and writes 2 for the accepted rows only: HBM-bound, laid out like solver.hip: lanes walk consecutive addresses,
-// 16 B per lane whenever n is a multiple of 4 and every pointer given is 16-byte aligned, a scalar path otherwise.
+// reads 2 and writes 2 for the accepted rows only: HBM-bound, and laid out as stream.h describes, the 16-byte path taken
+// whenever n is a multiple of 4 (an item never leaves its row).
 //
 // The grid is two-dimensional because everything here is per sample: blockIdx.y walks the samples (striding when B exceeds
 // the grid), blockIdx.x is one of the `parts` blocks that share a row and stride along it.  parts x rows is stk_ew_grid's
@@ -11,27 +11,13 @@
 // the entries), so the index arithmetic is 32-bit.
 //
 // No fused multiply-add in this file (header, "Arithmetic"): the pragma below holds for every function that follows.
-#include "common.h"
+// stream.h, included before it, holds loads, stores and host code only.
+#include "stream.h"
 #include "stk_adaptive.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-template <int V> struct Vec;
-template <> struct Vec<1> {
-  float v[1];
-  __device__ static Vec load(const float* p, unsigned i) { Vec r; r.v[0] = p[i]; return r; }
-  __device__ void store(float* p, unsigned i) const { p[i] = v[0]; }
-};
-template <> struct Vec<4> {
-  float v[4];
-  __device__ static Vec load(const float* p, unsigned i) {
-    float4 t = reinterpret_cast<const float4*>(p)[i];
-    Vec r; r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w; return r;
-  }
-  __device__ void store(float* p, unsigned i) const { reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]); }
-};
 
 // Blocks that share one row, and rows walked at once: functions of (B, n) alone.
 int sde_rows(int B, long n) {
@@ -198,16 +184,11 @@ extern "C" int stk_sde_stage_f32(const float* x, const float* xp, const float* s
   if (!x || !score || !z || !coef || !out) return STK_EINVAL;
   const int rc = check_sizes(B, n);
   if (rc != STK_OK) return rc;
-  const bool vec = (n & 3) == 0 && stk_aligned16(x) && stk_aligned16(score) && stk_aligned16(z) && stk_aligned16(out) &&
-                   (!xp || stk_aligned16(xp));
+  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, z, out, xp);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
   const dim3 grid(sde_parts(B, n), sde_rows(B, n));
   StageArgs a{x, xp, score, z, coef, out};
-  hipStream_t st = (hipStream_t)stream;
-  if (vec) hipLaunchKernelGGL(sde_stage_kernel<4>, grid, dim3(256), 0, st, row, B, a);
-  else hipLaunchKernelGGL(sde_stage_kernel<1>, grid, dim3(256), 0, st, row, B, a);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  return stk_launch_vec(vec, sde_stage_kernel<4>, sde_stage_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }
 
 extern "C" int stk_sde_heun_error_f32(const float* x, const float* x1, const float* x1_prev, const float* score2,
@@ -218,16 +199,11 @@ extern "C" int stk_sde_heun_error_f32(const float* x, const float* x1, const flo
   const int rc = check_sizes(B, n);
   if (rc != STK_OK) return rc;
   if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
-  const bool vec = (n & 3) == 0 && stk_aligned16(x) && stk_aligned16(x1) && stk_aligned16(x1_prev) && stk_aligned16(score2) &&
-                   stk_aligned16(z) && stk_aligned16(x2);
+  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1, x1_prev, score2, z, x2);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
   const dim3 grid(sde_parts(B, n), sde_rows(B, n));
   HeunArgs a{x, x1, x1_prev, score2, z, coef, x2, (double*)ws, atol, rtol};
-  hipStream_t st = (hipStream_t)stream;
-  if (vec) hipLaunchKernelGGL(sde_heun_error_kernel<4>, grid, dim3(256), 0, st, row, B, a);
-  else hipLaunchKernelGGL(sde_heun_error_kernel<1>, grid, dim3(256), 0, st, row, B, a);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  return stk_launch_vec(vec, sde_heun_error_kernel<4>, sde_heun_error_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }
 
 extern "C" int stk_sde_commit_f32(float* x, float* x1_prev, const float* x2, const float* x1, const float* t, const float* h,
@@ -239,13 +215,9 @@ extern "C" int stk_sde_commit_f32(float* x, float* x1_prev, const float* x2, con
   const int rc = check_sizes(B, n);
   if (rc != STK_OK) return rc;
   if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
-  const bool vec = (n & 3) == 0 && stk_aligned16(x) && stk_aligned16(x1_prev) && stk_aligned16(x2) && stk_aligned16(x1);
+  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1_prev, x2, x1);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
   const dim3 grid(sde_parts(B, n), sde_rows(B, n));
   CommitArgs a{x, x1_prev, x2, x1, t, h, (const double*)ws, t_out, h_out, E_out, accept_out, eps, safety, exponent, (double)n};
-  hipStream_t st = (hipStream_t)stream;
-  if (vec) hipLaunchKernelGGL(sde_commit_kernel<4>, grid, dim3(256), 0, st, row, B, a);
-  else hipLaunchKernelGGL(sde_commit_kernel<1>, grid, dim3(256), 0, st, row, B, a);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  return stk_launch_vec(vec, sde_commit_kernel<4>, sde_commit_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }

@@ -1,11 +1,9 @@
 // elementwise.hip -- HBM-bound element-wise kernels of libstk (gfx950).
 //
-// All of them are pure streaming passes, so the only rules that matter are coalescing and width:
-// lanes walk consecutive addresses, 16 B per lane (float4) whenever every pointer is 16-byte
-// aligned and the length is a multiple of 4 (true for every buffer the engine plans: offsets are
-// 256 B aligned and H*W is a multiple of 16), with a scalar path otherwise; grids are capped at
-// 8 blocks per CU and grid-stride the rest.
-#include "common.h"
+// All of them are pure streaming passes, so the only rules that matter are coalescing and width: the layout, Vec<V>
+// and the launch of the 16-byte / scalar pair are stream.h's.  The 16-byte condition holds for every buffer the engine
+// plans: offsets are 256 B aligned and H*W is a multiple of 16.
+#include "stream.h"
 #include "stk_blocks.h"
 
 // A product that must be ROUNDED before it is used (torch evaluates a * x + b as two kernels): HIP's __fmul_rn is a plain
@@ -13,23 +11,6 @@
 __device__ __forceinline__ float rounded(float v) { asm volatile("" : "+v"(v)); return v; }
 
 namespace {
-
-template <int V> struct Vec;
-template <> struct Vec<1> {
-  float v[1];
-  __device__ static Vec load(const float* p, long i) { Vec r; r.v[0] = p[i]; return r; }
-  __device__ void store(float* p, long i) const { p[i] = v[0]; }
-};
-template <> struct Vec<4> {
-  float v[4];
-  __device__ static Vec load(const float* p, long i) {
-    float4 t = reinterpret_cast<const float4*>(p)[i];
-    Vec r; r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w; return r;
-  }
-  __device__ void store(float* p, long i) const {
-    reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
 
 // Generic launcher: F::run<V>(i) processes vector item i (elements [V*i, V*i+V)).
 template <int V, class F>
@@ -41,14 +22,9 @@ __global__ __launch_bounds__(256) void ew_kernel(long nv, F f) {
 template <class F>
 int launch_ew(long n, bool vec_ok, F f, hipStream_t s) {
   if (n <= 0) return STK_OK;
-  if (vec_ok && (n & 3) == 0) {
-    long nv = n >> 2;
-    hipLaunchKernelGGL((ew_kernel<4, F>), dim3(stk_ew_grid(nv)), dim3(256), 0, s, nv, f);
-  } else {
-    hipLaunchKernelGGL((ew_kernel<1, F>), dim3(stk_ew_grid(n)), dim3(256), 0, s, n, f);
-  }
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  const bool vec = vec_ok && (n & 3) == 0;
+  const long nv = vec ? n >> 2 : n;
+  return stk_launch_vec(vec, ew_kernel<4, F>, ew_kernel<1, F>, dim3(stk_ew_grid(nv)), s, nv, f);
 }
 
 // ---- functors -------------------------------------------------------------------------------
@@ -383,35 +359,35 @@ extern "C" {
 
 int stk_silu_fwd_f32(const float* x, float* y, long n, void* stream) {
   if (!x || !y || n < 0) return STK_EINVAL;
-  return launch_ew(n, stk_aligned16(x) && stk_aligned16(y), SiluFwd{x, y}, S(stream));
+  return launch_ew(n, stk_all_aligned16(x, y), SiluFwd{x, y}, S(stream));
 }
 
 int stk_silu_bwd_f32(const float* x, const float* dy, float* dx, float beta, long n, void* stream) {
   if (!x || !dy || !dx || n < 0) return STK_EINVAL;
-  return launch_ew(n, stk_aligned16(x) && stk_aligned16(dy) && stk_aligned16(dx), SiluBwd{x, dy, dx, beta}, S(stream));
+  return launch_ew(n, stk_all_aligned16(x, dy, dx), SiluBwd{x, dy, dx, beta}, S(stream));
 }
 
 int stk_act_fwd_f32(const float* x, float* y, long n, int act, void* stream) {
   if (!x || !y || n < 0 || act < 0 || act > STK_ACT_ELU) return STK_EINVAL;
   if (act == STK_ACT_SILU) return stk_silu_fwd_f32(x, y, n, stream);
-  return launch_ew(n, stk_aligned16(x) && stk_aligned16(y), ActFwd{x, y, act}, S(stream));
+  return launch_ew(n, stk_all_aligned16(x, y), ActFwd{x, y, act}, S(stream));
 }
 
 int stk_act_bwd_f32(const float* x, const float* dy, float* dx, float beta, long n, int act, void* stream) {
   if (!x || !dy || !dx || n < 0 || act < 0 || act > STK_ACT_ELU) return STK_EINVAL;
   if (act == STK_ACT_SILU) return stk_silu_bwd_f32(x, dy, dx, beta, n, stream);
-  return launch_ew(n, stk_aligned16(x) && stk_aligned16(dy) && stk_aligned16(dx), ActBwd{x, dy, dx, beta, act}, S(stream));
+  return launch_ew(n, stk_all_aligned16(x, dy, dx), ActBwd{x, dy, dx, beta, act}, S(stream));
 }
 
 int stk_axpby_f32(const float* a, float alpha, const float* b, float beta, float* out, long n, void* stream) {
   if (!a || !out || n < 0) return STK_EINVAL;
-  return launch_ew(n, stk_aligned16(a) && stk_aligned16(out) && (!b || stk_aligned16(b)),
+  return launch_ew(n, stk_all_aligned16(a, out, b),
                    Axpby{a, alpha, b, beta, out}, S(stream));
 }
 
 int stk_add_div_f32(const float* a, const float* b, float div, float* out, long n, void* stream) {
   if (!a || !b || !out || n < 0 || div == 0.f) return STK_EINVAL;
-  return launch_ew(n, stk_aligned16(a) && stk_aligned16(b) && stk_aligned16(out),
+  return launch_ew(n, stk_all_aligned16(a, b, out),
                    AddDiv{a, b, 1.f / div, div != 1.f, out}, S(stream));
 }
 
@@ -486,7 +462,7 @@ int stk_fixed_fourier_bwd_f32(const float* x, const float* dy, float* dx, float 
 
 int stk_affine_f32(const float* x, float a, float b, float* out, long n, void* stream) {
   if (!x || !out || n < 0) return STK_EINVAL;
-  return launch_ew(n, stk_aligned16(x) && stk_aligned16(out), Affine{x, a, b, out}, S(stream));
+  return launch_ew(n, stk_all_aligned16(x, out), Affine{x, a, b, out}, S(stream));
 }
 
 __global__ __launch_bounds__(256) void fill_strided_kernel(float* __restrict__ out, float v, long total, long len, long stride) {
@@ -508,7 +484,7 @@ int stk_fill_f32(float* out, float v, long n, void* stream) {
 int stk_fused_bias_act_f32(const float* x, const float* b, const float* ref, float* out, long size_x,
                            int step_b, int size_b, int act, int grad, float alpha, float scale, void* stream) {
   if (!x || !out || size_x < 0 || (b && (step_b <= 0 || size_b <= 0))) return STK_EINVAL;
-  const bool v = stk_aligned16(x) && stk_aligned16(out) && (!ref || stk_aligned16(ref));
+  const bool v = stk_all_aligned16(x, out, ref);
   return launch_ew(size_x, v, BiasAct{x, b, ref, out, b ? step_b : 1, b ? size_b : 1, act * 10 + grad, alpha, scale},
                    S(stream));
 }
@@ -524,14 +500,14 @@ int stk_fused_bias_act_f64(const double* x, const double* b, const double* ref, 
 
 int stk_rowscale_f32(const float* x, const float* s, float* out, int N, long inner, int mode, void* stream) {
   if (!x || !s || !out || N <= 0 || inner <= 0) return STK_EINVAL;
-  const bool v = stk_aligned16(x) && stk_aligned16(out) && (inner & 3) == 0;
+  const bool v = stk_all_aligned16(x, out) && (inner & 3) == 0;
   return launch_ew((long)N * inner, v, RowScale{x, s, out, inner, mode}, S(stream));
 }
 
 int stk_perturb_f32(const float* x, const float* z, const float* a, const float* s, float* out, int N,
                     long inner, void* stream) {
   if (!x || !z || !s || !out || N <= 0 || inner <= 0) return STK_EINVAL;
-  const bool v = stk_aligned16(x) && stk_aligned16(z) && stk_aligned16(out) && (inner & 3) == 0;
+  const bool v = stk_all_aligned16(x, z, out) && (inner & 3) == 0;
   return launch_ew((long)N * inner, v, Perturb{x, z, a, s, out, inner}, S(stream));
 }
 
@@ -608,7 +584,7 @@ int stk_sm_loss_fwd_f32(const float* net, const float* z, const float* std, cons
 int stk_sm_loss_bwd_f32(const float* net, const float* z, const float* std, const float* wgt, const float* dloss,
                         float* dnet, int N, long inner, int vp, int mode, int reduce_mean, void* stream) {
   if (!net || !z || !std || !wgt || !dloss || !dnet || N <= 0 || inner <= 0) return STK_EINVAL;
-  const bool v = stk_aligned16(net) && stk_aligned16(z) && stk_aligned16(dnet) && (inner & 3) == 0;
+  const bool v = stk_all_aligned16(net, z, dnet) && (inner & 3) == 0;
   const float red = reduce_mean ? 1.f / (float)inner : 0.5f;
   return launch_ew((long)N * inner, v, LossBwd{net, z, std, wgt, dloss, dnet, inner, vp, mode, red}, S(stream));
 }

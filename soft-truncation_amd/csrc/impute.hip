@@ -1,31 +1,15 @@
 // impute.hip -- the data-consistency pass of the inpainting / colourisation samplers (include/stk_impute.h, gfx950).
 //
 // One streaming pass: per half-step it reads x, data, z and the mask and writes x and x_mean, 24 B per element with a full
-// mask, and does a dozen multiply-adds per element (about thirty with the 3x3 colour mix) -- HBM-bound, like the kernels of
-// elementwise.hip, and laid out like them: lanes walk consecutive addresses, 16 B per lane whenever H*W is a multiple of 4
-// and every pointer is 16-byte aligned, a scalar path otherwise; the grid is capped at 8 blocks per CU and strides the rest.
+// mask, and does a dozen multiply-adds per element (about thirty with the 3x3 colour mix) -- HBM-bound, and laid out as
+// stream.h describes, the 16-byte path taken whenever H*W is a multiple of 4 (an item never leaves its plane).
 // With the colour mix a thread needs the three channels of its pixels: it reads three planes H*W apart, each access still
 // consecutive across the lanes, so nothing is transposed.  Every tensor has fewer than 2^31 elements (checked by the entry),
 // so the index arithmetic is 32-bit: one unsigned division per item instead of a 64-bit one.
-#include "common.h"
+#include "stream.h"
 #include "stk_impute.h"
 
 namespace {
-
-template <int V> struct Vec;
-template <> struct Vec<1> {
-  float v[1];
-  __device__ static Vec load(const float* p, unsigned i) { Vec r; r.v[0] = p[i]; return r; }
-  __device__ void store(float* p, unsigned i) const { p[i] = v[0]; }
-};
-template <> struct Vec<4> {
-  float v[4];
-  __device__ static Vec load(const float* p, unsigned i) {
-    float4 t = reinterpret_cast<const float4*>(p)[i];
-    Vec r; r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w; return r;
-  }
-  __device__ void store(float* p, unsigned i) const { reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]); }
-};
 
 struct Mat3 { float m[9]; };   // row-major: (x M)_j = sum_i x_i m[3 i + j]
 
@@ -116,8 +100,7 @@ extern "C" int stk_impute_f32(const float* x, const float* data, const float* z,
   if ((mask_n != 1 && mask_n != N) || (mask_c != 1 && mask_c != C)) return STK_EUNSUPPORTED;
   const long LIMIT = 1L << 31;
   if (HW >= LIMIT || (long)N * C >= LIMIT || (long)N * C * HW >= LIMIT) return STK_EUNSUPPORTED;
-  const bool vec = (HW & 3) == 0 && stk_aligned16(x) && stk_aligned16(data) && stk_aligned16(mask) && stk_aligned16(x_out) &&
-                   (!z || stk_aligned16(z)) && (!xmean_out || stk_aligned16(xmean_out));
+  const bool vec = (HW & 3) == 0 && stk_all_aligned16(x, data, mask, x_out, z, xmean_out);
   const unsigned hwv = (unsigned)(vec ? HW >> 2 : HW);
   Args g{x, data, z, mask, a, s, x_out, xmean_out, (unsigned)C, hwv,
          mask_n == 1 ? 0u : (unsigned)mask_c * hwv, mask_c == 1 ? 0u : hwv};
@@ -126,13 +109,8 @@ extern "C" int stk_impute_f32(const float* x, const float* data, const float* z,
     Mat3 m, u;
     for (int i = 0; i < 9; ++i) { m.m[i] = mix[i]; u.m[i] = unmix[i]; }
     const unsigned total = (unsigned)N * hwv;
-    if (vec) hipLaunchKernelGGL(impute_mix_kernel<4>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, g, m, u);
-    else hipLaunchKernelGGL(impute_mix_kernel<1>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, g, m, u);
-  } else {
-    const unsigned total = (unsigned)N * (unsigned)C * hwv;
-    if (vec) hipLaunchKernelGGL(impute_kernel<4>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, g);
-    else hipLaunchKernelGGL(impute_kernel<1>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, g);
+    return stk_launch_vec(vec, impute_mix_kernel<4>, impute_mix_kernel<1>, dim3(stk_ew_grid(total)), st, total, g, m, u);
   }
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  const unsigned total = (unsigned)N * (unsigned)C * hwv;
+  return stk_launch_vec(vec, impute_kernel<4>, impute_kernel<1>, dim3(stk_ew_grid(total)), st, total, g);
 }

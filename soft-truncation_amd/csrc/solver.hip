@@ -2,29 +2,13 @@
 //
 // One streaming pass per network evaluation: it reads x, the score and (second order) the previous data prediction and
 // writes x and the data prediction, at most 12 B read and 8 B written per element, around seven multiply-adds -- HBM-bound,
-// like the kernels of elementwise.hip and impute.hip, and laid out like them: lanes walk consecutive addresses, 16 B per
-// lane whenever n is a multiple of 4 and every pointer given is 16-byte aligned, a scalar path otherwise; the grid is
-// capped at 8 blocks per CU and strides the rest.  n < 2^31 (checked by the entry), so the index arithmetic is 32-bit.
+// and laid out as stream.h describes, the 16-byte path taken whenever n is a multiple of 4.  n < 2^31 (checked by the
+// entry), so the index arithmetic is 32-bit.
 // The five coefficients and the two bounds are launch arguments: nothing is read from a table.
-#include "common.h"
+#include "stream.h"
 #include "stk_solver.h"
 
 namespace {
-
-template <int V> struct Vec;
-template <> struct Vec<1> {
-  float v[1];
-  __device__ static Vec load(const float* p, unsigned i) { Vec r; r.v[0] = p[i]; return r; }
-  __device__ void store(float* p, unsigned i) const { p[i] = v[0]; }
-};
-template <> struct Vec<4> {
-  float v[4];
-  __device__ static Vec load(const float* p, unsigned i) {
-    float4 t = reinterpret_cast<const float4*>(p)[i];
-    Vec r; r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w; return r;
-  }
-  __device__ void store(float* p, unsigned i) const { reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]); }
-};
 
 // The operands of one launch.  x_out may be x and d_out may be d_prev: an item reads all it needs before it writes, and no
 // two items share an element.
@@ -63,13 +47,8 @@ extern "C" int stk_dpm_update_f32(const float* x, const float* score, const floa
                                   float B, float clip_lo, float clip_hi, float* x_out, float* d_out, long n, void* stream) {
   if (!x || !score || !x_out || n <= 0 || (g != 0.f && !d_prev) || !(clip_lo <= clip_hi)) return STK_EINVAL;
   if (n >= (1L << 31)) return STK_EUNSUPPORTED;
-  const bool vec = (n & 3) == 0 && stk_aligned16(x) && stk_aligned16(score) && stk_aligned16(x_out) &&
-                   (!d_prev || stk_aligned16(d_prev)) && (!d_out || stk_aligned16(d_out));
+  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, x_out, d_prev, d_out);
   const unsigned total = (unsigned)(vec ? n >> 2 : n);
   Args a{x, score, d_prev, x_out, d_out, cx, cs, g, A, B, clip_lo, clip_hi};
-  hipStream_t st = (hipStream_t)stream;
-  if (vec) hipLaunchKernelGGL(dpm_update_kernel<4>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, a);
-  else hipLaunchKernelGGL(dpm_update_kernel<1>, dim3(stk_ew_grid(total)), dim3(256), 0, st, total, a);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  return stk_launch_vec(vec, dpm_update_kernel<4>, dpm_update_kernel<1>, dim3(stk_ew_grid(total)), (hipStream_t)stream, total, a);
 }

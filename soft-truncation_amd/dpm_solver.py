@@ -30,7 +30,6 @@ import torch
 from . import sde_lib
 from .engine import lib as stk_lib
 from .models import utils as mutils
-from .op import _backend
 
 SKIPS = ('logsnr', 'time', 'time_quadratic')
 LOWER_ORDER_FINAL_BELOW = 15     # order 2 ends with a first-order step when steps < 15 (DPM-Solver's lower_order_final)
@@ -38,11 +37,7 @@ _INF = float('inf')
 
 
 def _library():
-  lib = _backend.get()
-  if not lib.has_solver:
-    raise NotImplementedError(f'{lib.path} ({lib.backend}) does not implement include/stk_solver.h: the DPM-Solver++ sampler '
-                              f'needs stk_dpm_update_f32 (there is no other path)')
-  return lib
+  return mutils.require('has_solver', 'stk_solver.h', 'stk_dpm_update_f32', 'the DPM-Solver++ sampler needs')
 
 
 def alpha_sigma(sde, t):
@@ -184,23 +179,18 @@ def dpm_sample(score_fn, x, schedule, clip=None, denoise=False):
   lives in one buffer, overwritten in place.  clip = (lo, hi) clamps every data prediction.  denoise: one more evaluation
   at eps, after which `x` holds the data prediction there."""
   lib = _library()
-  _backend.check(x, lib)
-  if x.dtype != torch.float32 or not x.is_contiguous():
-    raise ValueError(f'x must be a contiguous float32 tensor (it is updated in place), got {x.dtype}, strides {x.stride()}')
+  mutils.check_inplace_state(x, lib)
   bounds = _clip_bounds(clip)
   rows = list(schedule.coeffs) + ([schedule.final] if denoise else [])
   times = list(schedule.times[:-1]) + ([schedule.times[-1]] if denoise else [])
   ones = torch.ones(x.shape[0], dtype=torch.float32, device=x.device)
   hist = None
   for i, (row, t) in enumerate(zip(rows, times)):
-    score = score_fn(x, ones * float(t))
-    _backend.check(score, lib)
-    if score.shape != x.shape or score.dtype != torch.float32:
-      raise ValueError(f'score_fn returned {score.dtype} {tuple(score.shape)} for a float32 state {tuple(x.shape)}')
+    score = mutils.checked_score(score_fn, x, ones * float(t), lib)
     keep = i + 1 < len(rows) and rows[i + 1][2] != 0.       # the next step extrapolates from this data prediction
     if keep and hist is None:
       hist = torch.empty_like(x)
-    _update(lib, x, score.contiguous(), hist if row[2] != 0. else None, row, bounds, x, hist if keep else None)
+    _update(lib, x, score, hist if row[2] != 0. else None, row, bounds, x, hist if keep else None)
   return x
 
 
@@ -212,15 +202,12 @@ def get_dpm_sampler(config, sde, shape, inverse_scaler, steps=20, order=2, skip=
   lib = _library()
   schedule = dpm_schedule(sde, steps, order=order, skip=skip, eps=eps, lower_order_final=lower_order_final)
   _clip_bounds(clip)
-  if precision not in mutils.PRECISIONS:
-    raise ValueError(f'precision must be one of {mutils.PRECISIONS}, got {precision!r}')
+  mutils.check_precision(precision)
   nfe = schedule.steps + (1 if denoise else 0)
 
   def dpm_sampler(model):
-    with torch.no_grad(), mutils.frozen_weights(model), mutils.precision(model, precision):
-      score_fn = mutils.get_score_fn(config, sde, model, train=False, continuous=config.training.continuous)
-      x = sde.prior_sampling(shape).to(device).contiguous()
-      _backend.check(x, lib)
+    with mutils.sampling_run(model, precision):
+      score_fn, x = mutils.score_and_prior(config, sde, model, shape, device, lib)
       x = dpm_sample(score_fn, x, schedule, clip=clip, denoise=denoise)
       return inverse_scaler(x), nfe
 
@@ -230,10 +217,6 @@ def get_dpm_sampler(config, sde, shape, inverse_scaler, steps=20, order=2, skip=
 def sampling_options(config):
   """(steps, order, skip, clip) of ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip``: 20, 2, 'logsnr' and None
   where a key is absent (the reference's configs have none)."""
-  def read(key, default):
-    try:
-      return getattr(config.sampling, key)
-    except (AttributeError, KeyError):
-      return default
+  read = lambda key, default: mutils.config_option(config, 'sampling', key, default)
   clip = read('dpm_clip', None)
   return read('dpm_steps', 20), read('dpm_order', 2), read('dpm_skip', 'logsnr'), None if clip is None else tuple(clip)

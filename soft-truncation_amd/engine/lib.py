@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, include/stk_fp16.h,
-include/stk_fp16_train.h, include/stk_blocks.h, include/stk_attention_long.h, include/stk_upconv.h, include/stk_impute.h, include/stk_solver.h and include/stk_adaptive.h).
+"""ctypes binding of the C ABI declared in include/stk.h (and, where the library has them, of the optional headers listed
+in ``OPTIONAL_HEADERS``).
 
 ``load()`` returns the product library (``csrc/libstk.so``, hand-written HIP for gfx950) and
 raises :class:`StkMissingError` when it has not been built -- there is no CPU or PyTorch
@@ -7,6 +7,7 @@ fallback anywhere in the product path.  ``load_path()`` binds any library implem
 header; tests use it to inject the oracle's plain-C restatement as a *checker* backend for
 host-logic tests on CPU tensors.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -109,15 +110,14 @@ SIGNATURES = {
   'stk_samples_to_uint8': [P, P, I, I, L, S],
   'stk_preprocess_u8': [P, P, I, I, I, I, I, I, I, U64, S],
 }
-# include/stk_fp16.h: the one-product forward twins (fp16 mode).  Only the product library exports them; they are bound when
-# present and `StkLib.has_fp16` says whether they are.  Asking for the fp16 mode without them is an error (engine/executor.py).
+# The optional headers: one SIGNATURES_* table each, gathered in OPTIONAL_HEADERS below, which says how they are bound.
+# include/stk_fp16.h: the one-product forward twins (fp16 mode; asking for it without them is an error, engine/executor.py).
 SIGNATURES_FP16 = {
   'stk_conv2d_fwd_pl_f16x1': SIGNATURES['stk_conv2d_fwd_pl_f32'],
   'stk_conv2d_fwd_rec_f16x1': SIGNATURES['stk_conv2d_fwd_rec_f32'],
   'stk_conv2d_fwd_wp_f16x1': SIGNATURES['stk_conv2d_fwd_wp_f32'],
 }
-# include/stk_fp16_train.h: the one-product backward twins (fp16 training mode).  Bound like SIGNATURES_FP16, when present;
-# `StkLib.has_fp16_train` says whether they are.
+# include/stk_fp16_train.h: the one-product backward twins (fp16 training mode).
 SIGNATURES_FP16_TRAIN = {
   'stk_conv2d_dgrad_pl_f16x1': SIGNATURES['stk_conv2d_dgrad_pl_f32'],
   'stk_conv2d_dgrad_rec_f16x1': SIGNATURES['stk_conv2d_dgrad_rec_f32'],
@@ -126,42 +126,37 @@ SIGNATURES_FP16_TRAIN = {
   'stk_conv2d_wgrad_pl_wgs_f16x1': SIGNATURES['stk_conv2d_wgrad_pl_wgs_f32'],
   'stk_conv2d_wgrad_amax_f16x1': SIGNATURES['stk_conv2d_wgrad_amax_f32'],
 }
-# include/stk_blocks.h: gradients only the stand-alone building blocks need.  Bound like SIGNATURES_FP16, when present;
-# `StkLib.has_blocks` says whether they are (a graph that needs one on a library without them is refused when it is planned).
+# include/stk_blocks.h: gradients only the stand-alone building blocks need (a graph that needs one on a library without them
+# is refused when it is planned).
 SIGNATURES_BLOCKS = {
   'stk_fourier_embedding_bwd_f32': [P, P, P, P, F, I, I, S],
 }
-# include/stk_attention_long.h: the streaming attention core for maps above 16 x 16.  Bound like SIGNATURES_FP16, when
-# present; `StkLib.has_attention_long` says whether they are (AttentionCore plans the GEMM form without them).  _ok and
-# _ws_bytes are queries, not launches: they are bound unchecked, _ws_bytes returning a long.
+# include/stk_attention_long.h: the streaming attention core for maps above 16 x 16 (AttentionCore plans the GEMM form
+# without it).
 SIGNATURES_ATTN_LONG = {
   'stk_attention_long_ok': [I, I, I],
   'stk_attention_long_ws_bytes': [I, I, I],
   'stk_attention_long_fwd_f32': [P, P, P, L, P, P, P, I, I, I, F, P, L, S],
   'stk_attention_long_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, F, P, L, S],
 }
-# include/stk_upconv.h: the FIR-upsampling convolution (Conv2d(up=True)).  Bound like SIGNATURES_FP16, when present;
-# `StkLib.has_upconv` says whether they are (engine.graph.UpConv refuses to plan without them).  _ws_bytes is a query.
+_NO_CHECK_ATTN_LONG = {'stk_attention_long_ws_bytes', 'stk_attention_long_ok'}   # its queries (tests/_launch_trace.py reads this)
+# include/stk_upconv.h: the FIR-upsampling convolution, Conv2d(up=True) (engine.graph.UpConv refuses to plan without it).
 SIGNATURES_UPCONV = {
   'stk_upconv2d_ws_bytes': [I, I, I, I, I, I, I, I],
   'stk_upconv2d_fwd_f32': [P, P, P, P, P, F, P, I, I, I, I, I, I, I, I, P, L, S],
   'stk_upconv2d_dgrad_f32': [P, P, P, P, I, P, F, F, I, I, I, I, I, I, I, I, S],
   'stk_upconv2d_wgrad_f32': [P, P, P, P, I, P, F, I, I, I, I, I, I, I, I, P, L, S],
 }
-_RESTYPE_UPCONV = {'stk_upconv2d_ws_bytes': c_long}
-# include/stk_impute.h: the data-consistency pass of the inpainting / colourisation samplers.  Bound like SIGNATURES_FP16, when
-# present; `StkLib.has_impute` says whether it is (controllable_generation refuses to build a sampler without it).  The two
-# 3x3 matrices are HOST pointers.
+# include/stk_impute.h: the data-consistency pass of the inpainting / colourisation samplers.  The two 3x3 matrices are HOST
+# pointers.
 SIGNATURES_IMPUTE = {
   'stk_impute_f32': [P, P, P, P, P, P, P, P, P, P, I, I, L, I, I, S],
 }
-# include/stk_solver.h: the update of the DPM-Solver++ samplers.  Bound like SIGNATURES_FP16, when present;
-# `StkLib.has_solver` says whether it is (dpm_solver refuses to build a sampler without it).
+# include/stk_solver.h: the update of the DPM-Solver++ samplers.
 SIGNATURES_SOLVER = {
   'stk_dpm_update_f32': [P, P, P, F, F, F, F, F, F, F, P, P, L, S],
 }
-# include/stk_adaptive.h: the three passes of the adaptive-step SDE sampler.  Bound like SIGNATURES_FP16, when present;
-# `StkLib.has_adaptive` says whether they are (adaptive_sde refuses to build a sampler without them).  _ws_bytes is a query.
+# include/stk_adaptive.h: the three passes of the adaptive-step SDE sampler.
 SIGNATURES_ADAPTIVE = {
   'stk_sde_ws_bytes': [I, L],
   'stk_sde_stage_f32': [P, P, P, P, P, P, I, L, S],
@@ -169,12 +164,30 @@ SIGNATURES_ADAPTIVE = {
   'stk_sde_commit_f32': [P, P, P, P, P, P, F, F, F, P, L, P, P, P, P, I, L, S],
 }
 _RESTYPE_ADAPTIVE = {'stk_sde_ws_bytes': c_long}
+
+# One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
+# otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
+#   has: the StkLib attribute that says whether they are bound;  restype: the entries that do not return an int (the
+#   workspace queries return a long);  unchecked: the further entries whose int is an answer, not a status.  Both kinds are
+#   bound as raw functions, every other entry status-checked.
+Header = collections.namedtuple('Header', 'has path table restype unchecked')
+OPTIONAL_HEADERS = (
+  Header('has_fp16', 'include/stk_fp16.h', SIGNATURES_FP16, {}, ()),
+  Header('has_fp16_train', 'include/stk_fp16_train.h', SIGNATURES_FP16_TRAIN, {}, ()),
+  Header('has_blocks', 'include/stk_blocks.h', SIGNATURES_BLOCKS, {}, ()),
+  Header('has_attention_long', 'include/stk_attention_long.h', SIGNATURES_ATTN_LONG, {'stk_attention_long_ws_bytes': c_long},
+         _NO_CHECK_ATTN_LONG),
+  Header('has_upconv', 'include/stk_upconv.h', SIGNATURES_UPCONV, {'stk_upconv2d_ws_bytes': c_long}, ()),
+  Header('has_impute', 'include/stk_impute.h', SIGNATURES_IMPUTE, {}, ()),
+  Header('has_solver', 'include/stk_solver.h', SIGNATURES_SOLVER, {}, ()),
+  Header('has_adaptive', 'include/stk_adaptive.h', SIGNATURES_ADAPTIVE, _RESTYPE_ADAPTIVE, ()),
+)
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
             'stk_conv2d_wp_bytes': c_long, 'stk_conv2d_wp_desc': c_long, 'stk_planes_bytes': c_long, 'stk_conv2d_wgrad_pl_ws_bytes': c_long}
-_RESTYPE_ATTN_LONG = {'stk_attention_long_ws_bytes': c_long}
-_NO_CHECK_ATTN_LONG = set(_RESTYPE_ATTN_LONG) | {'stk_attention_long_ok'}
+# every entry, of stk.h or of an optional header, that is bound as a raw function
 _NO_CHECK = set(_RESTYPE) | {'stk_version', 'stk_conv2d_variant', 'stk_conv2d_pl_ok', 'stk_gn_fwd_pl_fused', 'stk_conv2d_wgrad_pl_ok', 'stk_attention_ok', 'stk_gn_bwd_out_ok', 'stk_conv2d_pl_ksplit', 'stk_conv2d_pl_halo'}
+_NO_CHECK |= {name for h in OPTIONAL_HEADERS for name in (*h.restype, *h.unchecked)}
 
 
 class StkMissingError(RuntimeError):
@@ -202,32 +215,21 @@ class StkLib:
         setattr(self, name[4:], fn)
       else:
         setattr(self, name[4:], self._checked(name, fn))
-    self.has_fp16 = self._bind_optional(SIGNATURES_FP16, 'include/stk_fp16.h')
-    self.has_fp16_train = self._bind_optional(SIGNATURES_FP16_TRAIN, 'include/stk_fp16_train.h')
-    self.has_blocks = self._bind_optional(SIGNATURES_BLOCKS, 'include/stk_blocks.h')
-    self.has_attention_long = self._bind_optional(SIGNATURES_ATTN_LONG, 'include/stk_attention_long.h',
-                                                  restype=_RESTYPE_ATTN_LONG, unchecked=_NO_CHECK_ATTN_LONG)
-    self.has_upconv = self._bind_optional(SIGNATURES_UPCONV, 'include/stk_upconv.h', restype=_RESTYPE_UPCONV,
-                                          unchecked=set(_RESTYPE_UPCONV))
-    self.has_impute = self._bind_optional(SIGNATURES_IMPUTE, 'include/stk_impute.h')
-    self.has_solver = self._bind_optional(SIGNATURES_SOLVER, 'include/stk_solver.h')
-    self.has_adaptive = self._bind_optional(SIGNATURES_ADAPTIVE, 'include/stk_adaptive.h', restype=_RESTYPE_ADAPTIVE,
-                                            unchecked=set(_RESTYPE_ADAPTIVE))
+    for header in OPTIONAL_HEADERS:
+      setattr(self, header.has, self._bind_optional(header))
     self.backend = self._cdll.stk_backend().decode()
     self.is_device = self.backend.startswith('hip')
 
-  def _bind_optional(self, table, header, restype=None, unchecked=()):
-    """Bind the entries of an optional header: all of them or none (a partial table raises StkMissingError).
-    restype: name -> ctypes result type of the entries that do not return an int status; unchecked: names bound as raw
-    functions (queries whose result is not a status)."""
-    present = [name for name in table if hasattr(self._cdll, name)]
-    if present and len(present) != len(table):
-      raise StkMissingError(f'{self.path} exports only part of {header}: {present}')
+  def _bind_optional(self, header):
+    """Bind the entries of one row of OPTIONAL_HEADERS: all of them or none (a partial table raises StkMissingError)."""
+    present = [name for name in header.table if hasattr(self._cdll, name)]
+    if present and len(present) != len(header.table):
+      raise StkMissingError(f'{self.path} exports only part of {header.path}: {present}')
     for name in present:
       fn = getattr(self._cdll, name)
-      fn.argtypes = table[name]
-      fn.restype = (restype or {}).get(name, c_int)
-      setattr(self, name[4:], fn if name in unchecked else self._checked(name, fn))
+      fn.argtypes = header.table[name]
+      fn.restype = header.restype.get(name, c_int)
+      setattr(self, name[4:], fn if name in _NO_CHECK else self._checked(name, fn))
     return bool(present)
 
   def _checked(self, name, fn):

@@ -12,10 +12,13 @@ parameters).  Here every GPU runs its own process; :class:`DataParallel` below o
 initialised, averages gradients with one bucketed RCCL all-reduce per step
 (see ``engine/ddp.py``).
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from .. import sde_lib
+from ..op import _backend
 
 _MODELS = {}
 
@@ -85,7 +88,6 @@ def create_model(config, sde):
 def frozen_weights(model):
   """Context manager for loops that evaluate `model` many times on fixed parameters (samplers, likelihood ODEs): the
   engine prepares the convolution weights once instead of once per evaluation.  A no-op for models without an engine."""
-  import contextlib
   inner = getattr(model, 'module', model)
   engine = getattr(inner, 'engine', None)
   return engine().frozen_weights() if callable(engine) else contextlib.nullcontext()
@@ -94,14 +96,18 @@ def frozen_weights(model):
 PRECISIONS = ('fp32', 'fp16')
 
 
+def check_precision(value, what='precision'):
+  if value not in PRECISIONS:
+    raise ValueError(f'{what} must be one of {PRECISIONS}, got {value!r}')
+  return value
+
+
 def precision(model, precision):
   """Context manager: the network evaluations of `model` inside it run in `precision` -- 'fp32' (the default path) or
   'fp16' (one fp16 product per multiply-add in the split convolutions, include/stk_fp16.h; forward-only: a forward that
   a backward may follow raises ValueError inside the block).  For a user's own loop around get_score_fn.  A no-op for
   models without an engine (the value is still checked)."""
-  import contextlib
-  if precision not in PRECISIONS:
-    raise ValueError(f'precision must be one of {PRECISIONS}, got {precision!r}')
+  check_precision(precision)
   inner = getattr(model, 'module', model)
   engine = getattr(inner, 'engine', None)
   return engine().precision(precision) if callable(engine) else contextlib.nullcontext()
@@ -113,9 +119,7 @@ def training_precision(model, precision):
   multiply-add in every split convolution, include/stk_fp16.h and include/stk_fp16_train.h).  Forward-only evaluations
   inside it keep following precision(), fp32 by default.  For a user's own training loop; get_step_fn applies it from
   config.training.precision.  A no-op for models without an engine (the value is still checked)."""
-  import contextlib
-  if precision not in PRECISIONS:
-    raise ValueError(f'precision must be one of {PRECISIONS}, got {precision!r}')
+  check_precision(precision)
   inner = getattr(model, 'module', model)
   engine = getattr(inner, 'engine', None)
   return engine().training_precision(precision) if callable(engine) else contextlib.nullcontext()
@@ -128,26 +132,68 @@ def current_training_precision(model):
   return engine().train_mode if callable(engine) else 'fp32'
 
 
-def config_training_precision(config):
-  """config.training.precision: 'fp32' when the key is absent (the reference's configs have none), else checked."""
+def config_option(config, section, key, default):
+  """``config.<section>.<key>``, or `default` where the key is absent (the reference's configs have none of the keys this
+  package adds)."""
   try:
-    p = config.training.precision
+    return getattr(getattr(config, section), key)
   except (AttributeError, KeyError):
-    return 'fp32'
-  if p not in PRECISIONS:
-    raise ValueError(f'config.training.precision must be one of {PRECISIONS}, got {p!r}')
-  return p
+    return default
+
+
+def config_training_precision(config):
+  """config.training.precision: 'fp32' when the key is absent, else checked."""
+  return check_precision(config_option(config, 'training', 'precision', 'fp32'), 'config.training.precision')
 
 
 def sampling_precision(config):
-  """config.sampling.precision: 'fp32' when the key is absent (the reference's configs have none), else checked."""
-  try:
-    p = config.sampling.precision
-  except (AttributeError, KeyError):
-    return 'fp32'
-  if p not in PRECISIONS:
-    raise ValueError(f'config.sampling.precision must be one of {PRECISIONS}, got {p!r}')
-  return p
+  """config.sampling.precision: 'fp32' when the key is absent, else checked."""
+  return check_precision(config_option(config, 'sampling', 'precision', 'fp32'), 'config.sampling.precision')
+
+
+# ---- what the samplers share (sampling.py, controllable_generation.py, dpm_solver.py, adaptive_sde.py) --------------------
+def require(has, header, entries, user):
+  """The bound library, which must implement the optional header `header` (``has``: its StkLib attribute, engine/lib.py
+  OPTIONAL_HEADERS); NotImplementedError otherwise.  user: who needs `entries`, e.g. 'the DPM-Solver++ sampler needs'."""
+  lib = _backend.get()
+  if not getattr(lib, has):
+    raise NotImplementedError(f'{lib.path} ({lib.backend}) does not implement include/{header}: {user} {entries} '
+                              f'(there is no other path)')
+  return lib
+
+
+@contextlib.contextmanager
+def sampling_run(model, mode=None):
+  """Context of one sampling run on fixed weights: ``torch.no_grad``, the convolution weights prepared once
+  (:func:`frozen_weights`) and, unless `mode` is None, the network evaluations in precision `mode` (:func:`precision`).
+  Inside it a sampler builds its score function, draws the prior and loops, in that order."""
+  with torch.no_grad(), frozen_weights(model), contextlib.nullcontext() if mode is None else precision(model, mode):
+    yield
+
+
+def score_and_prior(config, sde, model, shape, device, lib):
+  """(score_fn, x): the score function of `model` and ONE ``sde.prior_sampling(shape)`` as a contiguous tensor on `device`,
+  which must be the library's."""
+  score_fn = get_score_fn(config, sde, model, train=False, continuous=config.training.continuous)
+  x = sde.prior_sampling(shape).to(device).contiguous()
+  _backend.check(x, lib)
+  return score_fn, x
+
+
+def check_inplace_state(x, lib):
+  """The state a loop advances in place: on the library's device, contiguous, float32."""
+  _backend.check(x, lib)
+  if x.dtype != torch.float32 or not x.is_contiguous():
+    raise ValueError(f'x must be a contiguous float32 tensor (it is updated in place), got {x.dtype}, strides {x.stride()}')
+
+
+def checked_score(score_fn, x, t, lib):
+  """``score_fn(x, t)``, which must be a float32 tensor of x's shape on the library's device, made contiguous."""
+  score = score_fn(x, t)
+  _backend.check(score, lib)
+  if score.shape != x.shape or score.dtype != torch.float32:
+    raise ValueError(f'score_fn returned {score.dtype} {tuple(score.shape)} for a float32 state {tuple(x.shape)}')
+  return score.contiguous()
 
 
 def get_model_fn(model, train=False):

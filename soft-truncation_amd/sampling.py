@@ -292,6 +292,15 @@ def shared_corrector_update_fn(x, t, sde, model, corrector, continuous, snr, n_s
   return obj.update_fn(x, t)
 
 
+def pc_updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous):
+  """(predict, correct): the two shared update functions bound to everything but ``(x, t, model=...)``."""
+  predict = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
+                              probability_flow=probability_flow, continuous=continuous, config=config)
+  correct = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
+                              n_steps=n_steps, config=config)
+  return predict, correct
+
+
 def _denoiser(config, sde, probability_flow):
   """Final noise-free reverse-diffusion step from ``sde.eps`` to 0, returning the mean (sampling.py:402-408,
   :457-463; the PC sampler uses the probability-flow form, the ODE sampler the SDE form)."""
@@ -341,15 +350,11 @@ def get_pc_sampler(config, sde, shape, predictor, corrector, inverse_scaler, snr
   """Predictor-corrector sampler (sampling.py:365-433): at each of the N times from T down to eps the corrector runs
   first, then the predictor; ``nfe = N (n_steps + 1)``.  precision='fp16': every network evaluation of the loop, the
   final denoising step included, runs in the engine's fp16 mode (models.utils.precision)."""
-  predict = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
-                              probability_flow=probability_flow, continuous=continuous, config=config)
-  correct = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
-                              n_steps=n_steps, config=config)
+  predict, correct = pc_updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
   denoise_update_fn = _denoiser(config, sde, probability_flow=True)
 
   def pc_sampler(model):
-    # the parameters are fixed for the whole loop: convolution weights are prepared once (models.utils.frozen_weights)
-    with torch.no_grad(), mutils.frozen_weights(model), mutils.precision(model, precision):
+    with mutils.sampling_run(model, precision):
       x = sde.prior_sampling(shape).to(device)
       grid = torch.linspace(sde.T, eps, sde.N, device=device)
       for i in tqdm(range(sde.N)):
@@ -393,7 +398,7 @@ def get_ode_sampler(config, sde, shape, inverse_scaler, denoise=False, rtol=1e-5
     return torch.tensor(solution.y[:, -1]).reshape(shape), solution.nfev
 
   def ode_sampler(model):
-    with torch.no_grad(), mutils.frozen_weights(model):
+    with mutils.sampling_run(model):                      # no precision of its own: fp32 (get_sampling_fn)
       x = sde.prior_sampling(shape).to(device)
       x, nfe = (integrate_on_device if method == 'RK45' else integrate_on_host)(model, x)
       x = x.to(device).type(torch.float32)

@@ -1,0 +1,40 @@
+"""Helpers of the GPU tests of the streaming kernels (test_gpu_impute.py, test_gpu_dpm_solver.py, test_gpu_adaptive_sde.py):
+operands on the 16-byte and on the scalar path, and the per-element rounding bound k u B."""
+import numpy as np
+import torch
+
+U = 2.0 ** -24
+
+
+def shifted(t, dev):
+  """A contiguous copy of t that starts 4 bytes into its buffer: a view no 16-byte access may touch."""
+  buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=dev)
+  view = buf[1:].view(t.shape)
+  view.copy_(t)
+  assert view.is_contiguous() and view.data_ptr() % 16 == 4
+  return view
+
+
+def place(t, dev, one_in=False):
+  """A fresh copy of t (a tensor or a numpy array) on dev: aligned, or entered one element into its buffer."""
+  if isinstance(t, np.ndarray):
+    t = torch.from_numpy(np.ascontiguousarray(t))
+  return shifted(t, dev) if one_in else t.to(dev).clone()
+
+
+def within(got, want, mag, k, what, show=False):
+  """|got - want| <= k u B, element by element, u = 2^-24; want and B = mag are float64, tensors or numpy arrays.  Returns
+  the worst ratio err / (u B), and prints it with show."""
+  want, mag = torch.as_tensor(want), torch.as_tensor(mag)
+  err = (got.detach().cpu().double() - want).abs()
+  assert torch.isfinite(err).all(), f'{what}: non-finite result'
+  units = float((err / (U * mag).clamp_min(1e-300)).max())
+  if show:
+    print(f'{what}: worst error {units:.2f} x 2^-24 B (bound {k})')
+  assert bool((err <= k * U * mag).all()), f'{what}: {units:.2f} x 2^-24 B exceeds {k}'
+  return units
+
+
+def case_id(v):
+  """Parametrize id of a (shape, shifted) case: '2x3x8x8' for the shape, 'aligned' / 'entered-one-in' for the flag."""
+  return 'x'.join(map(str, v)) if isinstance(v, tuple) else ('entered-one-in' if v else 'aligned')

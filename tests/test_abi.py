@@ -92,3 +92,34 @@ def test_product_never_imports_the_oracle():
       if f.endswith(('.py', '.hip', '.h')):
         text = open(os.path.join(dirpath, f)).read()
         assert 'ref_torch' not in text and 'refimport' not in text and 'libstk_ref' not in text, os.path.join(dirpath, f)
+
+
+def test_optional_headers_are_bound_from_one_table(st, ref_lib, monkeypatch):
+  """engine/lib.py OPTIONAL_HEADERS: one row per header under include/ other than stk.h and stk_rng.h (which declares no
+  entry), no entry name in two tables, and a library that exports only part of a header is refused."""
+  L = st.engine.lib
+  headers = sorted('include/' + f for f in os.listdir(os.path.join(ROOT, 'include'))
+                   if re.fullmatch(r'stk_\w+\.h', f) and f != 'stk_rng.h')
+  assert sorted(h.path for h in L.OPTIONAL_HEADERS) == headers
+  assert len({h.has for h in L.OPTIONAL_HEADERS}) == len(headers)
+  names = [n for table in [L.SIGNATURES] + [h.table for h in L.OPTIONAL_HEADERS] for n in table]
+  assert len(names) == len(set(names)) and len(L.SIGNATURES) == 84
+  for h in L.OPTIONAL_HEADERS:
+    assert set(h.restype) | set(h.unchecked) <= set(h.table), h.path
+    assert getattr(ref_lib, h.has) is False, h.path                 # the plain-C checker implements stk.h alone
+
+  class Partial:
+    """The checker's library, seeming to export `extra` as well."""
+    def __init__(self, extra):
+      self.extra = extra
+
+    def __getattr__(self, name):
+      return getattr(ref_lib._cdll, 'stk_version' if name in self.extra else name)
+
+  several = [h for h in L.OPTIONAL_HEADERS if len(h.table) > 1]
+  assert len(several) >= 4
+  for h in several:
+    some = list(h.table)[:-1]
+    monkeypatch.setattr(L.ctypes, 'CDLL', lambda path, some=some: Partial(some))
+    with pytest.raises(L.StkMissingError, match=f'only part of {h.path}'):
+      L.StkLib(ref_lib.path)

@@ -20,14 +20,13 @@ The loop and the sampler are compared with by-hand torch loops on the device, in
 seed and draw order (one randn_like per iteration), after asserting the precondition that the two by-hand loops take the
 identical accept / reject sequence and every float64 E of the run is at least 1e-3 from 1.
 """
-import copy
-
 import numpy as np
 import pytest
 import torch
 
 import _adaptive_ref as R
-from _model_cases import build_pair, tiny_config
+from _sampler_util import sampler, setup, shape_of as _shape
+from _stream_util import case_id, place, within
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +42,6 @@ closest float64 E to 1 7.8e-3; VE 113 iterations, 1.42e-6 / 5.41e-6, closest 4.0
 fp16 against fp32, max |difference| of the samples: 0 on the vp and ve networks (no layer of theirs takes an fp16 form),
 3.3e-3 on the wide one."""
 
-U = 2.0 ** -24
 K_X1, K_X1P, K_X2 = 4, 5, 6
 EPS = 1e-3
 EPS32 = float(np.float32(EPS))
@@ -55,21 +53,6 @@ F09 = float(np.float32(0.9))          # the controller's constants as the entry 
 # twelve blocks on the scalar path); 2048 blocks, each striding along its row
 SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True), ((2, 3, 32, 32), False),
           ((2, 3, 32, 32), True), ((16, 3, 256, 256), False)]
-_ids = lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else ('entered-one-in' if v else 'aligned')
-
-
-def _shifted(t, dev):
-  """A contiguous copy of t that starts 4 bytes into its buffer: a view no 16-byte access may touch."""
-  buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=dev)
-  view = buf[1:].view(t.shape)
-  view.copy_(t)
-  assert view.is_contiguous() and view.data_ptr() % 16 == 4
-  return view
-
-
-def _place(a, dev, shifted=False):
-  t = torch.from_numpy(np.ascontiguousarray(a))
-  return _shifted(t, dev) if shifted else t.to(dev).clone()
 
 
 def _stream():
@@ -137,14 +120,6 @@ def cases():
   return out
 
 
-def _within(got, want, mag, k, what):
-  err = np.abs(got.detach().cpu().double().numpy() - want)
-  assert np.isfinite(err).all(), f'{what}: non-finite result'
-  units = float((err / np.maximum(U * mag, 1e-300)).max())
-  assert bool((err <= k * U * mag).all()), f'{what}: {units:.2f} u B exceeds {k}'
-  return units
-
-
 class _Step:
   """The device buffers of one iteration and the three launches on them."""
 
@@ -152,10 +127,10 @@ class _Step:
     self.lib, self.shape = lib, op['x'].shape
     self.B, self.n = self.shape[0], int(np.prod(self.shape[1:]))
     for name in ('x', 'xp', 's1', 'z', 'x1', 'x1_prev', 's2'):
-      setattr(self, name, _place(op[name], dev, shifted))
-    self.row1, self.row2 = _place(op['row1'], dev), _place(op['row2'], dev)
+      setattr(self, name, place(op[name], dev, shifted))
+    self.row1, self.row2 = place(op['row1'], dev), place(op['row2'], dev)
     nan = np.full(self.shape, np.nan, dtype=np.float32)
-    self.out, self.x2 = _place(nan, dev, shifted), _place(nan, dev, shifted)
+    self.out, self.x2 = place(nan, dev, shifted), place(nan, dev, shifted)
     self.ws_bytes = lib.sde_ws_bytes(self.B, self.n)
     assert self.ws_bytes > 0 and self.ws_bytes % 8 == 0
     self.ws = torch.full((self.ws_bytes // 8,), float('nan'), dtype=torch.float64, device=dev)
@@ -183,7 +158,7 @@ class _Step:
     return x, x1_prev
 
 
-@pytest.mark.parametrize('shape,shifted', SHAPES, ids=_ids)
+@pytest.mark.parametrize('shape,shifted', SHAPES, ids=case_id)
 def test_kernels_match_float64(hip_lib, cases, shape, shifted):
   dev = torch.device('cuda:0')
   op, ref = cases[shape]
@@ -192,10 +167,10 @@ def test_kernels_match_float64(hip_lib, cases, shape, shifted):
   worst = {}
   for with_xp, key, K in ((False, 'x1', K_X1), (True, 'x1p', K_X1P)):
     got = st.stage(with_xp)
-    worst[key] = _within(got, ref['f64'][key], ref['B_' + key], K, f'stage {what} xp={with_xp}')
+    worst[key] = within(got, ref['f64'][key], ref['B_' + key], K, f'stage {what} xp={with_xp}')
     assert np.array_equal(got.cpu().numpy(), ref['f32'][key]), f'stage {what} xp={with_xp}: not the fp32 restatement bit for bit'
   x2 = st.heun()
-  worst['x2'] = _within(x2, ref['f64']['x2'], ref['B_x2'], K_X2, f'heun_error {what}')
+  worst['x2'] = within(x2, ref['f64']['x2'], ref['B_x2'], K_X2, f'heun_error {what}')
   assert np.array_equal(x2.cpu().numpy(), ref['f32']['x2']), f'heun_error {what}: x2 is not the fp32 restatement bit for bit'
   t = torch.full((st.B,), 0.5, device=dev)
   h = torch.full((st.B,), 0.01, device=dev)
@@ -471,31 +446,17 @@ def test_loop_with_a_closed_form_score(st, hip_lib, family):
 
 
 # ---- the sampler on the tiny networks -----------------------------------------------------------------------------------
-_built = {}
 # tolerances for a few dozen iterations on the random tiny networks (rtol 0.3 gives 8, rtol 1.0 gives 4)
 SAMPLER = {f: dict(rtol=0.03, atol=0.0078, seed=3) for f in ('vp', 've', 'wide')}
 
 
 def _setup(st, lib, family):
-  if family not in _built:
-    cfg = tiny_config(st, family)
-    cfg.sampling.method, cfg.sampling.noise_removal = 'adaptive', True
-    cfg.sampling.adaptive_rtol, cfg.sampling.adaptive_atol = SAMPLER[family]['rtol'], SAMPLER[family]['atol']
-    cfg, _, sde, model, _ = build_pair(st, cfg, lib)
-    model.eval()
-    _built[family] = (cfg, sde, model)
-  return _built[family]
-
-
-def _shape(cfg):
-  return (2, cfg.data.num_channels, cfg.data.image_size, cfg.data.image_size)
+  return setup(st, lib, family, dict(method='adaptive', noise_removal=True, adaptive_rtol=SAMPLER[family]['rtol'],
+                                     adaptive_atol=SAMPLER[family]['atol']))
 
 
 def _sampler(st, cfg, sde, **options):
-  c = copy.deepcopy(cfg)
-  for k, v in options.items():
-    setattr(c.sampling, k, v)
-  return st.sampling.get_sampling_fn(c, sde, _shape(c), st.datasets.get_data_inverse_scaler(c), EPS)
+  return sampler(st, cfg, sde, EPS, **options)
 
 
 @pytest.mark.parametrize('family', ['vp', 've'])

@@ -16,7 +16,6 @@ networks: every operation rounded), and four times its deviation from float64 is
 deviations are printed by the tests.  On the CPU the restatement in numpy fp32 deviates from float64 by 3.6e-7 (VP) and
 9.3e-7 (VE) relative at order 2, 20 steps; the figures of the product loop on an MI355X are not recorded yet (MEASURED).
 """
-import copy
 import itertools
 
 import numpy as np
@@ -24,13 +23,13 @@ import pytest
 import torch
 
 import _dpm_ref as R
-from _model_cases import build_pair, tiny_config
+from _sampler_util import sampler, setup, shape_of as _shape
+from _stream_util import case_id, place, within
 
 pytestmark = pytest.mark.gpu
 
 MEASURED = "unmeasured: no MI355X run of this file has been recorded"
 
-U = 2.0 ** -24
 K_D, K_X = 3, 8
 EPS = 1e-3
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -43,19 +42,6 @@ CLIPS = {'off': None, 'on': (-1., 1.), 'inf': (-INF, INF)}
 # the same entered one element in: 3145728 scalar items against 2048 x 256 threads, the scalar grid strides too
 SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True),
           ((16, 3, 256, 256), False), ((16, 3, 256, 256), True)]
-
-
-def _shifted(t, dev):
-  """A contiguous copy of t that starts 4 bytes into its buffer: a view no 16-byte access may touch."""
-  buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=dev)
-  view = buf[1:].view(t.shape)
-  view.copy_(t)
-  assert view.is_contiguous() and view.data_ptr() % 16 == 4
-  return view
-
-
-def _place(t, dev, shifted):
-  return _shifted(t, dev) if shifted else t.to(dev).clone()
 
 
 def _launch(lib, x, score, d_prev, row, clip, x_out, d_out):
@@ -77,15 +63,6 @@ def _restate(x, score, d_prev, row, clip):
   return A * x + B * D, d, abs(A) * x.abs() + abs(B) * b_D, b_d
 
 
-def _within(got, want, mag, k, what):
-  """|got - want| <= k u B, element by element; returns the worst ratio err / (u B)."""
-  err = (got.detach().cpu().double() - want).abs()
-  assert torch.isfinite(err).all(), f'{what}: non-finite result'
-  units = float((err / (U * mag).clamp_min(1e-300)).max())
-  assert bool((err <= k * U * mag).all()), f'{what}: {units:.2f} u B exceeds {k}'
-  return units
-
-
 @pytest.fixture(scope='module')
 def operands():
   """x, score, d_prev per shape, float32 on the host, and their float64 copies: drawn once."""
@@ -97,35 +74,35 @@ def operands():
   return out
 
 
-@pytest.mark.parametrize('shape,shifted', SHAPES, ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else ('entered-one-in' if v else 'aligned'))
+@pytest.mark.parametrize('shape,shifted', SHAPES, ids=case_id)
 def test_kernel_matches_float64(hip_lib, operands, shape, shifted):
   dev = torch.device('cuda:0')
   (x, s, p), (x64, s64, p64) = operands[shape]
-  xd, sd, pd = (_place(t, dev, shifted) for t in (x, s, p))
+  xd, sd, pd = (place(t, dev, shifted) for t in (x, s, p))
   worst_x = worst_d = 0.0
   for use_prev, use_dout in itertools.product((True, False), (True, False)):
     row = ROW if use_prev else ROW[:2] + (0.,) + ROW[3:]
     outs = {}
     for name, clip in CLIPS.items():
       want_x, want_d, b_x, b_d = _restate(x64, s64, p64 if use_prev else None, row, clip)
-      x_out = _place(torch.full(shape, float('nan')), dev, shifted)
-      d_out = _place(torch.full(shape, float('nan')), dev, shifted) if use_dout else None
+      x_out = place(torch.full(shape, float('nan')), dev, shifted)
+      d_out = place(torch.full(shape, float('nan')), dev, shifted) if use_dout else None
       _launch(hip_lib, xd, sd, pd if use_prev else None, row, clip, x_out, d_out)
       what = f'dpm_update {shape} shifted={shifted} d_prev={use_prev} d_out={use_dout} clip={name}'
-      worst_x = max(worst_x, _within(x_out, want_x, b_x, K_X, what + ' x_out'))
+      worst_x = max(worst_x, within(x_out, want_x, b_x, K_X, what + ' x_out'))
       if use_dout:
-        worst_d = max(worst_d, _within(d_out, want_d, b_d, K_D, what + ' d_out'))
+        worst_d = max(worst_d, within(d_out, want_d, b_d, K_D, what + ' d_out'))
         if clip is not None:
           assert float(d_out.min()) >= clip[0] and float(d_out.max()) <= clip[1]
       outs[name] = (x_out, d_out)
       # state and history kept in place: bit-identical to the separate-buffer form
-      xa, pa = _place(x, dev, shifted), _place(p, dev, shifted)
+      xa, pa = place(x, dev, shifted), place(p, dev, shifted)
       _launch(hip_lib, xa, sd, pa if use_prev else None, row, clip, xa, pa if (use_prev and use_dout) else d_out)
       assert torch.equal(xa, x_out), what + ': x_out = x differs from the separate-buffer form'
       if use_prev and use_dout:
         assert torch.equal(pa, d_out), what + ': d_out = d_prev differs from the separate-buffer form'
     # bounds of -inf / +inf leave every finite d bit-identical: the same bits as bounds no fp32 number reaches
-    x_max, d_max = _place(torch.full(shape, float('nan')), dev, shifted), _place(torch.full(shape, float('nan')), dev, shifted)
+    x_max, d_max = place(torch.full(shape, float('nan')), dev, shifted), place(torch.full(shape, float('nan')), dev, shifted)
     _launch(hip_lib, xd, sd, pd if use_prev else None, row, (-FLT_MAX, FLT_MAX), x_max, d_max)
     for name in ('off', 'inf'):
       assert torch.equal(outs[name][0], x_max), f'{shape}: clip {name} is not bit-identical to an unreachable clip'
@@ -255,30 +232,15 @@ def test_loop_with_a_closed_form_score(st, hip_lib, gaussian_reference, family):
 
 
 # ---- the sampler on the tiny networks -----------------------------------------------------------------------------------
-_built = {}
-
-
 def _setup(st, lib, family):
-  """(cfg, sde, model, restated family) of a tiny network, built once per family."""
-  if family not in _built:
-    cfg = tiny_config(st, family)
-    cfg.sampling.method, cfg.sampling.dpm_steps, cfg.sampling.noise_removal = 'dpm_solver', 6, True
-    cfg, _, sde, model, _ = build_pair(st, cfg, lib)
-    model.eval()
-    fam = R.VE(sde.sigma_min, sde.sigma_max) if isinstance(sde, st.sde_lib.VESDE) else R.VP(sde.beta_0, sde.beta_1)
-    _built[family] = (cfg, sde, model, fam)
-  return _built[family]
-
-
-def _shape(cfg):
-  return (2, cfg.data.num_channels, cfg.data.image_size, cfg.data.image_size)
+  """(cfg, sde, model, restated family) of a tiny network."""
+  cfg, sde, model = setup(st, lib, family, dict(method='dpm_solver', dpm_steps=6, noise_removal=True))
+  fam = R.VE(sde.sigma_min, sde.sigma_max) if isinstance(sde, st.sde_lib.VESDE) else R.VP(sde.beta_0, sde.beta_1)
+  return cfg, sde, model, fam
 
 
 def _sampler(st, cfg, sde, **options):
-  c = copy.deepcopy(cfg)
-  for k, v in options.items():
-    setattr(c.sampling, k, v)
-  return st.sampling.get_sampling_fn(c, sde, _shape(c), st.datasets.get_data_inverse_scaler(c), EPS)
+  return sampler(st, cfg, sde, EPS, **options)
 
 
 def _by_hand(st, cfg, sde, model, fam, order, denoise, dtype, seed, clip=None):

@@ -10,12 +10,15 @@ k = 8 and k = 32, gamma_k = k 2^-24.
 Worst measured error over the cases below, in units of 2^-24 B (MI355X): 2.70 without the mix, 2.21 with it.
 """
 import ctypes
+import functools
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
+import _stream_util
+from _stream_util import place
 from _util import call
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +26,7 @@ pytestmark = pytest.mark.gpu
 K_PLAIN, K_MIX = 8, 32
 SHAPES = [(2, 3, 8, 8), (3, 3, 5, 7), (2, 1, 6, 10), (1, 4, 4, 4)]     # 16-byte path, scalar tail, one channel, four channels
 MASK_FORMS = ['NC', '11', 'N1', '1C']
+within = functools.partial(_stream_util.within, show=True)      # every comparison prints its worst ratio
 
 
 def matrices():
@@ -52,16 +56,6 @@ def magnitude(x, data, z, mask, a, s, mix=None, unmix=None):
   return restate(ab(x), ab(data), ab(z), mask, ab(a), ab(s), ab(mix), ab(unmix))
 
 
-def within(got, want, mag, k, what):
-  """|got - want| <= k 2^-24 B, element by element; prints and returns the worst ratio err / (2^-24 B)."""
-  err = (got.detach().cpu().double() - want).abs()
-  assert torch.isfinite(err).all(), f'{what}: non-finite result'
-  units = float((err / (2.0 ** -24 * mag).clamp_min(1e-300)).max())
-  print(f'{what}: worst error {units:.2f} x 2^-24 B (bound {k})')
-  assert bool((err <= k * 2.0 ** -24 * mag).all()), f'{what}: {units:.2f} x 2^-24 B exceeds {k}'
-  return units
-
-
 def _operands(shape, form, soft, seed):
   N, C, H, W = shape
   g = torch.Generator().manual_seed(seed)
@@ -72,19 +66,10 @@ def _operands(shape, form, soft, seed):
               s=torch.rand(N, generator=g) * 3 + 0.05)
 
 
-def _shifted(t, dev):
-  """A contiguous copy of t that starts 4 bytes into its buffer: a sliced view no 16-byte access may touch."""
-  buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=dev)
-  view = buf[1:].view(t.shape)
-  view.copy_(t)
-  assert view.is_contiguous() and view.data_ptr() % 16 == 4
-  return view
-
-
 def _run(lib, o, dev, use_z, use_mean, inplace, mix, shifted=False, x='x'):
   N, C, H, W = o['x'].shape
   d = {k: v.to(dev) for k, v in o.items()}
-  xin = _shifted(o[x], dev) if shifted else d[x].clone()
+  xin = place(o[x], dev, shifted)
   out = xin if inplace else torch.full_like(d['x'], float('nan'))
   mean = torch.full_like(d['x'], float('nan')) if use_mean else None
   call(lib, 'impute_f32', xin, d['data'], d['z'] if use_z else None, d['mask'], d['a'], d['s'],

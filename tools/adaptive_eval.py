@@ -7,37 +7,21 @@ trained score is smoother), and sample quality is not measured here.  Writes pro
 
     python tools/adaptive_eval.py --workload celebahq256 --batch 16
 """
-import argparse
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
 
-import bench
-import soft_truncation_amd as st
+import _sampler_eval as E
+from _sampler_eval import st
 
-ap = argparse.ArgumentParser()
-ap.add_argument('--workload', default='celebahq256', choices=sorted(bench.WORKLOADS))
-ap.add_argument('--batch', type=int, default=16)
+ap = E.parser('adaptive_eval.txt')
 ap.add_argument('--rtols', type=float, nargs='+', default=[0.01, 0.05])
 ap.add_argument('--pc-steps', type=int, default=1000, help='N of the predictor-corrector run (0: skip it)')
-ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'adaptive_eval.txt'))
 args = ap.parse_args()
-cfg_name, _, desc = bench.WORKLOADS[args.workload]
-cfg = st.configs.get_config(cfg_name)
-device = torch.device('cuda', 0)
-cfg.device = device
-sde = st.sde_lib.get_sde(cfg, None)
-torch.manual_seed(0)
-model = st.models.utils.create_model(cfg, sde)
-model.eval()
+cfg_name, desc, cfg, device, sde, model, shape = E.workload(args)
 ada, mutils, stk_lib = st.adaptive_sde, st.models.utils, st.engine.lib
 lib = ada._library()
-B, C, H = args.batch, cfg.data.num_channels, cfg.data.image_size
-shape = (B, C, H, H)
+B, C, H, _ = shape
 n = C * H * H
 eps = 1e-3
 atol = ada.default_atol(cfg)
@@ -68,37 +52,20 @@ def launches_alone(reps=200):
   }
   out = []
   for name, (tensors, call) in calls.items():
-    for _ in range(10):
-      call()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-      call()
-    e1.record()
-    e1.synchronize()
-    us = 1e3 * e0.elapsed_time(e1) / reps
     moved = 4 * x.numel() * tensors
-    out.append((name, us, moved, moved / (us * 1e-6) / 1e12))
+    us, tbs = E.launches_alone(call, reps, moved)
+    out.append((name, us, moved, tbs))
   assert int(accept.sum()) == B
   return out
 
 
-def evaluation(reps=5):
+def evaluation():
   score_fn = mutils.get_score_fn(cfg, sde, model, train=False, continuous=cfg.training.continuous)
-  x = sde.prior_sampling(shape).to(device)
-  t = torch.ones(B, device=device) * 0.5
-  for _ in range(2):
-    score_fn(x, t)
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  for _ in range(reps):
-    score_fn(x, t)
-  torch.cuda.synchronize()
-  return 1e3 * (time.perf_counter() - t0) / reps
+  return E.evaluation(score_fn, sde, shape, device)
 
 
 def adaptive_run(rtol):
-  with torch.no_grad(), mutils.frozen_weights(model):
+  with mutils.sampling_run(model):
     score_fn = mutils.get_score_fn(cfg, sde, model, train=False, continuous=cfg.training.continuous)
     torch.manual_seed(1)
     x = sde.prior_sampling(shape).to(device).contiguous()
@@ -129,7 +96,7 @@ def pc_run(N):
 
 lines = [f'{desc}, batch {B}: adaptive-step SDE sampler, atol {atol}, h_init 0.01, safety 0.9, exponent 0.9, eps = {eps}; random '
          f'weights; wall time over a device synchronisation, everything in one job on one box.']
-with torch.no_grad(), mutils.frozen_weights(model):
+with mutils.sampling_run(model):
   total = 0.
   for name, us, moved, tbs in launches_alone():
     total += us
@@ -144,8 +111,4 @@ for rtol in args.rtols:
 if args.pc_steps:
   wall, nfe = pc_run(args.pc_steps)
   lines.append(f'predictor-corrector sampler at N = {args.pc_steps} in the same job: nfe = {nfe}, {wall:.2f} s')
-text = '\n'.join(lines)
-print(text)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, 'w') as f:
-  f.write(text + '\n')
+E.write(lines, args.out)

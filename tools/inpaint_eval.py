@@ -7,38 +7,22 @@ also timed alone, with and without the colour mix.  Writes profiles/controllable
 
     python tools/inpaint_eval.py --workload celebahq256 --batch 16 --iters 10
 """
-import argparse
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
 
-import bench
-import soft_truncation_amd as st
+import _sampler_eval as E
+from _sampler_eval import st
 
-ap = argparse.ArgumentParser()
-ap.add_argument('--workload', default='celebahq256', choices=sorted(bench.WORKLOADS))
-ap.add_argument('--batch', type=int, default=16)
+ap = E.parser('controllable_eval.txt')
 ap.add_argument('--iters', type=int, default=10)
 ap.add_argument('--precision', default='fp32', choices=('fp32', 'fp16'))
-ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'controllable_eval.txt'))
 args = ap.parse_args()
-cfg_name, _, desc = bench.WORKLOADS[args.workload]
-cfg = st.configs.get_config(cfg_name)
-device = torch.device('cuda', 0)
-cfg.device = device
-sde = st.sde_lib.get_sde(cfg, None)
-torch.manual_seed(0)
-model = st.models.utils.create_model(cfg, sde)
-model.eval()
+_, desc, cfg, device, sde, model, (B, C, H, _) = E.workload(args)
 cg, S = st.controllable_generation, st.sampling
 lib = cg._library()
-predict, correct = cg._updates(cfg, sde, S.get_predictor('reverse_diffusion'), S.get_corrector('langevin'), cfg.sampling.snr, 1,
-                               False, cfg.training.continuous)
-B, C, H = args.batch, cfg.data.num_channels, cfg.data.image_size
+predict, correct = S.pc_updates(cfg, sde, S.get_predictor('reverse_diffusion'), S.get_corrector('langevin'), cfg.sampling.snr, 1,
+                                False, cfg.training.continuous)
 data = torch.rand(B, C, H, H, device=device)
 mask = torch.zeros(1, 1, H, H, device=device)
 mask[..., : H // 2, :] = 1.
@@ -75,22 +59,13 @@ def kernel_alone(mix, n=200):
   out, mean = torch.empty_like(x), torch.empty_like(x)
   a = s = torch.ones(B, device=device)
   m, f = (cg.get_mask(x[:1]), (1, 3)) if mix else (mask, form)
-  for _ in range(10):
-    cg._impute(lib, x, data, z, m, f, a, s, out, mean, mix)
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for _ in range(n):
-    cg._impute(lib, x, data, z, m, f, a, s, out, mean, mix)
-  e1.record()
-  e1.synchronize()
-  us = 1e3 * e0.elapsed_time(e1) / n
   moved = 4 * (5 * x.numel() + m.numel())            # x, data, z read, x and x_mean written, the mask read once
-  return us, moved / (us * 1e-6) / 1e12
+  return E.launches_alone(lambda: cg._impute(lib, x, data, z, m, f, a, s, out, mean, mix), n, moved)
 
 
 lines = [f'{desc} [{args.precision}], batch {B}: reverse diffusion + Langevin (1 step), t = 0.5, {args.iters} iterations after 3 '
          f'warm-ups, weights prepared once; wall time over a device synchronisation, modes alternated in one job on one box.']
-with torch.no_grad(), st.models.utils.frozen_weights(model), st.models.utils.precision(model, args.precision):
+with st.models.utils.sampling_run(model, args.precision):
   runs = [(timed(plain, args.iters), timed(inpaint, args.iters)) for _ in range(2)]
   alone = [(name, kernel_alone(mix)) for name, mix in (('inpainting (no colour mix)', None), ('colourisation (3x3 mix)', cg._MIX_BLEND))]
 p, i = min(r[0] for r in runs), min(r[1] for r in runs)
@@ -101,8 +76,4 @@ lines.append(f'stk_impute_f32 alone on the [{B},{C},{H},{H}] state (200 back-to-
              f'[1,1,H,W] / [1,3,H,W] mask):')
 for name, (us, tbs) in alone:
   lines.append(f'  {name}: {us:.1f} us per launch, {tbs:.2f} TB/s of the 20 B per element it moves')
-text = '\n'.join(lines)
-print(text)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, 'w') as f:
-  f.write(text + '\n')
+E.write(lines, args.out)

@@ -7,38 +7,22 @@ weights: the times do not depend on them, and sample quality is not measured her
 
     python tools/solver_eval.py --workload celebahq256 --batch 16 --steps 20
 """
-import argparse
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
 
-import bench
-import soft_truncation_amd as st
+import _sampler_eval as E
+from _sampler_eval import st
 
-ap = argparse.ArgumentParser()
-ap.add_argument('--workload', default='celebahq256', choices=sorted(bench.WORKLOADS))
-ap.add_argument('--batch', type=int, default=16)
+ap = E.parser('dpm_solver_eval.txt')
 ap.add_argument('--steps', type=int, default=20)
 ap.add_argument('--order', type=int, default=2)
 ap.add_argument('--runs', type=int, default=2)
-ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'dpm_solver_eval.txt'))
 args = ap.parse_args()
-cfg_name, _, desc = bench.WORKLOADS[args.workload]
-cfg = st.configs.get_config(cfg_name)
-device = torch.device('cuda', 0)
-cfg.device = device
-sde = st.sde_lib.get_sde(cfg, None)
-torch.manual_seed(0)
-model = st.models.utils.create_model(cfg, sde)
-model.eval()
+_, desc, cfg, device, sde, model, shape = E.workload(args)
 dpm, mutils = st.dpm_solver, st.models.utils
 lib = dpm._library()
-B, C, H = args.batch, cfg.data.num_channels, cfg.data.image_size
-shape = (B, C, H, H)
+B, C, H, _ = shape
 eps = 1e-3
 schedule = dpm.dpm_schedule(sde, args.steps, order=args.order, eps=eps)
 HBM_TBS = 8.0
@@ -52,31 +36,14 @@ def kernel_alone(second_order, n=200):
   out = torch.empty_like(x)
   row = (1.3, 0.7, 0.45 if second_order else 0., 0.8, 0.35)
   bounds = dpm._clip_bounds(None)
-  for _ in range(10):
-    dpm._update(lib, x, s, hist, row, bounds, out, hist)
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for _ in range(n):
-    dpm._update(lib, x, s, hist, row, bounds, out, hist)
-  e1.record()
-  e1.synchronize()
-  us = 1e3 * e0.elapsed_time(e1) / n
   moved = 4 * x.numel() * (5 if second_order else 3)
-  return us, moved, moved / (us * 1e-6) / 1e12
+  us, tbs = E.launches_alone(lambda: dpm._update(lib, x, s, hist, row, bounds, out, hist), n, moved)
+  return us, moved, tbs
 
 
-def evaluation(n=5):
+def evaluation():
   score_fn = mutils.get_score_fn(cfg, sde, model, train=False, continuous=cfg.training.continuous)
-  x = sde.prior_sampling(shape).to(device)
-  t = torch.ones(B, device=device) * 0.5
-  for _ in range(2):
-    score_fn(x, t)
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  for _ in range(n):
-    score_fn(x, t)
-  torch.cuda.synchronize()
-  return 1e3 * (time.perf_counter() - t0) / n
+  return E.evaluation(score_fn, sde, shape, device)
 
 
 def whole_run(precision):
@@ -93,7 +60,7 @@ def whole_run(precision):
 
 lines = [f'{desc}, batch {B}: DPM-Solver++ order {args.order}, {args.steps} steps + the data prediction at eps = {eps}, logsnr '
          f'spacing; random weights; wall time over a device synchronisation, everything in one job on one box.']
-with torch.no_grad(), mutils.frozen_weights(model):
+with mutils.sampling_run(model):
   for name, second in (('second-order step (x, score, d_prev read; x, d written: 20 B per element)', True),
                        ('first-order step (x, score read; x written: 12 B per element)', False)):
     us, moved, tbs = kernel_alone(second)
@@ -115,8 +82,4 @@ lines.append(f'fp16 against fp32 result (same prior draw, after the inverse scal
 lines.append('recorded for comparison (README, profiles/r06_sampler_eval_celebahq256.txt, profiles/fp16_sampler_eval.txt; NCSN++ 256^2, '
              'batch 16): predictor-corrector sampling 78.2 s at N = 1000, 156.6 s at N = 2000 (107.7 s in fp16 mode), 38.5 ms per '
              'network evaluation')
-text = '\n'.join(lines)
-print(text)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, 'w') as f:
-  f.write(text + '\n')
+E.write(lines, args.out)
