@@ -1,5 +1,5 @@
 """Conditional predictor-corrector samplers: inpainting and colourisation (score_sde's controllable_generation.py, which
-the reference dropped from its fork).
+the reference dropped from its fork), and super-resolution, the member of that family upstream does not spell out.
 
 ``get_pc_inpainter`` / ``get_pc_colorizer`` keep upstream's names, update rules and loop; like ``sampling.get_pc_sampler``
 of this package they take ``config`` first.  At each of the N times of ``linspace(sde.T, eps, sde.N)`` the corrector
@@ -20,6 +20,16 @@ The network evaluations follow the engine's conventions exactly as ``get_pc_samp
 prepared once per run (``models.utils.frozen_weights``), ``config.sampling.precision`` ('fp16' applies to the network only:
 the imputation is always fp32).  Everything runs on the device: host tensors raise the package's device error, there is
 no CPU path; a library without include/stk_impute.h is refused when the sampler is built.
+
+``get_pc_superresolver`` samples a full-resolution image given its r x r block means ``low`` [N,C,H/r,W/r] (``block_mean`` makes
+one from an image), r = ``factor`` in {2, 4, 8, 16}.  It is the colouriser's construction with the orthonormal transform
+acting on the r^2 pixels of a block instead of the 3 channels of a pixel, the kept coefficient being the block's DC term:
+r times the block mean, so noise of std ``s`` on the data is ``s / r`` on the mean.  The loop and the conventions are those
+above.  A half-step (``superres_update``) is, in this order: the unconditional update; ``sde.marginal_prob`` per image;
+ONE ``torch.randn`` of ``low``'s shape (fp32, on x's device); ONE launch of ``stk_superres_f32`` (include/stk_superres.h,
+csrc/superres.hip), which shifts every pixel of a block by ``(a low + (s / r) z) - blockmean(x)``, and by
+``a low - blockmean(x)`` for ``x_mean``.  That draw order, too, is part of the interface.  A library without
+include/stk_superres.h is refused when the sampler is built.  Sample quality is unmeasured.
 """
 import ctypes
 
@@ -239,3 +249,123 @@ def get_pc_colorizer(config, sde, predictor, corrector, inverse_scaler, snr, n_s
     return _run(config, sde, lib, model, gray, get_mask(gray[:1]), (1, 3), _MIX_BLEND, updates, inverse_scaler, denoise, eps)
 
   return pc_colorizer
+
+
+FACTORS = (2, 4, 8, 16)      # the block sizes of include/stk_superres.h
+
+
+def _superres_library():
+  return mutils.require('has_superres', 'stk_superres.h', 'stk_superres_f32 and stk_block_mean_f32',
+                        'the super-resolution sampler needs')
+
+
+def _check_factor(factor):
+  if isinstance(factor, bool) or not isinstance(factor, int) or factor not in FACTORS:
+    raise ValueError(f'factor must be one of {FACTORS}, got {factor!r}')
+  return factor
+
+
+def superres_shape(low, factor):
+  """The [N,C,H,W] shape of the image a measurement `low` [N,C,H/r,W/r] (float32) of block size r = `factor` belongs to.
+  Host-only: reads shapes and dtypes, so meta tensors do."""
+  r = _check_factor(factor)
+  if low.dim() != 4 or low.dtype != torch.float32:
+    raise ValueError(f'low must be a float32 [N,C,H/{r},W/{r}] tensor, got {low.dtype} {tuple(low.shape)}')
+  N, C, h, w = low.shape
+  if min(N, C, h, w) < 1:
+    raise ValueError(f'low must not be empty, got {tuple(low.shape)}')
+  return N, C, h * r, w * r
+
+
+def _check_low(low, factor, shape, what):
+  """`low` is the measurement of an [N,C,H,W] = `shape` image at this factor."""
+  full = superres_shape(low, factor)
+  if full != tuple(shape):
+    raise ValueError(f'low {tuple(low.shape)} at factor {factor} stands for an image of {full}, not for {what} {tuple(shape)}')
+
+
+def _superres(lib, x, low, z, a, s, r, x_out, x_mean):
+  """One launch of stk_superres_f32 on contiguous fp32 device tensors."""
+  N, C, H, W = x.shape
+  with stk_lib.device_guard(x.device):
+    lib.superres_f32(x.data_ptr(), low.data_ptr(), z.data_ptr() if z is not None else None, a.data_ptr(), s.data_ptr(),
+                     x_out.data_ptr(), x_mean.data_ptr() if x_mean is not None else None, N, C, H, W, r,
+                     stk_lib.stream_ptr(x.device))
+  return x_out
+
+
+def block_mean(images, factor):
+  """The r x r block means of `images` [N,C,H,W] -> [N,C,H/r,W/r], r = `factor`: the measurement the super-resolution
+  sampler takes (one launch of stk_block_mean_f32, the sum the data-consistency step itself takes)."""
+  lib = _superres_library()
+  _backend.check(images, lib)
+  _check_state(images, 'images')
+  r = _check_factor(factor)
+  N, C, H, W = images.shape
+  if N * C == 0 or H == 0 or W == 0 or H % r or W % r:
+    raise ValueError(f'images {tuple(images.shape)} do not divide into {r} x {r} blocks')
+  x = images.contiguous()
+  out = torch.empty((N, C, H // r, W // r), dtype=torch.float32, device=x.device)
+  with stk_lib.device_guard(x.device):
+    lib.block_mean_f32(x.data_ptr(), out.data_ptr(), N * C, H, W, r, stk_lib.stream_ptr(x.device))
+  return out
+
+
+def _superres_half_step(lib, update_fn, sde, model, low, r, x, t):
+  """update, marginal_prob, one randn of low's shape, one launch (module docstring).  low: contiguous and checked."""
+  vec_t = torch.ones(low.shape[0], device=low.device) * t
+  xu, _ = update_fn(x, vec_t, model=model)
+  a, s = _coefficients(sde, low, vec_t)
+  z = torch.randn(low.shape, dtype=torch.float32, device=xu.device)
+  xu = xu.contiguous()
+  # as in _half_step: overwrite the update's own output, never the caller's tensor
+  out = xu if xu.data_ptr() != x.data_ptr() else torch.empty_like(xu)
+  x_mean = torch.empty_like(xu)
+  _superres(lib, xu, low, z, a, s, r, out, x_mean)
+  return out, x_mean
+
+
+def superres_update(update_fn, sde, model, low, factor, x, t):
+  """One super-resolution half-step at time t around ``update_fn(x, vec_t, model=model)`` -> (x, x_mean): the r x r block
+  means of the state become ``a low + (s / r) z`` (``a low`` for x_mean), what the update gave is kept otherwise.  Draw
+  order: the update's own noise, then ONE ``torch.randn`` of low's shape on x's device.  `x` is not written."""
+  lib = _superres_library()
+  for v in (x, low):
+    _backend.check(v, lib)
+  _check_state(x, 'x')
+  _check_low(low, factor, x.shape, 'the state')
+  with torch.no_grad():
+    return _superres_half_step(lib, update_fn, sde, model, low.contiguous(), factor, x, t)
+
+
+def get_pc_superresolver(config, sde, predictor, corrector, inverse_scaler, snr, n_steps=1, probability_flow=False,
+                         continuous=False, denoise=True, eps=1e-5, factor=4):
+  """``pc_superresolver(model, low)`` -> [N,C,H,W]: PC sampling of an image whose `factor` x `factor` block means are `low`
+  [N,C,H/factor,W/factor], float32 in the model's data scale; H = W = ``config.data.image_size``."""
+  lib = _superres_library()
+  r = _check_factor(factor)
+  updates = pc_updates(config, sde, predictor, corrector, snr, n_steps, probability_flow, continuous)
+  precision = mutils.sampling_precision(config)      # a bad config.sampling.precision fails here, not in the loop
+  size, channels = config.data.image_size, config.data.num_channels
+  if size % r:
+    raise ValueError(f'config.data.image_size = {size} does not divide into {r} x {r} blocks')
+
+  def pc_superresolver(model, low):
+    _backend.check(low, lib)
+    shape = (superres_shape(low, r)[0], channels, size, size)
+    _check_low(low, r, shape, 'the model\'s input')
+    low = low.contiguous()
+    predict, correct = updates
+    with mutils.sampling_run(model, precision):
+      # the initial state: the prior with its block means replaced by low's (a = 1, no noise)
+      prior = sde.prior_sampling(shape).to(low.device).contiguous()
+      one = _ones(low)
+      x = x_mean = _superres(lib, prior, low, None, one, one, r, prior, None)
+      timesteps = torch.linspace(sde.T, eps, sde.N)
+      for i in tqdm(range(sde.N)):
+        t = timesteps[i]
+        x, x_mean = _superres_half_step(lib, correct, sde, model, low, r, x, t)
+        x, x_mean = _superres_half_step(lib, predict, sde, model, low, r, x, t)
+      return inverse_scaler(x_mean if denoise else x)
+
+  return pc_superresolver

@@ -164,6 +164,11 @@ SIGNATURES_ADAPTIVE = {
   'stk_sde_commit_f32': [P, P, P, P, P, P, F, F, F, P, L, P, P, P, P, I, L, S],
 }
 _RESTYPE_ADAPTIVE = {'stk_sde_ws_bytes': c_long}
+# include/stk_superres.h: the data-consistency pass of the super-resolution sampler, and the block means it measures with.
+SIGNATURES_SUPERRES = {
+  'stk_superres_f32': [P, P, P, P, P, P, P, I, I, I, I, I, S],
+  'stk_block_mean_f32': [P, P, L, I, I, I, S],
+}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -181,6 +186,7 @@ OPTIONAL_HEADERS = (
   Header('has_impute', 'include/stk_impute.h', SIGNATURES_IMPUTE, {}, ()),
   Header('has_solver', 'include/stk_solver.h', SIGNATURES_SOLVER, {}, ()),
   Header('has_adaptive', 'include/stk_adaptive.h', SIGNATURES_ADAPTIVE, _RESTYPE_ADAPTIVE, ()),
+  Header('has_superres', 'include/stk_superres.h', SIGNATURES_SUPERRES, {}, ()),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
