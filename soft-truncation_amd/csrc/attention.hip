@@ -37,14 +37,12 @@
 #include <utility>
 
 #include "common.h"
+#include "split.h"
 
 namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef short s4 __attribute__((__vector_size__(8)));
 typedef __attribute__((address_space(3))) s4 lds_s4;
 
@@ -83,23 +81,10 @@ __global__ __launch_bounds__(1024) void attn_amax_kernel(AmaxArgs a) {          
   }
 }
 
-// power of two s with m s in [2^13, 2^14) (1 for m = 0) -- the same rule as x2::pow2_scale_of (conv_x2.h)
-__device__ __forceinline__ float pow2_scale_of(float m) {
-  const int be = (int)((__float_as_uint(m) >> 23) & 0xffu);
-  if (be == 0) return 1.f;
-  const int se = min(max(127 + 13 - (be - 127), 1), 254);
-  return __uint_as_float((unsigned)se << 23);
-}
-__device__ __forceinline__ unsigned pack_h2(float a, float b) {
-  const halfx2 v = {(_Float16)a, (_Float16)b};                  // round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float lo_part(float v) { return v - (float)(_Float16)v; }      // exact
-// four scaled fp32 values -> hi and lo fp16 quadruples (8 bytes each)
-__device__ __forceinline__ void split4(const float (&v)[4], u32x2& hi, u32x2& lo) {
-  hi = u32x2{pack_h2(v[0], v[1]), pack_h2(v[2], v[3])};
-  lo = u32x2{pack_h2(lo_part(v[0]), lo_part(v[1])), pack_h2(lo_part(v[2]), lo_part(v[3]))};
-}
+using split2::pow2_scale_of;      // the split rule itself: split.h
+using split2::pack_h2;
+using split2::lo_part;
+using split2::split4;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }

@@ -28,6 +28,7 @@
 // {4 g + e, 16 + 4 g + e} of column r, and these 8 values ARE its B fragment of the next contraction (k order permuted
 // consistently: the A operand reads the same 4 + 4 positions from a PF row).  So p and ds never leave the registers.
 #include "common.h"
+#include "split.h"
 #include "stk_attention_long.h"
 
 namespace {
@@ -70,13 +71,7 @@ __global__ __launch_bounds__(1024) void amax_kernel(AmaxArgs a) {
   }
 }
 
-// power of two s with m s in [2^13, 2^14) (1 for m = 0) -- the rule of attention.hip and conv_x2.h
-__device__ __forceinline__ float pow2_scale_of(float m) {
-  const int be = (int)((__float_as_uint(m) >> 23) & 0xffu);
-  if (be == 0) return 1.f;
-  const int se = min(max(127 + 13 - (be - 127), 1), 254);
-  return __uint_as_float((unsigned)se << 23);
-}
+using split2::pow2_scale_of;      // the split rule itself: split.h
 // scale of a tensor from its 256-entry record, computed by every wave on its own
 __device__ __forceinline__ float rec_scale(const float* rec, int lane) {
   float m = fmaxf(fmaxf(rec[lane], rec[lane + 64]), fmaxf(rec[lane + 128], rec[lane + 192]));

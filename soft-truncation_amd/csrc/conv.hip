@@ -19,6 +19,7 @@
 // split-K: each slice writes its partial tile to a scratch slab and a second kernel sums the slabs in a
 // fixed order into dw (deterministic -- no float atomics).
 #include "igemm.h"
+#include "split.h"
 #include "stk_fp16.h"
 #include "stk_fp16_train.h"
 

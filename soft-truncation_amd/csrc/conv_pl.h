@@ -15,7 +15,7 @@
 // tap-dependent pixel shift: the B loader becomes the same four 16-byte copies per thread as the weight loader, with
 // the halo zeros still coming from the buffer range check (offset bit 31).
 //
-// scale is the power of two that puts the tensor's |x| bound in [2^13, 2^14) (x2::pow2_scale_of): the bound is either
+// scale is the power of two that puts the tensor's |x| bound in [2^13, 2^14) (split2::pow2_scale_of, split.h): the bound is either
 // the measured maximum (256 partial maxima, as for the fp32 path) or an a-priori one (GroupNorm outputs:
 // gn_bound_kernel in groupnorm.hip), stored in the same 256-float "amax" record that the consumer reads.
 #pragma once

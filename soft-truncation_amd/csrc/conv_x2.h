@@ -23,11 +23,13 @@
 // reads of the same 32 x (128 + halo) activation patch hit L1 / L2.
 #pragma once
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
 
 namespace x2 {
+
+using split2::pow2_scale_of;      // the split rule itself: split.h (included by conv.hip at file scope)
+using split2::pack_h2;
+using split2::lo_part;
 
 constexpr int KC = 32;
 constexpr int PITCH = 80;              // bytes per LDS row: 32 fp16 + 16 bytes of padding
@@ -89,13 +91,6 @@ __global__ __launch_bounds__(AMAX_THREADS) void amax_partial_kernel(const float*
   }
 }
 
-// power of two s with m * s in [2^13, 2^14) (1 for m = 0)
-__device__ __forceinline__ float pow2_scale_of(float m) {
-  const int be = (int)((__float_as_uint(m) >> 23) & 0xffu);          // m = 1.f * 2^(be - 127)
-  if (be == 0) return 1.f;
-  const int se = min(max(127 + 13 - (be - 127), 1), 254);
-  return __uint_as_float((unsigned)se << 23);
-}
 // block-wide maximum of `count` (256 or 512) partials; all 256 threads call it; `red` = 4 floats of LDS
 __device__ __forceinline__ float block_amax(const float* __restrict__ part, int count, float* red) {
   float m = part[threadIdx.x];
@@ -124,12 +119,6 @@ struct LateAmax {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   }
 };
-
-__device__ __forceinline__ unsigned pack_h2(float lo, float hi) {
-  const halfx2 v = {(_Float16)lo, (_Float16)hi};                      // round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float lo_part(float v) { return v - (float)(_Float16)v; }   // exact
 
 // ---- weight preparation ---------------------------------------------------------------------------------------------
 // A prepared block = [HEADER bytes: partial |w| maxima][2 planes: Wp[split][k / 32][tap][row (pad 128)][k % 32] fp16 of scale*W],

@@ -26,7 +26,14 @@
 //  * backward: per (sample, group) workgroup computes the per-channel partial sums of d(gamma),
 //    d(beta) into a [N,C,2] scratch and dx; a second tiny kernel folds the scratch over N.  Groups of up to 16384
 //    elements (every group of the score network) take the flat register-resident variant.
+//  * The arithmetic of one element is written once and shared by the kernels: gn_seed, gn_act_out / gn_out4 (affine step,
+//    activation, dropout), gn_du (backward), gn_bound_load / gn_bound_fold (the a-priori bound of |y|), gn_amax_wave /
+//    gn_amax_commit (block maxima into a scale record).  The kernels that write planes split their output by the rule of
+//    split.h, the one the convolutions that read them assume.
+#include <type_traits>
+
 #include "common.h"
+#include "split.h"
 
 namespace {
 
@@ -69,6 +76,18 @@ __device__ __forceinline__ void group_segments(const GnArgs& a, int n, int g, Se
   }
 }
 
+// Channel c of sample n in the (never materialised) concat: its HW run in x1 or x2
+__device__ __forceinline__ const float* gn_chan(const GnArgs& a, int n, int c) {
+  return c < a.C1 ? a.x1 + ((long)n * a.C1 + c) * a.HW : a.x2 + ((long)n * a.C2 + (c - a.C1)) * a.HW;
+}
+// dx = ob * dx + r for one float4 of a gradient (ob == 0 never reads dx): r += ob * (what is there); the caller stores
+__device__ __forceinline__ void gn_dx_accum(float (&r)[4], float ob, const float4* dx) {
+  if (ob != 0.f) {
+    const float4 old = *dx;
+    r[0] += ob * old.x; r[1] += ob * old.y; r[2] += ob * old.z; r[3] += ob * old.w;
+  }
+}
+
 // u * sigmoid(u) = u / (1 + exp(-u)), to the accuracy of the libm expf + IEEE division it replaces (<= ~1.5 ulp in the
 // exponential, a correctly rounded quotient in all but rare cases) at about half their VALU cost (14 instead of ~25
 // instructions per element -- the forward GroupNorm + SiLU kernels are VALU-limited, not HBM-limited, at that cost):
@@ -78,11 +97,10 @@ __device__ __forceinline__ void group_segments(const GnArgs& a, int n, int g, Se
 // The raw hardware forms had been tried and rejected: __expf without the residual (argument scaling costs |u| 2^-24)
 // moved the likelihood ODE's latent to 3e-4 from the reference's fixture, and the bare 1-ulp v_rcp_f32 raised the noise
 // floor of the adaptive solver enough for 10 % more function evaluations.  STK_SILU_LIBM (compile time) restores libm.
-// Dropout: a float4 item is exactly one quad of the counter RNG (stk_rng.h): one 64-bit mix per item, a 16-bit field
-// per element (its flat index is a multiple of 4 because H*W is).
-__device__ __forceinline__ float silu_f(float u) {
+// The exponential and the reciprocal are sigmoid_f's too.
+__device__ __forceinline__ float one_plus_exp_neg(float u) {       // 1 + exp(-u)
 #ifdef STK_SILU_LIBM
-  return u / (1.f + expf(-u));
+  return 1.f + expf(-u);
 #else
   const float NL2E_HI = -1.44269502162933349609375f, NL2E_LO = -1.925963033500011e-8f;     // -log2(e) = HI + LO
   const float t = u * NL2E_HI;
@@ -90,31 +108,29 @@ __device__ __forceinline__ float silu_f(float u) {
   r = __fmaf_rn(u, NL2E_LO, r);
   const float p = __builtin_amdgcn_exp2f(t);
   const float e = fminf(__fmaf_rn(p, r * 0.693147182464599609375f, p), 3.0e38f);          // finite: 1 + e stays finite
-  const float d = 1.f + e;
-  float rc = __builtin_amdgcn_rcpf(d);
-  rc = __fmaf_rn(rc, __fmaf_rn(-d, rc, 1.f), rc);
-  const float q = u * rc;
-  return __fmaf_rn(__fmaf_rn(-q, d, u), rc, q);
+  return 1.f + e;
 #endif
 }
-
-// sigmoid(u) = 1 / (1 + exp(-u)) with the same exponential and the same refined reciprocal as silu_f (backward pass:
-// the libm expf + IEEE division cost ~25 VALU instructions per element of a kernel that has ~20 others).
-__device__ __forceinline__ float sigmoid_f(float u) {
+__device__ __forceinline__ float rcp_refined(float d) {            // 1 / d
 #ifdef STK_SILU_LIBM
-  return 1.f / (1.f + expf(-u));
+  return 1.f / d;
 #else
-  const float NL2E_HI = -1.44269502162933349609375f, NL2E_LO = -1.925963033500011e-8f;
-  const float t = u * NL2E_HI;
-  float r = __fmaf_rn(u, NL2E_HI, -t);
-  r = __fmaf_rn(u, NL2E_LO, r);
-  const float p = __builtin_amdgcn_exp2f(t);
-  const float e = fminf(__fmaf_rn(p, r * 0.693147182464599609375f, p), 3.0e38f);
-  const float d = 1.f + e;
-  float rc = __builtin_amdgcn_rcpf(d);
+  const float rc = __builtin_amdgcn_rcpf(d);
   return __fmaf_rn(rc, __fmaf_rn(-d, rc, 1.f), rc);     // one Newton step: <= 1 ulp of 1 / d
 #endif
 }
+__device__ __forceinline__ float silu_f(float u) {
+  const float d = one_plus_exp_neg(u);
+#ifdef STK_SILU_LIBM
+  return u / d;
+#else
+  const float rc = rcp_refined(d), q = u * rc;
+  return __fmaf_rn(__fmaf_rn(-q, d, u), rc, q);
+#endif
+}
+// sigmoid(u) = 1 / (1 + exp(-u)) with the same exponential and the same refined reciprocal as silu_f (backward pass:
+// the libm expf + IEEE division cost ~25 VALU instructions per element of a kernel that has ~20 others).
+__device__ __forceinline__ float sigmoid_f(float u) { return rcp_refined(one_plus_exp_neg(u)); }
 
 // The activation behind the normalisation, by the `act` code of include/stk.h (layers.get_act, models/layers.py:29-41).  SiLU -- the
 // only one the shipped configs use -- keeps its hand-tuned form and its place first in the (launch-uniform) branch.
@@ -132,6 +148,30 @@ __device__ __forceinline__ float act_slope_f(int act, float u) {
   if (act == STK_ACT_LRELU) return u > 0.f ? 1.f : 0.2f;
   if (act == STK_ACT_ELU) return u > 0.f ? 1.f : expf(u);
   return 1.f;
+}
+
+// The seed of this launch: the host's, plus the device-side counter when dropout is on.
+__device__ __forceinline__ unsigned long long gn_seed(const GnArgs& a) {
+  unsigned long long seed = a.seed;
+  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  return seed;
+}
+// One output element before dropout: the affine step on the normalised value, then the activation.
+__device__ __forceinline__ float gn_act_out(const GnArgs& a, float x, float mean, float rstd, float ga, float be) {
+  const float u = ga * ((x - mean) * rstd) + be;
+  return a.act ? act_f(a.act, u) : u;
+}
+// The four outputs of one float4 item of one channel, in place.  Dropout: such an item is exactly one quad of the counter
+// RNG (stk_rng.h): one 64-bit mix per item (the compiler hoists it), a 16-bit field per element; `flat`, the flat index of
+// the item's first element, is a multiple of 4 because H*W is.
+__device__ __forceinline__ void gn_out4(const GnArgs& a, float (&r)[4], float mean, float rstd, float ga, float be,
+                                        unsigned long long seed, unsigned long long flat) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float t = gn_act_out(a, r[j], mean, rstd, ga, be);
+    if (a.drop_p > 0.f) t = stk_drop_field(stk_mix64(seed, flat >> 2), j) >= a.drop_thr ? t * a.keep_scale : 0.f;
+    r[j] = t;
+  }
 }
 
 // block_sum (common.h) without its closing barrier: `red` must not be written again before the kernel's next barrier.  The two
@@ -237,8 +277,7 @@ __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __re
     mean_out[ng] = mean;
     rstd_out[ng] = rstd;
   }
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const int C = a.C1 + a.C2;
 #pragma unroll
   for (int k = 0; k < IPT; ++k) {
@@ -251,13 +290,7 @@ __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __re
     const int c = c_first + (i * 4) / a.HW;
     const float ga = a.gamma[c], be = a.beta[c];
     float r[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float u = ga * ((r[j] - mean) * rstd) + be;
-      float t = a.act ? act_f(a.act, u) : u;
-      if (a.drop_p > 0.f) t = stk_drop_field(stk_mix64(seed, (flat0 + (unsigned long long)(i * 4)) >> 2), j) >= a.drop_thr ? t * a.keep_scale : 0.f;
-      r[j] = t;
-    }
+    gn_out4(a, r, mean, rstd, ga, be, seed, flat0 + (unsigned long long)(i * 4));
     o4[i] = make_float4(r[0], r[1], r[2], r[3]);
   }
 }
@@ -320,8 +353,7 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict
     rstd_out[ng] = rstd;
   }
 
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const int C = a.C1 + a.C2;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -338,25 +370,34 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict
         const float ga = a.gamma[c], be = a.beta[c];
         const float4 v = p4[i];
         float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float u = ga * ((r[j] - mean) * rstd) + be;
-          float t = a.act ? act_f(a.act, u) : u;
-          if (a.drop_p > 0.f) t = stk_drop_field(stk_mix64(seed, (flat0 + (unsigned long long)(i * 4)) >> 2), j) >= a.drop_thr ? t * a.keep_scale : 0.f;
-          r[j] = t;
-        }
+        gn_out4(a, r, mean, rstd, ga, be, seed, flat0 + (unsigned long long)(i * 4));
         o4[i] = make_float4(r[0], r[1], r[2], r[3]);
       }
     } else {
       for (int i = threadIdx.x; i < len; i += 256) {
         const int c = seg[q].c_first + i / a.HW;
-        float u = a.gamma[c] * ((p[i] - mean) * rstd) + a.beta[c];
-        float t = a.act ? act_f(a.act, u) : u;
+        float t = gn_act_out(a, p[i], mean, rstd, a.gamma[c], a.beta[c]);
         if (a.drop_p > 0.f) t = stk_keep(seed, flat0 + (unsigned long long)i, a.drop_thr) ? t * a.keep_scale : 0.f;
         o[i] = t;
       }
     }
   }
+}
+
+// A block-wide maximum of non-negative values as a by-product, in two pieces around a barrier of the caller's: every wave
+// leaves its maximum in xm[wave]; then ONE thread folds the nw of them and issues ONE atomic per workgroup into the 256-slot
+// scale record `rec` (caller-zeroed; null = not wanted).  Non-negative floats order like their bit patterns: an integer max
+// is exact and order-independent.  One atomic per wave measured no gain over a separate pass (4096 workgroups on 256 slots:
+// 16 per address).  The slot is the block id mod 256, NOT the image mod 256: the 32 workgroups of an image run at the same
+// time, and 32 atomics on one address cost the flat backward 44 -> 54 us on the 32x32 layers, 11 -> 18 us on the 8x8 ones.
+__device__ __forceinline__ void gn_amax_wave(float m, float* xm) {
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) xm[threadIdx.x >> 6] = m;
+}
+__device__ __forceinline__ void gn_amax_commit(const float* xm, int nw, float* rec) {
+  float m = 0.f;
+  for (int w = 0; w < nw; ++w) m = fmaxf(m, xm[w]);
+  if (rec) atomicMax(reinterpret_cast<unsigned*>(rec) + (blockIdx.x & 255), __float_as_uint(m));
 }
 
 // ---- backward -------------------------------------------------------------------------------------
@@ -383,8 +424,7 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnArgs a, const float* __re
   const int n = ng / a.G, g = ng - n * a.G;
   const int C = a.C1 + a.C2;
   const float mean = mean_in[ng], rstd = rstd_in[ng];
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
 
   // pass A: per-channel sums (channel loop; each channel is one contiguous HW run)
   float gs[2] = {0.f, 0.f};   // group sums of du*gamma and du*gamma*xhat (thread-partial)
@@ -455,8 +495,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
   const int n = ng / a.G, g = ng - n * a.G;
   const int C = a.C1 + a.C2;
   const float mean = mean_in[ng], rstd = rstd_in[ng];
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const int c0 = g * a.cpg;
   const int L4 = (a.cpg << hw_log2) >> 2;
   const int seglog = min(6, hw_log2 - 2);          // lanes of a wave that share a channel = 2^seglog
@@ -535,10 +574,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
     if (valid && op) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) r[j] = rstd * (du[k][j] * gam[k] - m1 - xh[k][j] * m2);
-      if (ob != 0.f) {
-        const float4 old = *reinterpret_cast<const float4*>(op);
-        r[0] += ob * old.x; r[1] += ob * old.y; r[2] += ob * old.z; r[3] += ob * old.w;
-      }
+      gn_dx_accum(r, ob, reinterpret_cast<const float4*>(op));
       if (want && out.add && c < a.C1) {
         const float4 ad = *reinterpret_cast<const float4*>(out.add + (((long)n * a.C1 + c) << hw_log2) + off);
         r[0] += out.add_scale * ad.x; r[1] += out.add_scale * ad.y; r[2] += out.add_scale * ad.z; r[3] += out.add_scale * ad.w;
@@ -554,10 +590,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
     }
   }
   if (want) {
-    {
-      const float m = wave_max(amax_l);
-      if (lane == 0) s_mx[threadIdx.x >> 6] = m;          // (not s_ch: another wave may still be reading its group sums)
-    }
+    gn_amax_wave(amax_l, s_mx);                            // (not s_ch: another wave may still be reading its group sums)
     __syncthreads();
     for (int cl = threadIdx.x; cl < a.cpg; cl += T) {
       if (c0 + cl >= a.C1) continue;
@@ -567,15 +600,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
       if (out.sum) { out.sum[((long)n * a.C1 + c0 + cl) * 2] = t; out.sum[((long)n * a.C1 + c0 + cl) * 2 + 1] = t; }
       if (out.temb) out.temb[(long)n * out.temb_stride + c0 + cl] = t;
     }
-    if (out.amax && threadIdx.x == 0) {
-      // ONE atomic per workgroup (4096 workgroups on 256 slots: 16 per address; one per wave measured no gain over the
-      // separate pass).  Non-negative floats order like their bit patterns: an integer max is exact and order-independent
-      float m = 0.f;
-      for (int w = 0; w < (T >> 6); ++w) m = fmaxf(m, s_mx[w]);
-      // (slot = block id mod 256, NOT image mod 256: the 32 workgroups of an image run at the same time, and 32 atomics on one
-      // address cost this kernel 44 -> 54 us on the 32x32 layers, 11 -> 18 us on the 8x8 ones -- measured, round 5)
-      atomicMax(reinterpret_cast<unsigned*>(out.amax) + (blockIdx.x & 255), __float_as_uint(m));
-    }
+    if (out.amax && threadIdx.x == 0) gn_amax_commit(s_mx, T >> 6, out.amax);
   }
 }
 
@@ -586,10 +611,6 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
 // folds the partials of its group in a fixed order and streams its chunk.  Partials: part[((n*C + c)*Sc + k)*2 + {0,1}]
 // (forward: the chunk's mean and M2 = sum (x - mean)^2; backward: two plain sums).
 constexpr int GN_CHUNK = 4096;       // floats: 4 float4 per thread
-
-__device__ __forceinline__ const float* gn_chan(const GnArgs& a, int n, int c) {
-  return c < a.C1 ? a.x1 + ((long)n * a.C1 + c) * a.HW : a.x2 + ((long)n * a.C2 + (c - a.C1)) * a.HW;
-}
 
 // forward statistics of one chunk, held in registers: its mean and M2 by the corrected two-pass form (header)
 __global__ __launch_bounds__(256) void gn_split_stats_kernel(GnArgs a, float* __restrict__ part, int Sc) {
@@ -640,8 +661,7 @@ __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float
   float mean, rstd;
   gn_fold_chunks(part, ((long)n * C + g * a.cpg) * Sc, a.cpg * Sc, eps, red0, red, mean, rstd);
   if (threadIdx.x == 0 && k == 0 && c == g * a.cpg) { mean_out[n * a.G + g] = mean; rstd_out[n * a.G + g] = rstd; }
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const float ga = a.gamma[c], be = a.beta[c];
   const long coff = (long)k * GN_CHUNK;
   const float4* p4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
@@ -652,13 +672,7 @@ __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float
     const int e = threadIdx.x + 256 * i;
     const float4 v = p4[e];
     float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float u = ga * ((r[j] - mean) * rstd) + be;
-      float t = a.act ? act_f(a.act, u) : u;
-      if (a.drop_p > 0.f) t = stk_drop_field(stk_mix64(seed, (flat0 + (unsigned long long)(e * 4)) >> 2), j) >= a.drop_thr ? t * a.keep_scale : 0.f;
-      r[j] = t;
-    }
+    gn_out4(a, r, mean, rstd, ga, be, seed, flat0 + (unsigned long long)(e * 4));
     o4[e] = make_float4(r[0], r[1], r[2], r[3]);
   }
 }
@@ -672,8 +686,7 @@ __global__ __launch_bounds__(256) void gn_split_bwd_part_kernel(GnArgs a, const 
   const int k = blockIdx.x % Sc, nc = blockIdx.x / Sc;
   const int C = a.C1 + a.C2, n = nc / C, c = nc - n * C, g = c / a.cpg;
   const float mean = mean_in[n * a.G + g], rstd = rstd_in[n * a.G + g];
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const float ga = a.gamma[c], be = a.beta[c];
   const long coff = (long)k * GN_CHUNK;
   const float4* x4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
@@ -729,8 +742,7 @@ __global__ __launch_bounds__(256) void gn_split_bwd_kernel(GnArgs a, const float
   if (c < a.C1) { op = dx1 ? dx1 + ((long)n * a.C1 + c) * a.HW : nullptr; ob = beta1; }
   else { op = dx2 ? dx2 + ((long)n * a.C2 + (c - a.C1)) * a.HW : nullptr; ob = beta2; }
   if (!op) return;
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   const float ga = a.gamma[c], be = a.beta[c];
   const long coff = (long)k * GN_CHUNK;
   const float4* x4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
@@ -749,10 +761,7 @@ __global__ __launch_bounds__(256) void gn_split_bwd_kernel(GnArgs a, const float
       const float du = gn_du(a, xs[j], ds[j], mean, rstd, ga, be, seed, ((flat0 + (unsigned long long)(e * 4)) & ~3ULL) + j, xh);
       r[j] = rstd * (du * ga - m1 - xh * m2);
     }
-    if (ob != 0.f) {
-      const float4 old = o4[e];
-      r[0] += ob * old.x; r[1] += ob * old.y; r[2] += ob * old.z; r[3] += ob * old.w;
-    }
+    gn_dx_accum(r, ob, o4 + e);
     o4[e] = make_float4(r[0], r[1], r[2], r[3]);
   }
 }
@@ -802,20 +811,43 @@ __global__ __launch_bounds__(256) void gn_param_grad_kernel(const float* __restr
 // The consumer convolution scales its split by this bound instead of a measured maximum, which removes the |x| pass over
 // every GroupNorm output; the bound is loose (sqrt(L - 1) = 64 for a 4 x 32 x 32 group against a typical |xhat| <= 5),
 // which costs the split's second term a few of its 11 spare bits and nothing else (tests/test_planes.py).
-__global__ __launch_bounds__(256) void gn_bound_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, int C,
-                                                       float sqrt_lm1, float keep_scale, float* __restrict__ rec) {
-  __shared__ float red[8];
+// In two pieces, so that a kernel can issue the loads early and reduce late: the block's T threads take max|gamma| and
+// max|beta| over C and leave one pair per wave in red[wave], red[NW + wave]; after a barrier of the caller's, any thread
+// folds the block's nw pairs into the bound.
+template <int NW>
+__device__ __forceinline__ void gn_bound_load(const float* __restrict__ gamma, const float* __restrict__ beta, int C, int T,
+                                              float* red) {
   float g = 0.f, b = 0.f;
-  for (int c = threadIdx.x; c < C; c += 256) {
+  for (int c = threadIdx.x; c < C; c += T) {
     g = fmaxf(g, fabsf(gamma[c]));
     b = fmaxf(b, fabsf(beta[c]));
   }
   g = wave_max(g); b = wave_max(b);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = g; red[4 + (threadIdx.x >> 6)] = b; }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = g; red[NW + (threadIdx.x >> 6)] = b; }
+}
+template <int NW>
+__device__ __forceinline__ float gn_bound_fold(const float* red, int nw, float sqrt_lm1, float keep_scale) {
+  float g = 0.f, b = 0.f;
+  if (NW == 4) {                                         // the 256-thread kernels: four waves, as a tree
+    g = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    b = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+  } else {
+    for (int w = 0; w < nw; ++w) { g = fmaxf(g, red[w]); b = fmaxf(b, red[NW + w]); }
+  }
+  return __fmaf_rn(g, sqrt_lm1, b) * keep_scale;
+}
+// The whole record by one block of 256 threads.  red: 8 floats of LDS
+__device__ __forceinline__ void gn_bound_rec(const float* __restrict__ gamma, const float* __restrict__ beta, int C,
+                                             float sqrt_lm1, float keep_scale, float* red, float* __restrict__ rec) {
+  gn_bound_load<4>(gamma, beta, C, 256, red);
   __syncthreads();
-  g = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  b = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
-  rec[threadIdx.x] = threadIdx.x == 0 ? __fmaf_rn(g, sqrt_lm1, b) * keep_scale : 0.f;
+  const float bound = gn_bound_fold<4>(red, 4, sqrt_lm1, keep_scale);
+  rec[threadIdx.x] = threadIdx.x == 0 ? bound : 0.f;
+}
+__global__ __launch_bounds__(256) void gn_bound_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, int C,
+                                                       float sqrt_lm1, float keep_scale, float* __restrict__ rec) {
+  __shared__ float red[8];
+  gn_bound_rec(gamma, beta, C, sqrt_lm1, keep_scale, red, rec);
 }
 
 // ---- forward writing planes --------------------------------------------------------------------------------------
@@ -841,16 +873,13 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
   const int C = a.C1 + a.C2, Cb = C >> 5;
   const int n = blockIdx.x / Cb, cb = blockIdx.x - n * Cb;
   const int c0 = cb * 32;
-  const float* src = c0 < a.C1 ? a.x1 + ((long)n * a.C1 + c0) * a.HW : a.x2 + ((long)n * a.C2 + (c0 - a.C1)) * a.HW;
+  const float* src = gn_chan(a, n, c0);
   const int q = tid & 3;                  // 8-channel piece (constant per thread: T % 4 == 0)
   const int gb = 32 / a.cpg;              // groups in this block
   const int g_lo = (8 * q) / a.cpg, g_hi = (8 * q + 4) / a.cpg;
 
   // scale of the planes: |y| <= (max|gamma| sqrt(L - 1) + max|beta|) / (1 - p)
-  float gm = 0.f, bm = 0.f;
-  for (int c = tid; c < C; c += T) { gm = fmaxf(gm, fabsf(a.gamma[c])); bm = fmaxf(bm, fabsf(a.beta[c])); }
-  gm = wave_max(gm); bm = wave_max(bm);
-  if (lane == 0) { bnd[wave] = gm; bnd[16 + wave] = bm; }
+  gn_bound_load<16>(a.gamma, a.beta, C, T, bnd);
 
   float v[PASSES][8];
   float s[4] = {0.f, 0.f, 0.f, 0.f};
@@ -869,23 +898,16 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
   if (lane < 4) { red[(wave * 4 + lane) * 4] = s[0]; red[(wave * 4 + lane) * 4 + 2] = s[2]; }
   if (xmax1) {
     // by-product for the block's 1x1 shortcut convolution, which reads the same source tensors as fp32 operands of the
-    // split kernels: max |x| of this block, by atomic maximum into the 256-slot scale record of its source (zeroed by the
-    // caller; non-negative floats order like their bit patterns)
+    // split kernels: max |x| of this block, into the scale record of its source (gn_amax_commit)
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < PASSES; ++k)
 #pragma unroll
       for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[k][j]));
-    m = wave_max(m);
-    if (lane == 0) xm[wave] = m;
+    gn_amax_wave(m, xm);
   }
   __syncthreads();
-  if (xmax1 && tid == 0) {
-    float m = 0.f;
-    for (int w = 0; w < nw; ++w) m = fmaxf(m, xm[w]);
-    float* rec = c0 < a.C1 ? xmax1 : xmax2;
-    if (rec) atomicMax(reinterpret_cast<unsigned*>(rec) + (blockIdx.x & 255), __float_as_uint(m));
-  }
+  if (xmax1 && tid == 0) gn_amax_commit(xm, nw, c0 < a.C1 ? xmax1 : xmax2);
   const float inv_l = 1.f / ((float)a.cpg * (float)a.HW);
   if (tid < gb) {
     // pieces of group `tid`, in a fixed order: (q', half) with (8 q' + 4 half) / cpg == tid, over all waves
@@ -932,23 +954,15 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
     rstd_out[n * a.G + g] = rstd;
   }
   __syncthreads();
-  float gmax = 0.f, bmax = 0.f;
-  for (int w = 0; w < nw; ++w) { gmax = fmaxf(gmax, bnd[w]); bmax = fmaxf(bmax, bnd[16 + w]); }
-  const float bound = __fmaf_rn(gmax, sqrt_lm1, bmax) * a.keep_scale;
+  const float bound = gn_bound_fold<16>(bnd, nw, sqrt_lm1, a.keep_scale);
   if (blockIdx.x == 0)
     for (int i = tid; i < 256; i += T) rec[i] = i == 0 ? bound : 0.f;
-  // the power of two that puts the bound in [2^13, 2^14) (x2::pow2_scale_of in conv_x2.h)
-  float sc = 1.f;
-  {
-    const int be = (int)((__float_as_uint(bound) >> 23) & 0xffu);
-    if (be != 0) sc = __uint_as_float((unsigned)min(max(127 + 13 - (be - 127), 1), 254) << 23);
-  }
+  const float sc = split2::pow2_scale_of(bound);
   const float m_lo = gst[2 * g_lo], r_lo = gst[2 * g_lo + 1], m_hi = gst[2 * g_hi], r_hi = gst[2 * g_hi + 1];
   float ga[8], be8[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { ga[j] = a.gamma[c0 + 8 * q + j]; be8[j] = a.beta[c0 + 8 * q + j]; }
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const unsigned long long seed = gn_seed(a);
   float* yo = y ? y + ((long)n * C + c0) * a.HW : nullptr;
   unsigned char* po = planes + ((long)n * Cb + cb) * a.HW * 64 + q * 16;
 #pragma unroll
@@ -979,25 +993,15 @@ __global__ __launch_bounds__(1024) void gn_fwd_pl_kernel(GnArgs a, float* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float mean = j < 4 ? m_lo : m_hi, rstd = j < 4 ? r_lo : r_hi;
-      const float u = ga[j] * ((v[k][j] - mean) * rstd) + be8[j];
-      float r = a.act ? act_f(a.act, u) : u;
+      float r = gn_act_out(a, v[k][j], mean, rstd, ga[j], be8[j]);
       if (a.drop_p > 0.f) r = ((keep >> j) & 1u) ? r * a.keep_scale : 0.f;
-      t[j] = r;
+      t[j] = sc * r;
       if (yo) yo[(long)(8 * q + j) * a.HW + px] = r;
     }
-    unsigned hi[4], lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float v0 = sc * t[2 * j], v1 = sc * t[2 * j + 1];
-      const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-      const _Float16 l0 = (_Float16)(v0 - (float)h0), l1 = (_Float16)(v1 - (float)h1);
-      typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-      hi[j] = __builtin_bit_cast(unsigned, h2{h0, h1});
-      lo[j] = __builtin_bit_cast(unsigned, h2{l0, l1});
-    }
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<u4*>(po + (long)px * 64) = u4{hi[0], hi[1], hi[2], hi[3]};
-    *reinterpret_cast<u4*>(po + plane_stride + (long)px * 64) = u4{lo[0], lo[1], lo[2], lo[3]};
+    u32x4 hi, lo;
+    split2::split8(t, hi, lo);
+    *reinterpret_cast<u32x4*>(po + (long)px * 64) = hi;
+    *reinterpret_cast<u32x4*>(po + plane_stride + (long)px * 64) = lo;
   }
 }
 
@@ -1035,17 +1039,8 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GnArgs a, float* __restri
     mean_out[ng] = mean_v;
     rstd_out[ng] = rstd_v;
   }
-  if (rec && ng == 0) {                                  // the planes' scale record: a-priori bound of |y| (gn_bound_kernel)
-    const int C = a.C1 + a.C2;
-    float gm = 0.f, bm = 0.f;
-    for (int c = threadIdx.x; c < C; c += 256) { gm = fmaxf(gm, fabsf(a.gamma[c])); bm = fmaxf(bm, fabsf(a.beta[c])); }
-    gm = wave_max(gm); bm = wave_max(bm);
-    if ((threadIdx.x & 63) == 0) { redb[threadIdx.x >> 6] = gm; redb[4 + (threadIdx.x >> 6)] = bm; }
-    __syncthreads();
-    gm = fmaxf(fmaxf(redb[0], redb[1]), fmaxf(redb[2], redb[3]));
-    bm = fmaxf(fmaxf(redb[4], redb[5]), fmaxf(redb[6], redb[7]));
-    rec[threadIdx.x] = threadIdx.x == 0 ? __fmaf_rn(gm, sqrt_lm1, bm) * a.keep_scale : 0.f;
-  }
+  // the planes' scale record: a-priori bound of |y| (gn_bound_kernel)
+  if (rec && ng == 0) gn_bound_rec(a.gamma, a.beta, a.C1 + a.C2, sqrt_lm1, a.keep_scale, redb, rec);
 }
 
 // mean / rstd of large groups from the per-chunk partials of gn_split_stats_kernel (fixed order), + the scale record
@@ -1075,15 +1070,9 @@ __global__ __launch_bounds__(256) void gn_apply_pl_kernel(GnArgs a, const float*
   const int tile = blockIdx.x % tiles, rest = blockIdx.x / tiles;
   const int cb = rest % Cb, n = rest / Cb;
   const int c0 = cb * 32, p0 = tile * AP_PIX;
-  const float* src = c0 < a.C1 ? a.x1 + ((long)n * a.C1 + c0) * a.HW : a.x2 + ((long)n * a.C2 + (c0 - a.C1)) * a.HW;
-  // the power of two that puts the bound in [2^13, 2^14) (x2::pow2_scale_of in conv_x2.h)
-  float sc = 1.f;
-  {
-    const int be = (int)((__float_as_uint(rec[0]) >> 23) & 0xffu);
-    if (be != 0) sc = __uint_as_float((unsigned)min(max(127 + 13 - (be - 127), 1), 254) << 23);
-  }
-  unsigned long long seed = a.seed;
-  if (a.drop_p > 0.f && a.seed_dev) seed += *a.seed_dev;
+  const float* src = gn_chan(a, n, c0);
+  const float sc = split2::pow2_scale_of(rec[0]);
+  const unsigned long long seed = gn_seed(a);
   float amax_l = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -1096,13 +1085,13 @@ __global__ __launch_bounds__(256) void gn_apply_pl_kernel(GnArgs a, const float*
     const float ga = a.gamma[ch], be = a.beta[ch];
     float r[4] = {v.x, v.y, v.z, v.w};
     if (xmax1) amax_l = fmaxf(amax_l, fmaxf(fmaxf(fabsf(r[0]), fabsf(r[1])), fmaxf(fabsf(r[2]), fabsf(r[3]))));
+    // (gn_out4 with the item's mix taken first: in this kernel that order is worth 3 % of its time)
     const unsigned long long flat = ((unsigned long long)n * C + ch) * a.HW + px;
     unsigned long long z = 0;
     if (a.drop_p > 0.f) z = stk_mix64(seed, flat >> 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float u = ga * ((r[j] - mean) * rstd) + be;
-      float o = a.act ? act_f(a.act, u) : u;
+      float o = gn_act_out(a, r[j], mean, rstd, ga, be);
       if (a.drop_p > 0.f) o = stk_drop_field(z, j) >= a.drop_thr ? o * a.keep_scale : 0.f;
       r[j] = o;
     }
@@ -1110,34 +1099,21 @@ __global__ __launch_bounds__(256) void gn_apply_pl_kernel(GnArgs a, const float*
     float* d = t + c * 129 + 4 * q4;
     d[0] = sc * r[0]; d[1] = sc * r[1]; d[2] = sc * r[2]; d[3] = sc * r[3];
   }
-  if (xmax1) {
-    const float m = wave_max(amax_l);
-    if ((tid & 63) == 0) xm[tid >> 6] = m;
-  }
+  if (xmax1) gn_amax_wave(amax_l, xm);
   __syncthreads();
-  if (xmax1 && tid == 0) {
-    float* dst = c0 < a.C1 ? xmax1 : xmax2;
-    if (dst) atomicMax(reinterpret_cast<unsigned*>(dst) + (blockIdx.x & 255),
-                       __float_as_uint(fmaxf(fmaxf(xm[0], xm[1]), fmaxf(xm[2], xm[3]))));
-  }
+  if (xmax1 && tid == 0) gn_amax_commit(xm, 4, c0 < a.C1 ? xmax1 : xmax2);
 #pragma unroll
   for (int r2 = 0; r2 < 2; ++r2) {
     const int id = tid + 256 * r2;
     const int px = id >> 2, q = id & 3;
-    unsigned hi[4], lo[4];
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float v0 = t[(8 * q + 2 * j) * 129 + px], v1 = t[(8 * q + 2 * j + 1) * 129 + px];
-      const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-      const _Float16 l0 = (_Float16)(v0 - (float)h0), l1 = (_Float16)(v1 - (float)h1);
-      typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-      hi[j] = __builtin_bit_cast(unsigned, h2{h0, h1});
-      lo[j] = __builtin_bit_cast(unsigned, h2{l0, l1});
-    }
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    for (int j = 0; j < 8; ++j) v[j] = t[(8 * q + j) * 129 + px];
+    u32x4 hi, lo;
+    split2::split8(v, hi, lo);
     unsigned char* o = planes + (((long)n * Cb + cb) * a.HW + p0 + px) * 64 + q * 16;
-    *reinterpret_cast<u4*>(o) = u4{hi[0], hi[1], hi[2], hi[3]};
-    *reinterpret_cast<u4*>(o + plane_stride) = u4{lo[0], lo[1], lo[2], lo[3]};
+    *reinterpret_cast<u32x4*>(o) = hi;
+    *reinterpret_cast<u32x4*>(o + plane_stride) = lo;
   }
 }
 
@@ -1165,6 +1141,32 @@ static inline bool gn_pl_fused_ok(int C1, int C2, int HW, int G) {
 // Every later step of the bound is monotone in it.  oracle/stk_ref.c stk_gn_bound_f32 restates it.
 static inline float gn_bound_sqrt(long L) { return sqrtf((float)L - 1.f) * (1.f + 0x1p-16f); }
 
+// The launch-invariant arguments of every kernel here.
+static inline GnArgs gn_args(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, int N, int HW,
+                             int G, int act, float drop_p, unsigned long long seed, const unsigned long long* seed_dev) {
+  GnArgs a;
+  a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
+  a.N = N; a.HW = HW; a.G = G; a.cpg = (C1 + C2) / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
+  a.seed = seed; a.seed_dev = seed_dev;
+  return a;
+}
+
+// What every forward / backward entry requires of the arguments behind GnArgs (its own pointers it checks itself).
+static inline bool gn_check_common(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, int N,
+                                   int HW, int G, int act, float drop_p) {
+  return x1 && gamma && beta && N > 0 && HW > 0 && G > 0 && C1 > 0 && C2 >= 0 && (C1 + C2) % G == 0 && (C2 == 0 || x2) &&
+         drop_p >= 0.f && drop_p < 1.f && act >= 0 && act <= STK_ACT_ELU;
+}
+
+// A run-time count -> a template argument: f(std::integral_constant<int, V>) for the first V of the ladder with n <= V, the
+// last V for anything larger.
+template <int V, int... Rest, class F>
+static inline void gn_pick(int n, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+  else if (n <= V) f(std::integral_constant<int, V>{});
+  else gn_pick<Rest...>(n, f);
+}
+
 extern "C" {
 
 int stk_gn_bound_f32(const float* gamma, const float* beta, int C, int G, int HW, float drop_p, float* rec, void* stream) {
@@ -1178,21 +1180,17 @@ int stk_gn_bound_f32(const float* gamma, const float* beta, int C, int G, int HW
 int stk_gn_fwd_f32(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, float* y,
                    float* mean, float* rstd, int N, int HW, int G, float eps, int act, float drop_p,
                    unsigned long long seed, const unsigned long long* seed_dev, float* ws, void* stream) {
+  if (!y || !mean || !rstd || !gn_check_common(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p)) return STK_EINVAL;
   const int C = C1 + C2;
-  if (!x1 || !gamma || !beta || !y || !mean || !rstd || N <= 0 || HW <= 0 || G <= 0 || C1 <= 0 || C2 < 0 || C % G ||
-      (C2 > 0 && !x2) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > STK_ACT_ELU)
-    return STK_EINVAL;
-  GnArgs a;
-  a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
-  a.N = N; a.HW = HW; a.G = G; a.cpg = C / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
-  a.seed = seed; a.seed_dev = seed_dev;
+  const GnArgs a = gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
+  hipStream_t s = (hipStream_t)stream;
   const bool vec = (HW & 3) == 0 && stk_aligned16(x1) && stk_aligned16(y) && (!x2 || stk_aligned16(x2));
   if (ws && vec && gn_split_ok(HW, a.cpg)) {
     const int Sc = HW / GN_CHUNK;
     const dim3 grid((unsigned)((long)N * C * Sc));
-    hipLaunchKernelGGL(gn_split_stats_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, ws, Sc);
+    hipLaunchKernelGGL(gn_split_stats_kernel, grid, dim3(256), 0, s, a, ws, Sc);
     STK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_split_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, ws, Sc, y, mean, rstd, eps);
+    hipLaunchKernelGGL(gn_split_fwd_kernel, grid, dim3(256), 0, s, a, ws, Sc, y, mean, rstd, eps);
     STK_CHECK_LAUNCH();
     return STK_OK;
   }
@@ -1201,18 +1199,13 @@ int stk_gn_fwd_f32(const float* x1, int C1, const float* x2, int C2, const float
     const int L4 = (int)(L >> 2);
     int T = 64;
     while (T < 1024 && T * 4 < L4) T <<= 1;
-    const int ipt = stk_cdiv(L4, T);
-#define STK_GN_FWD_FLAT(IPT)                                                                                     \
-  hipLaunchKernelGGL((gn_fwd_flat_kernel<IPT>), dim3(N * G), dim3(T), 0, (hipStream_t)stream, a, y, mean, rstd, eps)
-    if (ipt <= 1) STK_GN_FWD_FLAT(1);
-    else if (ipt <= 2) STK_GN_FWD_FLAT(2);
-    else if (ipt <= 3) STK_GN_FWD_FLAT(3);
-    else STK_GN_FWD_FLAT(4);
-#undef STK_GN_FWD_FLAT
+    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
+      hipLaunchKernelGGL((gn_fwd_flat_kernel<decltype(ipt)::value>), dim3(N * G), dim3(T), 0, s, a, y, mean, rstd, eps);
+    });
   } else if (vec)
-    hipLaunchKernelGGL((gn_fwd_kernel<4>), dim3(N * G), dim3(256), 0, (hipStream_t)stream, a, y, mean, rstd, eps);
+    hipLaunchKernelGGL((gn_fwd_kernel<4>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
   else
-    hipLaunchKernelGGL((gn_fwd_kernel<1>), dim3(N * G), dim3(256), 0, (hipStream_t)stream, a, y, mean, rstd, eps);
+    hipLaunchKernelGGL((gn_fwd_kernel<1>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
   STK_CHECK_LAUNCH();
   return STK_OK;
 }
@@ -1222,7 +1215,54 @@ int stk_gn_fwd_f32(const float* x1, int C1, const float* x2, int C2, const float
 static int gn_fwd_pl_impl(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, float* y,
                           void* planes, float* rec, float* mean, float* rstd, int N, int HW, int G, float eps, int act,
                           float drop_p, unsigned long long seed, const unsigned long long* seed_dev, float* ws, void* stream,
-                          float* xmax1, float* xmax2);
+                          float* xmax1, float* xmax2) {
+  if (!planes || !rec || !mean || !rstd || !gn_check_common(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p)) return STK_EINVAL;
+  const int C = C1 + C2;
+  const long plane_stride = (long)N * ((C + 31) / 32) * HW * 64;
+  if (2 * plane_stride >= 0x7fffffffL) return STK_EUNSUPPORTED;
+  const GnArgs a = gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
+  const float sq = gn_bound_sqrt((long)a.cpg * HW);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* pl = static_cast<unsigned char*>(planes);
+  if (gn_pl_2k_ok(C1, C2, HW, G) && stk_aligned16(x1) && (!x2 || stk_aligned16(x2)) && (!y || stk_aligned16(y))) {
+    if ((long)a.cpg * HW <= 16384) {
+      gn_pick<1, 2, 4, 8, 16>(stk_cdiv((int)(((long)a.cpg * HW) >> 2), 256), [&](auto ipt) {
+        hipLaunchKernelGGL((gn_stats_kernel<decltype(ipt)::value>), dim3(N * G), dim3(256), 0, s, a, mean, rstd, eps, sq, rec);
+      });
+    } else {
+      if (!ws) return STK_EINVAL;
+      const int Sc = HW / GN_CHUNK;
+      hipLaunchKernelGGL(gn_split_stats_kernel, dim3((unsigned)((long)N * C * Sc)), dim3(256), 0, s, a, ws, Sc);
+      hipLaunchKernelGGL(gn_fold_stats_kernel, dim3(N * G), dim3(256), 0, s, a, ws, Sc, mean, rstd, eps);
+      hipLaunchKernelGGL(gn_bound_kernel, dim3(1), dim3(256), 0, s, gamma, beta, C, sq, a.keep_scale, rec);
+    }
+    STK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gn_apply_pl_kernel, dim3((unsigned)((long)N * (C / 32) * (HW / AP_PIX))), dim3(256), 0, s, a, mean, rstd, rec, y,
+                       pl, plane_stride, xmax1, xmax2);
+    STK_CHECK_LAUNCH();
+    return STK_OK;
+  }
+  if (gn_pl_fused_ok(C1, C2, HW, G)) {
+    // HW = 16, 64: a thread per (pixel, 8-channel piece).  HW = 256: the same, 1024 threads.  HW = 1024: two workgroups of
+    // 512 threads per CU instead of one of 1024 -- the same 16 waves per CU, but the load phase of one block overlaps the
+    // arithmetic / store phase of the other -- and 8 passes.
+    const int T = HW * 4 < 1024 ? HW * 4 : HW == 256 ? 1024 : 512;
+    gn_pick<1, 8>(HW * 4 / T, [&](auto passes) {
+      hipLaunchKernelGGL((gn_fwd_pl_kernel<decltype(passes)::value>), dim3((unsigned)(N * (C / 32))), dim3(T), 0, s, a, y, pl,
+                         plane_stride, rec, mean, rstd, eps, sq, xmax1, xmax2);
+    });
+    STK_CHECK_LAUNCH();
+    return STK_OK;
+  }
+  // the unfused route goes through the fp32 copy and leaves no |x| records: a caller that relied on stk_gn_fwd_pl_fused()
+  // for a shape whose pointers miss the 16-byte alignment of the two-kernel route gets an error, not a fault / stale records
+  if (!y || xmax1 || xmax2) return STK_EINVAL;
+  int rc = stk_gn_fwd_f32(x1, C1, x2, C2, gamma, beta, y, mean, rstd, N, HW, G, eps, act, drop_p, seed, seed_dev, ws, stream);
+  if (rc) return rc;
+  rc = stk_gn_bound_f32(gamma, beta, C, G, HW, drop_p, rec, stream);
+  if (rc) return rc;
+  return stk_split_planes_f32(y, N, C, HW, rec, 256, planes, stream);
+}
 
 int stk_gn_fwd_pl_f32(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, float* y,
                       void* planes, float* rec, float* mean, float* rstd, int N, int HW, int G, float eps, int act,
@@ -1242,73 +1282,6 @@ int stk_gn_fwd_pl_max_f32(const float* x1, int C1, const float* x2, int C2, cons
                         stream, xmax1, xmax2);
 }
 
-static int gn_fwd_pl_impl(const float* x1, int C1, const float* x2, int C2, const float* gamma, const float* beta, float* y,
-                          void* planes, float* rec, float* mean, float* rstd, int N, int HW, int G, float eps, int act,
-                          float drop_p, unsigned long long seed, const unsigned long long* seed_dev, float* ws, void* stream,
-                          float* xmax1, float* xmax2) {
-  const int C = C1 + C2;
-  if (!x1 || !gamma || !beta || !planes || !rec || !mean || !rstd || N <= 0 || HW <= 0 || G <= 0 || C1 <= 0 || C2 < 0 ||
-      C % G || (C2 > 0 && !x2) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > STK_ACT_ELU)
-    return STK_EINVAL;
-  const long plane_stride = (long)N * ((C + 31) / 32) * HW * 64;
-  if (2 * plane_stride >= 0x7fffffffL) return STK_EUNSUPPORTED;
-  if (gn_pl_2k_ok(C1, C2, HW, G) && stk_aligned16(x1) && (!x2 || stk_aligned16(x2)) && (!y || stk_aligned16(y))) {
-    GnArgs a;
-    a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
-    a.N = N; a.HW = HW; a.G = G; a.cpg = C / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
-    a.seed = seed; a.seed_dev = seed_dev;
-    const float sq = gn_bound_sqrt((long)a.cpg * HW);
-    hipStream_t s = (hipStream_t)stream;
-    if ((long)a.cpg * HW <= 16384) {
-      const int ipt = stk_cdiv((int)(((long)a.cpg * HW) >> 2), 256);
-#define STK_GN_STATS(IPT) hipLaunchKernelGGL((gn_stats_kernel<IPT>), dim3(N * G), dim3(256), 0, s, a, mean, rstd, eps, sq, rec)
-      if (ipt <= 1) STK_GN_STATS(1); else if (ipt <= 2) STK_GN_STATS(2); else if (ipt <= 4) STK_GN_STATS(4);
-      else if (ipt <= 8) STK_GN_STATS(8); else STK_GN_STATS(16);
-#undef STK_GN_STATS
-    } else {
-      if (!ws) return STK_EINVAL;
-      const int Sc = HW / GN_CHUNK;
-      hipLaunchKernelGGL(gn_split_stats_kernel, dim3((unsigned)((long)N * C * Sc)), dim3(256), 0, s, a, ws, Sc);
-      hipLaunchKernelGGL(gn_fold_stats_kernel, dim3(N * G), dim3(256), 0, s, a, ws, Sc, mean, rstd, eps);
-      hipLaunchKernelGGL(gn_bound_kernel, dim3(1), dim3(256), 0, s, gamma, beta, C, sq, a.keep_scale, rec);
-    }
-    STK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_apply_pl_kernel, dim3((unsigned)((long)N * (C / 32) * (HW / AP_PIX))), dim3(256), 0, s, a, mean, rstd, rec, y,
-                       static_cast<unsigned char*>(planes), plane_stride, xmax1, xmax2);
-    STK_CHECK_LAUNCH();
-    return STK_OK;
-  }
-  if (gn_pl_fused_ok(C1, C2, HW, G)) {
-    GnArgs a;
-    a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
-    a.N = N; a.HW = HW; a.G = G; a.cpg = C / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
-    a.seed = seed; a.seed_dev = seed_dev;
-    // HW = 1024: two workgroups of 512 threads per CU instead of one of 1024: the same 16 waves per CU, but the load phase of
-    // one block overlaps the arithmetic / store phase of the other
-    constexpr int tmax = 512;
-    int T = HW * 4 < 1024 ? HW * 4 : 1024;
-    if (HW * 4 > 1024 && tmax < T) T = tmax;
-    const int items = HW * 4, passes = items / T;
-    const float sq = gn_bound_sqrt((long)a.cpg * HW);
-    const dim3 grid((unsigned)(N * (C / 32)));
-#define STK_GN_PL(P)                                                                                               \
-  hipLaunchKernelGGL((gn_fwd_pl_kernel<P>), grid, dim3(T), 0, (hipStream_t)stream, a, y, static_cast<unsigned char*>(planes), \
-                     plane_stride, rec, mean, rstd, eps, sq, xmax1, xmax2)
-    if (passes == 1) STK_GN_PL(1); else if (passes == 2) STK_GN_PL(2); else if (passes == 4) STK_GN_PL(4); else if (passes == 8) STK_GN_PL(8); else return STK_EUNSUPPORTED;
-#undef STK_GN_PL
-    STK_CHECK_LAUNCH();
-    return STK_OK;
-  }
-  // the unfused route goes through the fp32 copy and leaves no |x| records: a caller that relied on stk_gn_fwd_pl_fused()
-  // for a shape whose pointers miss the 16-byte alignment of the two-kernel route gets an error, not a fault / stale records
-  if (!y || xmax1 || xmax2) return STK_EINVAL;
-  int rc = stk_gn_fwd_f32(x1, C1, x2, C2, gamma, beta, y, mean, rstd, N, HW, G, eps, act, drop_p, seed, seed_dev, ws, stream);
-  if (rc) return rc;
-  rc = stk_gn_bound_f32(gamma, beta, C, G, HW, drop_p, rec, stream);
-  if (rc) return rc;
-  return stk_split_planes_f32(y, N, C, HW, rec, 256, planes, stream);
-}
-
 /* 1 if stk_gn_fwd_pl_f32 takes this shape in one pass (and therefore accepts y = NULL) */
 int stk_gn_fwd_pl_fused(int C1, int C2, int HW, int G) { return gn_pl_fused_ok(C1, C2, HW, G) || gn_pl_2k_ok(C1, C2, HW, G) ? 1 : 0; }
 
@@ -1323,7 +1296,46 @@ int stk_gn_bwd_out_ok(int C1, int C2, int HW, int G) { return C1 > 0 && C2 >= 0 
 static int gn_bwd_impl(const float* dy, const float* x1, int C1, const float* x2, int C2, const float* gamma,
                        const float* beta, const float* mean, const float* rstd, float* dx1, float dx1_beta, float* dx2,
                        float dx2_beta, float* dgamma, float* dbeta, float* ws, int N, int HW, int G, int act, float drop_p,
-                       unsigned long long seed, const unsigned long long* seed_dev, void* stream, GnBwdOut out);
+                       unsigned long long seed, const unsigned long long* seed_dev, void* stream, GnBwdOut out) {
+  if (!dy || !mean || !rstd || !ws || !gn_check_common(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p)) return STK_EINVAL;
+  const int C = C1 + C2;
+  const GnArgs a = gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
+  hipStream_t s = (hipStream_t)stream;
+  const long L = (long)a.cpg * HW;
+  int hw_log2 = 0;
+  while ((1 << hw_log2) < HW) ++hw_log2;
+  const bool al16 = stk_aligned16(x1) && stk_aligned16(dy) && (!x2 || stk_aligned16(x2)) && (!dx1 || stk_aligned16(dx1)) &&
+                    (!dx2 || stk_aligned16(dx2));
+  const bool flat = al16 && (1 << hw_log2) == HW && HW >= 16 && L <= 16384 && a.cpg <= 512;
+  if (al16 && gn_split_ok(HW, a.cpg)) {
+    const int Sc = HW / GN_CHUNK;
+    float* part = ws + 2L * N * C;                       // after the [N][C][2] channel sums
+    const dim3 grid((unsigned)((long)N * C * Sc));
+    hipLaunchKernelGGL(gn_split_bwd_part_kernel, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc);
+    STK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gn_split_bwd_kernel, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc, dx1, dx1_beta, dx2, dx2_beta, ws);
+  } else if (flat) {
+    const int L4 = (int)(L >> 2);
+    const int tgt = 4;          // float4 per thread (measured best of 1..4 on the 32x32 / 16x16 layers)
+    int T = 64;
+    while (T < 1024 && T * tgt < L4) T <<= 1;
+    const bool want = out.sum || out.temb || out.amax || out.add;
+    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
+      constexpr int IPT = decltype(ipt)::value;
+      hipLaunchKernelGGL((want ? gn_bwd_flat_kernel<IPT, true> : gn_bwd_flat_kernel<IPT, false>), dim3(N * G), dim3(T), 0, s, a, dy,
+                         mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws, hw_log2, out);
+    });
+  } else {
+    hipLaunchKernelGGL(gn_bwd_kernel, dim3(N * G), dim3(256), 0, s, a, dy, mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws);
+  }
+  STK_CHECK_LAUNCH();
+  if (dgamma || dbeta) {
+    hipLaunchKernelGGL(gn_param_grad_kernel, dim3(stk_cdiv(C, 32)), dim3(256), 0, s, ws, dgamma, dbeta, N, C,
+                       (const StkGnFoldDesc*)nullptr);
+    STK_CHECK_LAUNCH();
+  }
+  return STK_OK;
+}
 
 int stk_gn_bwd_f32(const float* dy, const float* x1, int C1, const float* x2, int C2, const float* gamma,
                    const float* beta, const float* mean, const float* rstd, float* dx1, float dx1_beta, float* dx2,
@@ -1346,67 +1358,6 @@ int stk_gn_bwd_out_f32(const float* dy, const float* x1, int C1, const float* x2
   const GnBwdOut out = {dx_sum, dtemb, temb_stride, out_scale, dx_amax, dx1_add, add_scale};
   return gn_bwd_impl(dy, x1, C1, x2, C2, gamma, beta, mean, rstd, dx1, dx1_beta, dx2, dx2_beta, dgamma, dbeta, ws, N, HW, G,
                      act, drop_p, seed, seed_dev, stream, out);
-}
-
-static int gn_bwd_impl(const float* dy, const float* x1, int C1, const float* x2, int C2, const float* gamma,
-                       const float* beta, const float* mean, const float* rstd, float* dx1, float dx1_beta, float* dx2,
-                       float dx2_beta, float* dgamma, float* dbeta, float* ws, int N, int HW, int G, int act, float drop_p,
-                       unsigned long long seed, const unsigned long long* seed_dev, void* stream, GnBwdOut out) {
-  const int C = C1 + C2;
-  if (!dy || !x1 || !gamma || !beta || !mean || !rstd || !ws || N <= 0 || HW <= 0 || G <= 0 || C1 <= 0 || C2 < 0 ||
-      C % G || (C2 > 0 && !x2) || drop_p < 0.f || drop_p >= 1.f || act < 0 || act > STK_ACT_ELU)
-    return STK_EINVAL;
-  GnArgs a;
-  a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
-  a.N = N; a.HW = HW; a.G = G; a.cpg = C / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
-  a.seed = seed; a.seed_dev = seed_dev;
-  const long L = (long)a.cpg * HW;
-  int hw_log2 = 0;
-  while ((1 << hw_log2) < HW) ++hw_log2;
-  const bool flat = (1 << hw_log2) == HW && HW >= 16 && L <= 16384 && a.cpg <= 512 && stk_aligned16(x1) &&
-                    stk_aligned16(dy) && (!x2 || stk_aligned16(x2)) && (!dx1 || stk_aligned16(dx1)) &&
-                    (!dx2 || stk_aligned16(dx2));
-  const bool al16 = stk_aligned16(x1) && stk_aligned16(dy) && (!x2 || stk_aligned16(x2)) && (!dx1 || stk_aligned16(dx1)) &&
-                    (!dx2 || stk_aligned16(dx2));
-  if (al16 && gn_split_ok(HW, a.cpg)) {
-    const int Sc = HW / GN_CHUNK;
-    float* part = ws + 2L * N * C;                       // after the [N][C][2] channel sums
-    const dim3 grid((unsigned)((long)N * C * Sc));
-    hipLaunchKernelGGL(gn_split_bwd_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, dy, mean, rstd, part, Sc);
-    STK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_split_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, dy, mean, rstd, part, Sc, dx1,
-                       dx1_beta, dx2, dx2_beta, ws);
-  } else if (flat) {
-    const int L4 = (int)(L >> 2);
-    const int tgt = 4;          // float4 per thread (measured best of 1..4 on the 32x32 / 16x16 layers)
-    int T = 64;
-    while (T < 1024 && T * tgt < L4) T <<= 1;
-    const int ipt = stk_cdiv(L4, T);
-#define STK_GN_FLAT(IPT)                                                                                          \
-  do {                                                                                                            \
-    if (out.sum || out.temb || out.amax || out.add)                                                               \
-      hipLaunchKernelGGL((gn_bwd_flat_kernel<IPT, true>), dim3(N * G), dim3(T), 0, (hipStream_t)stream, a, dy, mean, rstd, dx1, \
-                         dx1_beta, dx2, dx2_beta, ws, hw_log2, out);                                               \
-    else                                                                                                          \
-      hipLaunchKernelGGL((gn_bwd_flat_kernel<IPT, false>), dim3(N * G), dim3(T), 0, (hipStream_t)stream, a, dy, mean, rstd, dx1, \
-                         dx1_beta, dx2, dx2_beta, ws, hw_log2, out);                                               \
-  } while (0)
-    if (ipt <= 1) STK_GN_FLAT(1);
-    else if (ipt <= 2) STK_GN_FLAT(2);
-    else if (ipt <= 3) STK_GN_FLAT(3);
-    else STK_GN_FLAT(4);
-#undef STK_GN_FLAT
-  } else {
-    hipLaunchKernelGGL(gn_bwd_kernel, dim3(N * G), dim3(256), 0, (hipStream_t)stream, a, dy, mean, rstd, dx1, dx1_beta,
-                       dx2, dx2_beta, ws);
-  }
-  STK_CHECK_LAUNCH();
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(gn_param_grad_kernel, dim3(stk_cdiv(C, 32)), dim3(256), 0, (hipStream_t)stream, ws, dgamma,
-                       dbeta, N, C, (const StkGnFoldDesc*)nullptr);
-    STK_CHECK_LAUNCH();
-  }
-  return STK_OK;
 }
 
 int stk_gn_param_grad_batch(const StkGnFoldDesc* descs_dev, int count, int max_C, void* stream) {
