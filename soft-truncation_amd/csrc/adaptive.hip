@@ -4,11 +4,9 @@
 // reads 2 and writes 2 for the accepted rows only: HBM-bound, and laid out as stream.h describes, the 16-byte path taken
 // whenever n is a multiple of 4 (an item never leaves its row).
 //
-// The grid is two-dimensional because everything here is per sample: blockIdx.y walks the samples (striding when B exceeds
-// the grid), blockIdx.x is one of the `parts` blocks that share a row and stride along it.  parts x rows is stk_ew_grid's
-// cap of 8 blocks per CU at most, and parts depends on (B, n) alone -- not on the alignment -- so the workspace of partial
-// sums has one layout, [B, parts] float64, which stk_sde_ws_bytes can state without seeing a pointer.  B n < 2^31 (checked by
-// the entries), so the index arithmetic is 32-bit.
+// The grid is the row grid of rowsum.h: blockIdx.y walks the samples, blockIdx.x is one of the `parts` blocks that share a row;
+// the workspace of partial sums is its [B, parts] float64 layout, which stk_sde_ws_bytes states without seeing a pointer.
+// B n < 2^31 (checked by the entries), so the index arithmetic is 32-bit.
 //
 // No fused multiply-add in this file (header, "Arithmetic"): the pragma below holds for every function that follows.
 // stream.h, included before it, holds loads, stores and host code only.
@@ -17,31 +15,9 @@
 
 #pragma clang fp contract(off)
 
+#include "rowsum.h"
+
 namespace {
-
-// Blocks that share one row, and rows walked at once: functions of (B, n) alone.
-int sde_rows(int B, long n) {
-  const int g = stk_ew_grid((long)B * n);
-  return B < g ? B : g;
-}
-int sde_parts(int B, long n) {
-  long p = stk_ew_grid((long)B * n) / sde_rows(B, n);
-  const long blocks_per_row = (n + 255) / 256;
-  if (p > blocks_per_row) p = blocks_per_row;
-  return (int)(p < 1 ? 1 : p);
-}
-
-// Block-wide float64 sum in a fixed order: xor butterfly inside each wave, then the four waves in index order.  The result
-// is the same in every thread.  Ends with a barrier so `red` (4 doubles) can be reused.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return s;
-}
 
 struct StageArgs {
   const float* x; const float* xp; const float* score; const float* z; const float* coef;
@@ -168,7 +144,7 @@ int check_sizes(int B, long n) {
 }
 
 bool ws_ok(const void* ws, long ws_bytes, int B, long n) {
-  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)B * sde_parts(B, n) * (long)sizeof(double);
+  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)B * stk_row_parts(B, n) * (long)sizeof(double);
 }
 
 }  // namespace
@@ -176,7 +152,7 @@ bool ws_ok(const void* ws, long ws_bytes, int B, long n) {
 extern "C" long stk_sde_ws_bytes(int B, long n_per_sample) {
   const int rc = check_sizes(B, n_per_sample);
   if (rc != STK_OK) return rc;
-  return (long)B * sde_parts(B, n_per_sample) * (long)sizeof(double);
+  return (long)B * stk_row_parts(B, n_per_sample) * (long)sizeof(double);
 }
 
 extern "C" int stk_sde_stage_f32(const float* x, const float* xp, const float* score, const float* z, const float* coef,
@@ -186,7 +162,7 @@ extern "C" int stk_sde_stage_f32(const float* x, const float* xp, const float* s
   if (rc != STK_OK) return rc;
   const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, z, out, xp);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(sde_parts(B, n), sde_rows(B, n));
+  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
   StageArgs a{x, xp, score, z, coef, out};
   return stk_launch_vec(vec, sde_stage_kernel<4>, sde_stage_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }
@@ -201,7 +177,7 @@ extern "C" int stk_sde_heun_error_f32(const float* x, const float* x1, const flo
   if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
   const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1, x1_prev, score2, z, x2);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(sde_parts(B, n), sde_rows(B, n));
+  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
   HeunArgs a{x, x1, x1_prev, score2, z, coef, x2, (double*)ws, atol, rtol};
   return stk_launch_vec(vec, sde_heun_error_kernel<4>, sde_heun_error_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }
@@ -217,7 +193,7 @@ extern "C" int stk_sde_commit_f32(float* x, float* x1_prev, const float* x2, con
   if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
   const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1_prev, x2, x1);
   const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(sde_parts(B, n), sde_rows(B, n));
+  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
   CommitArgs a{x, x1_prev, x2, x1, t, h, (const double*)ws, t_out, h_out, E_out, accept_out, eps, safety, exponent, (double)n};
   return stk_launch_vec(vec, sde_commit_kernel<4>, sde_commit_kernel<1>, grid, (hipStream_t)stream, row, B, a);
 }

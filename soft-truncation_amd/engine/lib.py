@@ -169,6 +169,15 @@ SIGNATURES_SUPERRES = {
   'stk_superres_f32': [P, P, P, P, P, P, P, I, I, I, I, I, S],
   'stk_block_mean_f32': [P, P, L, I, I, I, S],
 }
+# include/stk_posterior.h: the element-wise launches of a diffusion-posterior-sampling step.
+SIGNATURES_POSTERIOR = {
+  'stk_posterior_ws_bytes': [I, L],
+  'stk_tweedie_f32': [P, P, P, P, F, F, P, I, L, S],
+  'stk_residual_f32': [P, P, P, P, L, I, L, S],
+  'stk_guide_seed_f32': [P, P, P, P, F, F, P, L, L, P, P, I, L, S],
+  'stk_guide_update_f32': [P, P, P, P, P, P, P, F, F, F, P, P, I, L, S],
+}
+_RESTYPE_POSTERIOR = {'stk_posterior_ws_bytes': c_long}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -187,6 +196,7 @@ OPTIONAL_HEADERS = (
   Header('has_solver', 'include/stk_solver.h', SIGNATURES_SOLVER, {}, ()),
   Header('has_adaptive', 'include/stk_adaptive.h', SIGNATURES_ADAPTIVE, _RESTYPE_ADAPTIVE, ()),
   Header('has_superres', 'include/stk_superres.h', SIGNATURES_SUPERRES, {}, ()),
+  Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,
