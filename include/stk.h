@@ -45,7 +45,8 @@ int stk_version(void);
 
 /* ------------------------------------------------------------------------------------------
  * FIR resampling: pad -> zero-upsample -> FIR -> decimate, input viewed as
- * [major, in_h, in_w, minor].  out_h = (in_h*up_y + pad_y0 + pad_y1 - kh)/down_y + 1.
+ * [major, in_h, in_w, minor].  out_h = floor((in_h*up_y + pad_y0 + pad_y1 - kh)/down_y) + 1, likewise
+ * out_w; a negative numerator on either axis is an empty output and returns STK_EINVAL (nothing is written).
  * Same argument order as the reference pybind (op/upfirdn2d.cpp:12-14).
  * `stk_upfirdn2d_acc_f32` computes out = beta*out + result (used by the backward pass).
  * ------------------------------------------------------------------------------------------ */

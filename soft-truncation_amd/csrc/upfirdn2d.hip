@@ -419,9 +419,11 @@ int launch(const float* input, const float* kernel, float* out, float beta, int 
   p.in = input; p.k = kernel; p.out = out; p.beta = beta;
   p.major = major; p.in_h = in_h; p.in_w = in_w; p.minor = minor; p.kh = kh; p.kw = kw;
   p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.pad_x0 = pad_x0; p.pad_y0 = pad_y0;
-  p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
-  p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-  if (p.out_h <= 0 || p.out_w <= 0) return STK_EINVAL;
+  // a negative numerator is an empty output (floor division: 0 rows), not the one row C's truncation toward zero gives
+  const int num_h = in_h * up_y + pad_y0 + pad_y1 - kh, num_w = in_w * up_x + pad_x0 + pad_x1 - kw;
+  if (num_h < 0 || num_w < 0) return STK_EINVAL;
+  p.out_h = num_h / down_y + 1;
+  p.out_w = num_w / down_x + 1;
 
   const bool tiled_ok = minor == 1 && up_x == up_y && down_x == down_y && kh <= UFD_MAX_TAPS && kw <= UFD_MAX_TAPS &&
                         ((up_x == 1 && (down_x == 1 || down_x == 2)) || (up_x == 2 && down_x == 1)) &&
@@ -555,9 +557,11 @@ int launch_t(const void* input, const void* kernel, void* out, int major, int in
   UfdParams p = {};
   p.major = major; p.in_h = in_h; p.in_w = in_w; p.minor = minor; p.kh = kh; p.kw = kw;
   p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y; p.pad_x0 = pad_x0; p.pad_y0 = pad_y0;
-  p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
-  p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-  if (p.out_h <= 0 || p.out_w <= 0) return STK_EINVAL;
+  // a negative numerator is an empty output (floor division: 0 rows), not the one row C's truncation toward zero gives
+  const int num_h = in_h * up_y + pad_y0 + pad_y1 - kh, num_w = in_w * up_x + pad_x0 + pad_x1 - kw;
+  if (num_h < 0 || num_w < 0) return STK_EINVAL;
+  p.out_h = num_h / down_y + 1;
+  p.out_w = num_w / down_x + 1;
   const long total = (long)major * p.out_h * p.out_w * minor;
   hipLaunchKernelGGL((upfirdn2d_direct_t<T, ACC>), dim3(stk_ew_grid(total)), dim3(256), 0, stream, static_cast<const T*>(input),
                      static_cast<const T*>(kernel), static_cast<T*>(out), p);

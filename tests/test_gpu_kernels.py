@@ -89,7 +89,7 @@ def test_upfirdn2d(ref_lib, hip_lib, case):
     out = to(o0.clone())
     call(lib, 'upfirdn2d_acc_f32', to(x), to(k), out, float(beta), major, H, W, 1, kh, kw, up, up, down, down,
          p0, p1, p0, p1)
-    out2 = to(torch.zeros_like(o0))
+    out2 = to(torch.full_like(o0, float('nan')))
     call(lib, 'upfirdn2d_f32', to(x), to(k), out2, major, H, W, 1, kh, kw, up, up, down, down, p0, p1, p0, p1)
     return {'acc': out, 'plain': out2}
 
