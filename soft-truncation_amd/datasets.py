@@ -32,6 +32,15 @@ def synthetic_batch(config, batch_size, device=None, generator=None):
   return get_data_scaler(config)(x)
 
 
+def synthetic_classes(config, batch_size, device=None, generator=None):
+  """Labels ~ U{0 .. C - 1} for a synthetic batch of a class-conditional config (config.model.num_classes = C > 0), int64."""
+  C = int(getattr(config.model, 'num_classes', 0) or 0)
+  if C <= 0:
+    raise ValueError('config.model.num_classes is absent or 0: there are no classes to draw')
+  y = torch.randint(0, C, (batch_size,), generator=generator)
+  return y if device is None else y.to(device)
+
+
 def device_batch(config, images_u8, seed, evaluation=False, backend=None):
   """uint8 ``[N, H, W, C]`` images (device tensor) -> float32 ``[N, C, H, W]`` batch for ``step_fn``.
 

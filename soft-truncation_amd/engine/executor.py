@@ -380,10 +380,10 @@ class Program:
 
 class _NetFn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, ex, training, anchor, x, emb_in, sigma):
+  def forward(ctx, ex, training, anchor, x, emb_in, sigma, cls=None):
     need_xgrad = bool(ctx.needs_input_grad[3])
     # grad mode is OFF inside autograd.Function.forward: say explicitly that a backward will follow
-    out, c = ex.run_forward(x, emb_in, sigma, training, need_xgrad, with_backward=True, flat=ex.flat)
+    out, c = ex.run_forward(x, emb_in, sigma, training, need_xgrad, with_backward=True, flat=ex.flat, cls=cls)
     ctx.ex, ctx.c, ctx.need_xgrad = ex, c, need_xgrad
     ex._awaiting.add(c)       # a backward of this evaluation may still come (dropped with the autograd graph otherwise)
     return out
@@ -398,7 +398,7 @@ class _NetFn(torch.autograd.Function):
     # weight / bias / affine gradients are neither computed nor added into p.grad -- as in the reference, where autograd
     # only walks the branches that were asked for.
     gx = ctx.ex.run_backward(ctx.c, gout, param_grads=_wants_param_grads(ctx.ex._anchor_acc))
-    return None, None, None, (gx if ctx.need_xgrad else None), None, None
+    return None, None, None, (gx if ctx.need_xgrad else None), None, None, None
 
 
 def _wants_param_grads(anchor_acc):
@@ -665,13 +665,13 @@ class Executor:
     self.graph_replays += 1
     return True
 
-  def run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward=False, flat=None):
+  def run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward=False, flat=None, cls=None):
     if flat is None:                      # apply() has just checked the layout: one walk over the ~570 parameters per call
       flat = self.ensure_flat()
     with stk_lib.device_guard(flat.device):
-      return self._run_forward(x, emb_in, sigma, training, need_xgrad, with_backward, flat)
+      return self._run_forward(x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls)
 
-  def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat):
+  def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls=None):
     B, _, H, W = x.shape
     if (with_backward or need_xgrad) and self.train_mode != 'fp32':
       precision = self.train_mode + '-train'
@@ -684,6 +684,8 @@ class Executor:
     inputs = {'x': x, 'emb': emb_in}
     if sigma is not None:
       inputs['sigma'] = sigma
+    if cls is not None:                   # the class indices of a class-conditional network, [B] fp32-encoded integers
+      inputs['cls'] = cls
     return self._launch_forward(prog, inputs, training, with_backward, flat)
 
   def _uses_dropout(self):
@@ -869,14 +871,14 @@ class Executor:
     rows.sort(key=lambda r: -r[3])
     return rows
 
-  def apply(self, x, emb_in, sigma=None):
+  def apply(self, x, emb_in, sigma=None, cls=None):
     """Differentiable network evaluation (forward now, backward when autograd asks)."""
     self.ensure_flat()
     training = self.model.training
     x = x.contiguous()
     if torch.is_grad_enabled():
-      return _NetFn.apply(self, training, self._anchor, x, emb_in, sigma)
-    out, c = self.run_forward(x, emb_in, sigma, training, False, flat=self.flat)
+      return _NetFn.apply(self, training, self._anchor, x, emb_in, sigma, cls)
+    out, c = self.run_forward(x, emb_in, sigma, training, False, flat=self.flat, cls=cls)
     c.prog.release(c)
     return out
 

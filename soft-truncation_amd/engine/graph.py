@@ -734,6 +734,36 @@ class FourierEmbedding(Op):
     return self.x.needs_grad
 
 
+class ClassEmbedding(Op):
+  """y[b] = t[b] + table[class[b]] -- the class row of a class-conditional network, added to the time embedding between its
+  two activations (include/stk_cond.h).  `cls` is a graph input of B fp32-encoded integers; row C of the [C + 1, D] table is
+  the null class.  Only the product library has the kernels: on any other the operation is refused here, when the graph is
+  planned.  The backward passes the gradient of t through and adds the rows of the classes present into the table's slot of
+  the flat gradient -- unless the backward is input-only (Runtime.param_grads), which skips it as it skips every parameter."""
+
+  def __init__(self, g, t, cls, table, name='temb.class'):
+    lib = g.lib
+    if not getattr(lib, 'has_cond', False):
+      raise NotImplementedError(f'backend {getattr(lib, "backend", None)} does not export include/stk_cond.h: no kernel adds '
+                                f'the class embedding of a class-conditional network (config.model.num_classes > 0)')
+    self.t, self.cls, self.table = t, cls, table
+    self.B, self.D = t.shape
+    self.C = table.shape[0] - 1
+    if table.shape[1] != self.D or cls.shape != (self.B,):
+      raise RuntimeError(f'{name}: table {tuple(table.shape)} and classes {tuple(cls.shape)} do not fit an embedding '
+                         f'{tuple(t.shape)}')
+    self.y = g.new(t.shape, name=name)
+    self.inputs = (t,)
+
+  def forward(self, rt):
+    rt.lib.class_embed_fwd_f32(rt.v(self.t), rt.v(self.table), rt.v(self.cls), rt.v(self.y), self.B, self.C, self.D, rt.stream)
+
+  def backward(self, rt):
+    gt, gtable = rt.g(self.t), rt.g(self.table)
+    if gt is not None or gtable is not None:
+      rt.lib.class_embed_bwd_f32(rt.g(self.y), rt.v(self.cls), gt, self.b(self.t), gtable, self.B, self.C, self.D, rt.stream)
+
+
 class Affine(Op):
   """y = a*x + b (the `2x - 1` recentring, models/ncsnpp.py:296-298)."""
 

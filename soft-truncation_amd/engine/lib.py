@@ -178,6 +178,13 @@ SIGNATURES_POSTERIOR = {
   'stk_guide_update_f32': [P, P, P, P, P, P, P, F, F, F, P, P, I, L, S],
 }
 _RESTYPE_POSTERIOR = {'stk_posterior_ws_bytes': c_long}
+# include/stk_cond.h: the class embedding of a class-conditional network (engine.graph.ClassEmbedding refuses to plan without
+# it) and the combination of classifier-free guidance.
+SIGNATURES_COND = {
+  'stk_class_embed_fwd_f32': [P, P, P, P, I, I, I, S],
+  'stk_class_embed_bwd_f32': [P, P, P, F, P, I, I, I, S],
+  'stk_cfg_combine_f32': [P, P, F, P, L, S],
+}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -197,6 +204,7 @@ OPTIONAL_HEADERS = (
   Header('has_adaptive', 'include/stk_adaptive.h', SIGNATURES_ADAPTIVE, _RESTYPE_ADAPTIVE, ()),
   Header('has_superres', 'include/stk_superres.h', SIGNATURES_SUPERRES, {}, ()),
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
+  Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,

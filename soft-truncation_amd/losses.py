@@ -337,19 +337,37 @@ def get_step_fn(config, sde, train, optimize_fn=None):
   B/2 losses (losses.py:295-320).
 
   ``config.training.precision = 'fp16'`` runs every micro-batch, forward and backward, in the engine's fp16 training mode
-  (models.utils.training_precision); an absent key means 'fp32', the default path, and any other value raises here."""
+  (models.utils.training_precision); an absent key means 'fp32', the default path, and any other value raises here.
+
+  A class-conditional model (config.model.num_classes = C > 0) takes ``step_fn(state, batch, classes)``: a [n] integer
+  tensor or sequence (C or None: the null class) that follows the images through the micro-batches and the halves of
+  ``training.mixed``.  Per evaluated chunk one ``torch.rand(n) < config.training.class_dropout`` (default 0.1; 0 draws
+  nothing) is drawn BEFORE the loss's own draws and sends those samples to the null class: the unconditional branch
+  classifier-free guidance needs.  The values of a device tensor are not read back (no host synchronisation per step):
+  an index outside [0, C] takes the null row in the kernels.  ValueError: a conditional model without classes, an
+  unconditional one with classes, classes of another length than the batch."""
   precision = mutils.config_training_precision(config)
   loss_fn = _pick_loss_fn(config, sde, train)
   tr = config.training
   mixed = bool(tr.mixed)
+  class_dropout = float(mutils.config_option(config, 'training', 'class_dropout', 0.1))
 
-  def plain_losses(model, chunk, t_min):
-    return loss_fn(model, chunk, importance_sampling=tr.importance_sampling, t_min=t_min)
+  def evaluated(model, chunk, cls, **kw):
+    """loss_fn on one chunk, under its classes (None: an unconditional model) after label dropout."""
+    if cls is None:
+      return loss_fn(model, chunk, **kw)
+    if class_dropout > 0:
+      cls = cls.masked_fill(torch.rand(cls.shape[0], device=cls.device) < class_dropout, float(mutils.num_classes(model)))
+    with mutils.classes_in_force(model, cls):
+      return loss_fn(model, chunk, **kw)
 
-  def mixed_losses(model, chunk, t_min):
+  def plain_losses(model, chunk, t_min, cls=None):
+    return evaluated(model, chunk, cls, importance_sampling=tr.importance_sampling, t_min=t_min)
+
+  def mixed_losses(model, chunk, t_min, cls=None):
     half = chunk.shape[0] // 2
-    l_is = loss_fn(model, chunk[:half], importance_sampling=True, t_min=t_min)
-    l_ddpm = loss_fn(model, chunk[half:], importance_sampling=False, t_min=t_min)
+    l_is = evaluated(model, chunk[:half], None if cls is None else cls[:half], importance_sampling=True, t_min=t_min)
+    l_ddpm = evaluated(model, chunk[half:], None if cls is None else cls[half:], importance_sampling=False, t_min=t_min)
     weight = tr.ddpm_weight
     if tr.balanced:
       weight = weight * torch.mean(l_is / l_ddpm).detach().item()
@@ -359,11 +377,27 @@ def get_step_fn(config, sde, train, optimize_fn=None):
   staging = {}       # number of losses -> pinned host buffer of the asynchronous device-to-host copy
   range_every = RANGE_CHECK_EVERY if RANGE_CHECK_EVERY is not None else (1000 if getattr(tr, 'likelihood_weighting', False) else 0)
 
-  def step_fn(state, batch):
+  def step_classes(model, batch, classes):
+    """`classes` as the [n] float32 tensor the engine takes, on the batch's device; None for an unconditional model."""
+    C = mutils.num_classes(model)
+    if C == 0:
+      if classes is not None:
+        raise ValueError('step_fn was given classes, but the model is not class-conditional (config.model.num_classes)')
+      return None
+    if classes is None:
+      raise ValueError(f'a class-conditional model (config.model.num_classes = {C}) needs step_fn(state, batch, classes)')
+    on_device = torch.is_tensor(classes) and classes.device.type != 'cpu'
+    cls = mutils.as_class_tensor(classes, C, read_values=not on_device)
+    if cls.shape[0] != batch.shape[0]:
+      raise ValueError(f'{cls.shape[0]} classes for a batch of {batch.shape[0]} images')
+    return cls.to(device=batch.device, dtype=torch.float32)
+
+  def step_fn(state, batch, classes=None):
     model, optimizer = state['model'], state['optimizer']
     if not train:
       # the reference has no evaluation branch either: its `return losses_` raises exactly this (losses.py:279-293)
       raise UnboundLocalError("local variable 'losses_' referenced before assignment")
+    cls = step_classes(model, batch, classes)
     optimizer.zero_grad()
     n, parts = batch.shape[0], config.optim.num_micro_batch
     per = n // parts
@@ -374,11 +408,12 @@ def get_step_fn(config, sde, train, optimize_fn=None):
     ddp.begin_step(model)
     try:
       for k in range(parts):
+        of_chunk = () if cls is None else (cls[per * k: per * (k + 1)],)
         if precision != 'fp32':
           with mutils.training_precision(model, precision):
-            losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min)
+            losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, *of_chunk)
         else:
-          losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min)
+          losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, *of_chunk)
         if k == parts - 1 and OVERLAP_EXCHANGE:
           # multi-GPU: buckets of the flat gradient buffer are all-reduced as the last backward finishes them (with
           # several network evaluations per loss -- training.mixed -- as the LAST of their backwards does)

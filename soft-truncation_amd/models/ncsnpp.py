@@ -16,6 +16,7 @@ import torch.nn as nn
 from . import layers, layerspp, utils
 from ..engine import executor as _executor
 from ..engine import graph as G
+from ..engine import lib as _stk_lib
 from ..engine.graph import SQRT2
 
 ResnetBlockDDPM = layerspp.ResnetBlockDDPMpp
@@ -29,6 +30,17 @@ default_initializer = layers.default_init
 
 def _gn(ch):
   return nn.GroupNorm(num_groups=min(ch // 4, 32), num_channels=ch, eps=1e-6)
+
+
+class ClassTable(nn.Module):
+  """The class rows of a class-conditional network: ``weight`` [C + 1, D], row C the null class, all zeros at first -- a
+  fresh conditional network then computes what the unconditional one does, and an unconditional checkpoint loaded with
+  ``strict=False`` is a warm start.  A holder of the parameter only: the rows are added inside the planned graph
+  (engine.graph.ClassEmbedding)."""
+
+  def __init__(self, num_classes, dim):
+    super().__init__()
+    self.weight = nn.Parameter(torch.zeros(num_classes + 1, dim))
 
 
 @utils.register_model(name='ncsnpp')
@@ -56,6 +68,11 @@ class NCSNpp(nn.Module):
     self.all_resolutions = all_resolutions = [config.data.image_size // (2 ** i) for i in range(num_resolutions)]
 
     self.conditional = conditional = m.conditional
+    # class conditioning (absent from the reference): 0 = off, the network of the reference, key for key
+    self.num_classes = num_classes = int(utils.config_option(config, 'model', 'num_classes', 0) or 0)
+    if num_classes < 0 or (num_classes > 0 and not conditional):
+      raise ValueError(f'config.model.num_classes = {num_classes} needs config.model.conditional (the class row is added to '
+                       f'the time embedding) and must not be negative')
     fir = m.fir
     fir_kernel = m.fir_kernel
     self.skip_rescale = skip_rescale = m.skip_rescale
@@ -202,6 +219,10 @@ class NCSNpp(nn.Module):
       modules.append(conv3x3(in_ch, channels, init_scale=init_scale))
 
     self.all_modules = nn.ModuleList(modules)
+    if num_classes > 0:         # outside all_modules: the all_modules.<i>.* keys keep their indices
+      self.class_emb = ClassTable(num_classes, embed_dim_2 * 4)
+    self._class_ctx = None      # (classes, guidance, [classes; null]) in force: models.utils.class_condition
+    self._null_rows = {}
     self._engine = None
     self._backend = None
 
@@ -227,6 +248,10 @@ class NCSNpp(nn.Module):
     dense = self._dense_blocks()
     if dense:
       groups += [[b.Dense_0.weight for b in dense], [b.Dense_0.bias for b in dense]]
+    if self.num_classes:
+      # beside the stacked projections at the bottom of the flat buffers: its gradient is among the last the backward
+      # writes, as theirs are, so the buckets above become final as early as in the unconditional network
+      groups.append([self.class_emb.weight])
     for mod in self.modules():
       if isinstance(mod, layerspp.AttnBlockpp):
         ws, bs = mod.qkv_params()
@@ -236,8 +261,38 @@ class NCSNpp(nn.Module):
   def _uses_dropout(self):
     return any(isinstance(mod, nn.Dropout) and mod.p > 0 for mod in self.modules())
 
+  def null_classes(self, B, device):
+    """[B] class indices that all name the null row, as the engine takes them (fp32-encoded)."""
+    t = self._null_rows.get((B, device))
+    if t is None:
+      t = self._null_rows[(B, device)] = torch.full((B,), float(self.num_classes), dtype=torch.float32, device=device)
+    return t
+
   def forward(self, x, time_cond):
-    """x [B,C,H,W] fp32, time_cond [B] fp32 -> [B,C,H,W] (models/ncsnpp.py:258-432)."""
+    """x [B,C,H,W] fp32, time_cond [B] fp32 -> [B,C,H,W] (models/ncsnpp.py:258-432).  A class-conditional network
+    (config.model.num_classes > 0) takes the classes and the guidance weight in force (models.utils.class_condition): no
+    classes, every sample on the null row; a guidance weight w != 0, ONE evaluation of [x; x] with classes [y; null] and
+    out = c + w (c - u) of its halves -- by stk_cfg_combine_f32, or by torch operators under grad mode, where autograd
+    has to see it."""
+    if not self.num_classes:
+      return self._forward(x, time_cond, None)
+    B = x.shape[0]
+    cls, w, both = self._class_ctx if self._class_ctx is not None else (self.null_classes(B, x.device), 0.0, None)
+    if cls.shape[0] != B:
+      raise ValueError(f'class_condition holds {cls.shape[0]} classes, the batch evaluated has {B} samples')
+    if w == 0.0:
+      return self._forward(x, time_cond, cls)
+    out = self._forward(torch.cat([x, x]), torch.cat([time_cond, time_cond]), both)
+    c, u = out[:B], out[B:]
+    if torch.is_grad_enabled():
+      return c + w * (c - u)
+    lib = self.engine().lib
+    res = torch.empty_like(c)
+    with _stk_lib.device_guard(c.device):
+      lib.cfg_combine_f32(c.data_ptr(), u.data_ptr(), w, res.data_ptr(), c.numel(), _stk_lib.stream_ptr(c.device))
+    return res
+
+  def _forward(self, x, time_cond, cls):
     sigma = None
     if self.embedding_type == 'fourier':
       used_sigmas = time_cond
@@ -251,7 +306,7 @@ class NCSNpp(nn.Module):
         used_sigmas = self.sigmas[time_cond.long()].to(torch.float32)
     if self.config.model.scale_by_sigma:
       sigma = used_sigmas
-    return self.engine().apply(x, emb_in.to(torch.float32), sigma)
+    return self.engine().apply(x, emb_in.to(torch.float32), sigma, cls)
 
   # ------------------------------------------------------------------------------------------------
   # lowering: the walk of models/ncsnpp.py:258-432, emitted into the engine graph
@@ -265,6 +320,7 @@ class NCSNpp(nn.Module):
     x = g.input('x', (B, C, H, W), needs_grad=need_xgrad)
     emb_in = g.input('emb', (B,))
     sigma = g.input('sigma', (B,)) if cfg.model.scale_by_sigma else None
+    cls = g.input('cls', (B,)) if self.num_classes else None
 
     if self.embedding_type == 'fourier':
       temb = g.add(G.FourierEmbedding(g, emb_in, g.param(modules[m_idx].W)))
@@ -278,6 +334,8 @@ class NCSNpp(nn.Module):
       m_idx += 1
       temb = g.linear(g.silu(temb, name='temb.act0'), modules[m_idx].weight, modules[m_idx].bias, name='temb.l1')
       m_idx += 1
+      if cls is not None:
+        temb = g.add(G.ClassEmbedding(g, temb, cls, g.param(self.class_emb.weight)))
       dense = self._dense_blocks()
       if dense:
         # all Dense_0(act(temb)) of the residual blocks as ONE GEMM over the stacked weights

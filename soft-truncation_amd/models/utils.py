@@ -13,6 +13,7 @@ initialised, averages gradients with one bucketed RCCL all-reduce per step
 (see ``engine/ddp.py``).
 """
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -149,6 +150,83 @@ def config_training_precision(config):
 def sampling_precision(config):
   """config.sampling.precision: 'fp32' when the key is absent, else checked."""
   return check_precision(config_option(config, 'sampling', 'precision', 'fp32'), 'config.sampling.precision')
+
+
+# ---- class conditioning and classifier-free guidance (include/stk_cond.h) ----------------------------------------------------
+def num_classes(model):
+  """C of a class-conditional network (config.model.num_classes), 0 for any other model; sees through DataParallel."""
+  return int(getattr(getattr(model, 'module', model), 'num_classes', 0) or 0)
+
+
+def as_class_tensor(classes, C, read_values=True):
+  """`classes` -- a 1-D integer tensor, or a sequence of integers and None -- as an int64 tensor with None replaced by the
+  null class C.  ValueError for another shape or dtype, for an empty batch, and (read_values: ONE host read of a device
+  tensor) for a value outside [0, C]."""
+  if torch.is_tensor(classes):
+    if classes.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+      raise ValueError(f'classes must be an integer tensor, got {classes.dtype}')
+    t = classes.to(torch.int64)
+  else:
+    try:
+      items = list(classes)
+    except TypeError:
+      raise ValueError(f'classes must be a [B] integer tensor or a sequence, got {type(classes).__name__}') from None
+    for v in items:
+      if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+        raise ValueError(f'classes must hold integers or None, got {v!r}')
+    t = torch.tensor([C if v is None else int(v) for v in items], dtype=torch.int64)
+  if t.dim() != 1 or t.numel() == 0:
+    raise ValueError(f'classes must have shape [B] with B > 0, got {tuple(t.shape)}')
+  if read_values:
+    lo, hi = torch.stack(torch.aminmax(t)).tolist()
+    if lo < 0 or hi > C:
+      raise ValueError(f'classes must lie in [0, {C}] ({C} is the null class), got values from {lo} to {hi}')
+  return t
+
+
+@contextlib.contextmanager
+def classes_in_force(model, cls):
+  """The unchecked core of :func:`class_condition` without guidance, for callers that have checked already (get_step_fn):
+  `cls` is a [B] float32 tensor of class indices on the model's device."""
+  inner = getattr(model, 'module', model)
+  saved, inner._class_ctx = inner._class_ctx, (cls, 0.0, None)
+  try:
+    yield
+  finally:
+    inner._class_ctx = saved
+
+
+@contextlib.contextmanager
+def class_condition(model, classes, guidance=0.0):
+  """Context manager: every network evaluation of the class-conditional `model` inside it is conditioned on `classes` -- a
+  [B] integer tensor or sequence, the value C (= config.model.num_classes) or None for the null class -- with
+  classifier-free guidance of weight `guidance`: out = c + guidance (c - u), c the evaluation with the classes, u the one
+  with the null class.  guidance = 0 is the plain conditional evaluation, one pass at batch B, bit for bit; any other
+  weight costs ONE pass at batch 2 B ([x; x] with classes [y; null]) and one launch of stk_cfg_combine_f32 (torch
+  operators under grad mode, where autograd has to see the combination), and the engine's arena of a batch of 2 B.
+
+  Every sampler takes classes through it unchanged: ``with class_condition(model, y, 1.5): sampling_fn(model)``.
+  Checked once, on entry, with one host read: ValueError for a model that is not class-conditional, a wrong shape or
+  dtype, a value outside [0, C], a guidance weight that is not finite; an evaluation of a batch of another size inside it
+  raises ValueError too.  Contexts nest and restore; `model` may be the DataParallel wrapper."""
+  inner = getattr(model, 'module', model)
+  C = num_classes(model)
+  if C <= 0:
+    raise ValueError(f'{type(inner).__name__} is not class-conditional (config.model.num_classes is absent or 0)')
+  try:
+    w = float(guidance)
+  except (TypeError, ValueError):
+    raise ValueError(f'guidance must be a finite number, got {guidance!r}') from None
+  if not math.isfinite(w):
+    raise ValueError(f'guidance must be a finite number, got {guidance!r}')
+  device = next(inner.parameters()).device
+  cls = as_class_tensor(classes, C).to(device=device, dtype=torch.float32)
+  both = torch.cat([cls, inner.null_classes(cls.shape[0], device)]) if w != 0.0 else None
+  saved, inner._class_ctx = inner._class_ctx, (cls, w, both)
+  try:
+    yield
+  finally:
+    inner._class_ctx = saved
 
 
 # ---- what the samplers share (sampling.py, controllable_generation.py, dpm_solver.py, adaptive_sde.py) --------------------
