@@ -3,7 +3,9 @@
 //     s[t, t'] = C^-0.5 sum_c q[c, t] k[c, t']        p = softmax over t'        o[c, t] = sum_t' v[c, t'] p[t, t']
 //
 // on q, k, v, o of shape [B, C, T] (NCHW with T = H W <= 256 positions, one head of all C <= 256 channels), forward and
-// backward, without a [B, T, T] matrix in HBM.  The reference runs two einsums and a softmax (five more einsums and a
+// backward, without a [B, T, T] matrix in HBM.  Several heads (include/stk_attention_mh.h: contiguous channel slices of
+// d = C / heads <= 256 channels, C itself unbounded) run the same kernel under a workgroup index of (image, head): see MH
+// at attn_kernel and the end of the file.  The reference runs two einsums and a softmax (five more einsums and a
 // softmax backward under autograd); round 1 ran them as batched GEMMs on the f32-input MFMA (157 TFLOP/s peak) with the
 // score and probability matrices written to and read from HBM.
 //
@@ -36,6 +38,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "attention_mh.h"
 #include "common.h"
 #include "split.h"
 
@@ -107,6 +110,8 @@ struct Args {
   float* delta;           // [B, T]  DQ: written; DKV: read
   int B, C, T; float scale;
   long long* dbg;         // development aid: cycle stamps of workgroup 0 / wave 0 at the phase boundaries (NULL: off)
+  int H;                  // MH kernels: heads.  C is then the width d of ONE head, and workgroup (b, n) finds its head of an
+                          // operand n d T floats into image b and its lse / delta row at (b H + n) T
 };
 
 template <int MODE, int TK>
@@ -148,7 +153,16 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_in
 // stream (fragment reads, LDS store hand-off, barrier) and hides at most ~5 issue slots behind an MFMA; measured with
 // four waves, a chunk took 2400 cycles of which the MFMAs are 768.  With a partner wave on the SIMD the two streams
 // fill each other's gaps.
-template <int MODE, int TK, bool FULL>
+//
+// MH (include/stk_attention_mh.h): the workgroup index is (image, head) and the contraction width is the head's d = a.C.
+// FULL then means d == FC and T == TK: the head widths of the guided-diffusion recipe (32, 64, 128) get the same
+// straight-line code as C = 256.  Phase B of a narrow head: with d <= 128 a head has at most four 32-channel blocks, so "one block per
+// wave" would leave half (d = 128) or three quarters (d = 64) of the eight waves without an MFMA; SPLITN hands out
+// (32-channel block) x (32-position half of the n tile) instead -- wave w owns block w / 2 and half w % 2, six MFMAs per
+// 32 contracted positions -- and the A stage holds, and each thread converts, ceil(d / 64) pieces per block instead of 4.
+// A wave whose first channel block lies at or beyond d (any MH kernel, rolled ones included) issues no MFMA in phase B: it
+// stages its pieces, keeps the barriers and stores nothing.
+template <int MODE, int TK, bool FULL, bool MH = false, int FC = 256>
 __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // NT threads, NW / 4 waves per SIMD
   using G = Geo<MODE, TK>;
   constexpr int NG = G::NG, CK = G::CK, KS = G::KS, NW = G::NW, NT = G::NT;
@@ -161,8 +175,10 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntile = FULL ? TK / 64 : (a.T + 63) >> 6;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
-  const int b = id / ntile, n0 = (id - b * ntile) * 64;
-  const int T = FULL ? TK : a.T, C = FULL ? 256 : a.C;
+  const int bh = id / ntile, n0 = (id - bh * ntile) * 64;      // bh: the lse / delta row (b H + n for MH, else b)
+  const int b = MH ? bh / a.H : bh;
+  const int T = FULL ? TK : a.T, C = FULL ? FC : a.C;
+  const unsigned hoff = MH ? (unsigned)((bh - b * a.H) * C * T) * 4u : 0u;   // bytes from an image to this head's channels
   int stamp_i = 0;
   auto stamp = [&]() __attribute__((always_inline)) {
     if (a.dbg && blockIdx.x == 0 && tid == 0) a.dbg[stamp_i] = (long long)__builtin_amdgcn_s_memtime();
@@ -193,14 +209,14 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
   }
   if (MODE == MODE_DKV) {
     for (int m = tid; m < TK; m += NT) {
-      rowstat[0][m] = m < T ? a.lse[(long)b * T + m] : INFINITY;       // exp(s - inf) = 0 for the padding rows
-      rowstat[1][m] = m < T ? a.delta[(long)b * T + m] : 0.f;
+      rowstat[0][m] = m < T ? a.lse[(long)bh * T + m] : INFINITY;       // exp(s - inf) = 0 for the padding rows
+      rowstat[1][m] = m < T ? a.delta[(long)bh * T + m] : 0.f;
     }
   }
 
   stamp();
   // ---- phase A: D_g[m, n] = sum_c X_g[c, m] Y_g[c, n];  wave w owns rows m = 32 w .. 32 w + 31 -------------------------
-  auto bytes_of = [&](long bstride) { return ((long)(a.B - 1) * bstride + (long)C * T) * 4; };
+  auto bytes_of = [&](long bstride) { return ((long)(a.B - 1) * bstride + (long)(MH ? a.H * C : C) * T) * 4; };
   const int l8 = lane >> 3, l7 = lane & 7;
   __amdgpu_buffer_rsrc_t xrs[NG], yrs[NG];
 #pragma unroll
@@ -236,13 +252,13 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
 #pragma unroll
       for (int j = 0; j < G::XI; ++j)
         ra[S][g * G::XI + j] = __builtin_bit_cast(
-            u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs[g], (int)xvo[j], (int)((unsigned)(b * a.xs[g]) * 4u + coff), 0));
+            u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs[g], (int)xvo[j], (int)((unsigned)(b * a.xs[g]) * 4u + coff + hoff), 0));
 #pragma unroll
     for (int j = 0; j < G::YT; ++j) {
       const bool second = NG == 2 && yg[j];
       ra[S][NG * G::XI + j] = __builtin_bit_cast(
           u32x4, __builtin_amdgcn_raw_buffer_load_b128(second ? yrs[NG - 1] : yrs[0], (int)yvo[j],
-                                                       (int)((unsigned)(b * (second ? a.ys[NG - 1] : a.ys[0])) * 4u + coff), 0));
+                                                       (int)((unsigned)(b * (second ? a.ys[NG - 1] : a.ys[0])) * 4u + coff + hoff), 0));
     }
   };
   // A piece goes to LDS in two halves (so that they can be placed between MFMAs): scale + hi terms, then lo terms + stores
@@ -354,7 +370,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
   stage(P0{}, lds);
   __syncthreads();
   if constexpr (FULL) {
-    constexpr int NCH = 256 / CK;
+    constexpr int NCH = FC / CK;
     static_for<NCH>([&](auto ci) __attribute__((always_inline)) {
       constexpr int c = decltype(ci)::value;
       chunk_a(std::integral_constant<int, (c & 1)>{}, std::bool_constant<(c + 1 < NCH)>{}, c + 2 < NCH, c);
@@ -373,7 +389,11 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
 
   stamp();
   // ---- phase B plumbing: out[c, n] = sum_k A[c, k] bm[n, k];  wave w owns channel blocks CBW w .. CBW w + CBW - 1 ------
-  constexpr int CBW = G::CBW, AI = G::AI;
+  constexpr bool SPLITN = MH && FULL && FC <= 128 && NW == 8;
+  constexpr int CBW = SPLITN ? 1 : G::CBW, NBW = SPLITN ? 1 : 2;            // channel blocks / n halves of a wave
+  constexpr int AI = FULL ? (FC / 8 + NW - 1) / NW : G::AI;                 // pieces with a channel below FC
+  const int cb0 = SPLITN ? wid >> 1 : CBW * wid, nb0 = SPLITN ? wid & 1 : 0;
+  const bool wlive = !MH || cb0 * 32 < C;                                   // wave-uniform: this wave has a tile of phase B
   __amdgpu_buffer_rsrc_t ars = make_rsrc(a.a[0], bytes_of(a.as[0]));
   long a_bs = a.as[0];
   const int KB = FULL ? TK / 32 : (T + 31) >> 5;              // 32-position blocks of the contraction
@@ -387,15 +407,15 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
   u32x4 rb[2][AI];
   auto fetch_a = [&](auto SET, int kb) __attribute__((always_inline)) {
     constexpr int S = decltype(SET)::value;
-    const unsigned soff = (unsigned)(b * a_bs + kb * 32) * 4u;
+    const unsigned soff = (unsigned)(b * a_bs + kb * 32) * 4u + hoff;
     const unsigned dead = (FULL || kb * 32 + 4 * l7 < T) ? 0u : 0x80000000u;
 #pragma unroll
     for (int j = 0; j < AI; ++j)
       rb[S][j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, (int)(avo[j] | dead), (int)soff, 0));
   };
   const int fk = lane >> 5, fc = lane & 31;
-  floatx16 oacc[CBW][2];
-  constexpr int NMB = 12 * CBW, PRE_B = (2 * AI) / 5, REST_B = 2 * AI - PRE_B;
+  floatx16 oacc[CBW][NBW];
+  constexpr int NMB = 6 * NBW * CBW, PRE_B = (2 * AI) / 5, REST_B = 2 * AI - PRE_B;
   // One 32-position block of phase B, the next block's pieces staged between the MFMAs
   auto block_b = [&](auto PAR, auto MORE, bool fetch2, int kb, float s_a) __attribute__((always_inline)) {
     constexpr int P = decltype(PAR)::value;
@@ -403,19 +423,26 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
     const unsigned char* abuf = lds + P * G::ASTAGE;
     unsigned char* nxt = lds + (1 - P) * G::ASTAGE;
     if (fetch2) fetch_a(PAR, kb + 2);
-    halfx8 af[2][CBW][2], bf[2][2][2];                          // [k step][block][plane]
+    Half h;
+    if (MH && !wlive) {                                         // no tile: this wave only stages its pieces of the next block
+      if (more) {
+#pragma unroll
+        for (int j = 0; j < AI; ++j) { half_a(h, rb[1 - P][j], s_a); half_b(h, nxt, G::AP, adst[j]); }
+      }
+      return;
+    }
+    halfx8 af[2][CBW][2], bf[2][NBW][2];                        // [k step][block][plane]
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
 #pragma unroll
         for (int cb = 0; cb < CBW; ++cb)
-          af[kk][cb][p] = *reinterpret_cast<const halfx8*>(abuf + p * G::AP + ((CBW * wid + cb) * 32 + fc) * G::APITCH + (kk * 16 + 8 * fk) * 2);
+          af[kk][cb][p] = *reinterpret_cast<const halfx8*>(abuf + p * G::AP + ((cb0 + cb) * 32 + fc) * G::APITCH + (kk * 16 + 8 * fk) * 2);
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-          bf[kk][nb][p] = *reinterpret_cast<const halfx8*>(bm + p * G::BP + (nb * 32 + fc) * G::BPITCH + (kb * 32 + kk * 16 + 8 * fk) * 2);
+        for (int nb = 0; nb < NBW; ++nb)
+          bf[kk][nb][p] = *reinterpret_cast<const halfx8*>(bm + p * G::BP + ((nb0 + nb) * 32 + fc) * G::BPITCH + (kb * 32 + kk * 16 + 8 * fk) * 2);
       }
-    Half h;
     int hp = 0;
     auto half_piece = [&]() __attribute__((always_inline)) {
       if (more) {
@@ -429,7 +456,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NMB; ++i) {
-      const int kk = i / (6 * CBW), r = i % (6 * CBW), pr = r / (2 * CBW), cb = (r / 2) % CBW, nb = r % 2;
+      const int kk = i / (3 * NBW * CBW), r = i % (3 * NBW * CBW), pr = r / (NBW * CBW), cb = (r / NBW) % CBW, nb = r % NBW;
       oacc[cb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[kk][cb][SA[pr]], bf[kk][nb][SB[pr]], oacc[cb][nb], 0, 0, 0);
       if (((i + 1) * REST_B) / NMB > (i * REST_B) / NMB) half_piece();
       __builtin_amdgcn_sched_barrier(0);
@@ -456,7 +483,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
 #pragma unroll
     for (int cb = 0; cb < CBW; ++cb)
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
+      for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
         for (int e = 0; e < 16; ++e) oacc[cb][nb][e] = 0.f;
     fetch_a(P0{}, 0);
@@ -487,14 +514,15 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
     __amdgpu_buffer_rsrc_t ors = make_rsrc(a.out[which], bytes_of(a.os[which]));
     const float beta = a.beta[which];
     const float inv = 1.f / (s_a * s_b);
-    const unsigned obase = (unsigned)(b * a.os[which]) * 4u;
+    const unsigned obase = (unsigned)(b * a.os[which]) * 4u + hoff;
+    if (MH && !wlive) return;
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      const int n = n0 + nb * 32 + fc;
-      const float f = inv * post[nb];
+    for (int nb = 0; nb < NBW; ++nb) {
+      const int n = n0 + (nb0 + nb) * 32 + fc;
+      const float f = inv * (SPLITN ? (nb0 ? post[1] : post[0]) : post[nb]);
 #pragma unroll
       for (int cb = 0; cb < CBW; ++cb) {
-        const int cbase = (CBW * wid + cb) * 32 + 4 * fk;
+        const int cbase = (cb0 + cb) * 32 + 4 * fk;
         const unsigned vo = (unsigned)(cbase * T + n) * 4u | ((n < T && cbase < C) ? 0u : 0x80000000u);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -554,7 +582,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
     if (wid == 0 && fk == 0) {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
-        if (n0 + nb * 32 + fc < T) a.lse[(long)b * T + n0 + nb * 32 + fc] = mx[nb] + logf(sum[nb]);
+        if (n0 + nb * 32 + fc < T) a.lse[(long)bh * T + n0 + nb * 32 + fc] = mx[nb] + logf(sum[nb]);
     }
     stamp();
     put_bm(acc[0], P_SCALE);
@@ -570,7 +598,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const int n = n0 + nb * 32 + fc;
-        lse_n[nb] = n < T ? a.lse[(long)b * T + n] : 0.f;
+        lse_n[nb] = n < T ? a.lse[(long)bh * T + n] : 0.f;
       }
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
@@ -587,7 +615,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
       if (wid == 0 && fk == 0) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
-          if (n0 + nb * 32 + fc < T) a.delta[(long)b * T + n0 + nb * 32 + fc] = dl[nb];
+          if (n0 + nb * 32 + fc < T) a.delta[(long)bh * T + n0 + nb * 32 + fc] = dl[nb];
       }
     }
     float dmax = 0.f;
@@ -615,14 +643,21 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
 #pragma unroll
     for (int w = 1; w < NW; ++w) dm = fmaxf(dm, sred[w]);
     const float sds = pow2_scale_of(dm);
+    // MH: a gradient nobody wants has a NULL out (wave-uniform): its GEMM is skipped (DQ then only writes delta)
     if (MODE == MODE_DQ) {
-      put_bm(acc[1], sds);
-      phase_b(0, sa[0], sds, ones);                            // dq = k ds
+      if (!MH || a.out[0]) {
+        put_bm(acc[1], sds);
+        phase_b(0, sa[0], sds, ones);                          // dq = k ds
+      }
     } else {
-      put_bm(acc[0], P_SCALE);
-      phase_b(0, sa[0], P_SCALE, ones);                        // dv = do p      (ends with a barrier: bm is free again)
-      put_bm(acc[1], sds);
-      phase_b(1, sa[1], sds, ones);                            // dk = q ds
+      if (!MH || a.out[0]) {
+        put_bm(acc[0], P_SCALE);
+        phase_b(0, sa[0], P_SCALE, ones);                      // dv = do p      (ends with a barrier: bm is free again)
+      }
+      if (!MH || a.out[1]) {
+        put_bm(acc[1], sds);
+        phase_b(1, sa[1], sds, ones);                          // dk = q ds
+      }
     }
   }
 }
@@ -640,6 +675,21 @@ int launch(const Args& a, hipStream_t s) {
   if (a.T == 256 && a.C == 256) hipLaunchKernelGGL((attn_kernel<MODE, 256, true>), dim3(grid), dim3(512), 0, s, a);
   else if (a.T <= 128) hipLaunchKernelGGL((attn_kernel<MODE, 128, false>), dim3(grid), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((attn_kernel<MODE, 256, false>), dim3(grid), dim3(512), 0, s, a);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+// The MH instantiations: the straight-line code for a head of 32, 64, 128 or 256 channels on a full 16 x 16 map, the rolled
+// kernels for the rest.  a.C is the head width.
+template <int MODE>
+int launch_mh(const Args& a, hipStream_t s) {
+  const unsigned grid = (unsigned)(a.B * a.H * ((a.T + 63) / 64));
+  if (a.T == 256 && a.C == 32) hipLaunchKernelGGL((attn_kernel<MODE, 256, true, true, 32>), dim3(grid), dim3(512), 0, s, a);
+  else if (a.T == 256 && a.C == 64) hipLaunchKernelGGL((attn_kernel<MODE, 256, true, true, 64>), dim3(grid), dim3(512), 0, s, a);
+  else if (a.T == 256 && a.C == 128) hipLaunchKernelGGL((attn_kernel<MODE, 256, true, true, 128>), dim3(grid), dim3(512), 0, s, a);
+  else if (a.T == 256 && a.C == 256) hipLaunchKernelGGL((attn_kernel<MODE, 256, true, true, 256>), dim3(grid), dim3(512), 0, s, a);
+  else if (a.T <= 128) hipLaunchKernelGGL((attn_kernel<MODE, 128, false, true>), dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_kernel<MODE, 256, false, true>), dim3(grid), dim3(512), 0, s, a);
   STK_CHECK_LAUNCH();
   return STK_OK;
 }
@@ -718,3 +768,67 @@ int stk_attention_bwd_f32(const float* q, const float* k, const float* v, long q
 }
 
 }  // extern "C"
+
+// ---- the short form of include/stk_attention_mh.h (its entries are in attention_long.hip, which picks the form) ----------
+
+namespace stk_mh {
+
+bool short_ok(int B, int C, int T, int heads) {
+  if (B <= 0 || heads <= 0 || C <= 0 || C % heads) return false;
+  const int d = C / heads;
+  return d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= 256 && T % 4 == 0 && (long)B * C * T * 4 < 0x7fffffffL;
+}
+
+int short_fwd(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse, float* rec, int B, int C,
+              int T, int heads, float scale, void* stream) {
+  if (heads == 1) return stk_attention_fwd_f32(q, k, v, qkv_bstride, o, lse, rec, B, C, T, scale, stream);
+  if (!short_ok(B, C, T, heads) || !stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v))
+    return STK_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  AmaxArgs m = {};
+  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
+  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  Args a = {};
+  fwd_args(a, q, k, v, qkv_bstride, o, lse, rec, B, C / heads, T, scale);
+  a.os[0] = a.os[1] = (long)C * T; a.H = heads;
+  return launch_mh<MODE_FWD>(a, s);
+}
+
+int short_bwd(const float* q, const float* k, const float* v, long qkv_bstride, const float* d_o, const float* lse, float* rec,
+              float* delta, float* dq, float beta_q, float* dk, float beta_k, float* dv, float beta_v, long grad_bstride, int B,
+              int C, int T, int heads, float scale, void* stream) {
+  if (heads == 1 && dq && dk && dv)
+    return stk_attention_bwd_f32(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B,
+                                 C, T, scale, stream);
+  if (!short_ok(B, C, T, heads) || !stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) ||
+      !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(d_o))
+    return STK_EUNSUPPORTED;
+  if (!dq && !dk && !dv) return STK_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const long ct = (long)C * T;
+  float* rq = rec; float* rk = rec + NPART; float* rv = rec + 2 * NPART; float* rdo = rec + 3 * NPART;
+  AmaxArgs m = {};
+  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  Args a = {};
+  a.B = B; a.C = C / heads; a.H = heads; a.T = T; a.scale = scale; a.lse = const_cast<float*>(lse); a.delta = delta;
+  const long bs = qkv_bstride, gs = grad_bstride;
+  // as stk_attention_bwd_f32; the DQ kernel also writes delta, so it runs even when only dk / dv are wanted (and then
+  // skips its phase B)
+  a.x[0] = k; a.rx[0] = rk; a.xs[0] = bs; a.x[1] = v; a.rx[1] = rv; a.xs[1] = bs;
+  a.y[0] = q; a.ry[0] = rq; a.ys[0] = bs; a.y[1] = d_o; a.ry[1] = rdo; a.ys[1] = ct;
+  a.a[0] = k; a.ra[0] = rk; a.as[0] = bs; a.a[1] = k; a.ra[1] = rk; a.as[1] = bs;
+  a.out[0] = dq; a.out[1] = dq; a.os[0] = a.os[1] = gs; a.beta[0] = a.beta[1] = beta_q;
+  int rc = launch_mh<MODE_DQ>(a, s);
+  if (rc || (!dk && !dv)) return rc;
+  a.x[0] = q; a.rx[0] = rq; a.xs[0] = bs; a.x[1] = d_o; a.rx[1] = rdo; a.xs[1] = ct;
+  a.y[0] = k; a.ry[0] = rk; a.ys[0] = bs; a.y[1] = v; a.ry[1] = rv; a.ys[1] = bs;
+  a.a[0] = d_o; a.ra[0] = rdo; a.as[0] = ct; a.a[1] = q; a.ra[1] = rq; a.as[1] = bs;
+  a.out[0] = dv; a.out[1] = dk; a.os[0] = a.os[1] = gs; a.beta[0] = beta_v; a.beta[1] = beta_k;
+  return launch_mh<MODE_DKV>(a, s);
+}
+
+}  // namespace stk_mh

@@ -27,9 +27,11 @@
 // D[i = 4 g + e][n = r].  A score tile of 32 streamed positions is two 16-row D tiles; lane (r, g) holds rows
 // {4 g + e, 16 + 4 g + e} of column r, and these 8 values ARE its B fragment of the next contraction (k order permuted
 // consistently: the A operand reads the same 4 + 4 positions from a PF row).  So p and ds never leave the registers.
+#include "attention_mh.h"
 #include "common.h"
 #include "split.h"
 #include "stk_attention_long.h"
+#include "stk_attention_mh.h"
 
 namespace {
 
@@ -80,7 +82,10 @@ __device__ __forceinline__ float rec_scale(const float* rec, int lane) {
 
 // ---- fp32 [B, C, T] (image stride bs) -> hi / lo fp16 planes, CF and / or PF layout -------------------------------------------
 // grid (Tp / 64, C / 32, B), 256 threads: a tile of 32 channels x 64 positions; positions T .. Tp - 1 become zeros.
-struct SplitArgs { const float* x; long bs; const float* rec; _Float16* cf; _Float16* pf; long pe; int C, T, Tp; };
+// Heads (include/stk_attention_mh.h): with D = C / heads < C the CF planes are written head-major, [plane][b][head][t][D],
+// which is what the attention kernels read as B heads "images" of D channels; the PF layout [b][C][Tp] already is
+// [b][head][D][Tp] (head n starts n D / 32 of these 32-channel blocks in).
+struct SplitArgs { const float* x; long bs; const float* rec; _Float16* cf; _Float16* pf; long pe; int C, T, Tp, D; };
 __global__ __launch_bounds__(256) void split_kernel(SplitArgs a) {
   __shared__ __attribute__((aligned(16))) _Float16 sh[2][64][32 + 8];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -110,7 +115,8 @@ __global__ __launch_bounds__(256) void split_kernel(SplitArgs a) {
   if (!a.cf) return;
   __syncthreads();
   const int tl = tid >> 2, part = tid & 3;
-  const long o = ((long)b * a.Tp + p0 + tl) * a.C + c0 + part * 8;
+  const int hd = c0 / a.D;                                         // a 32-channel block lies in one head (D % 32 == 0)
+  const long o = (((long)b * (a.C / a.D) + hd) * a.Tp + p0 + tl) * a.D + (c0 - hd * a.D) + part * 8;
 #pragma unroll
   for (int p = 0; p < 2; ++p)
     *reinterpret_cast<halfx8*>(a.cf + p * a.pe + o) = *reinterpret_cast<const halfx8*>(&sh[p][tl][part * 8]);
@@ -232,7 +238,8 @@ struct KArgs {
   const float* rec;                                               // scale records q, k, v, d_o
   float* lse; const float* delta;
   int B, C, T, Tp; float scale;
-};
+  int H;                                                          // heads: B counts (image, head) pairs and C is one head's
+};                                                                // width; pair b writes out at (b / H) os + (b % H) C T
 
 template <int C, int NW>
 __global__ __launch_bounds__(NW * 64) void fwd_kernel(KArgs a) {
@@ -296,7 +303,7 @@ __global__ __launch_bounds__(NW * 64) void fwd_kernel(KArgs a) {
   l += __shfl_xor(l, 32, 64);
   if (t < T) {
     const float inv = 1.f / (sv * P_SCALE * l);
-    float* ob = a.out[0] + (long)b * a.os + t;
+    float* ob = a.out[0] + (long)(b / a.H) * a.os + (long)(b % a.H) * C * T + t;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -363,7 +370,7 @@ __global__ __launch_bounds__(NW * 64) void dq_kernel(KArgs a) {
   }
   if (live) {
     const float f = sig == 0.f ? 0.f : a.scale / (sk * sig), beta = a.beta[0];
-    float* ob = a.out[0] + (long)b * a.os + t;
+    float* ob = a.out[0] + (long)(b / a.H) * a.os + (long)(b % a.H) * C * T + t;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -453,7 +460,7 @@ __global__ __launch_bounds__(NW * 64) void dkv_kernel(KArgs a) {
       float* base = a.out[which];
       if (!base) continue;
       const float beta = a.beta[which], f = which == 0 ? fk : fv;
-      float* ob = base + (long)b * a.os + t;
+      float* ob = base + (long)(b / a.H) * a.os + (long)(b % a.H) * C * T + t;
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -510,17 +517,18 @@ Planes planes_of(void* ws, int B, int C, int T) {
   p.pe = rb / 4;                                                   // halves per plane
   return p;
 }
-int split(const float* x, long bs, const float* rec, const Planes& pl, int cf, int pf, int B, int C, int T, hipStream_t s) {
+int split(const float* x, long bs, const float* rec, const Planes& pl, int cf, int pf, int B, int C, int T, hipStream_t s,
+          int heads = 1) {
   SplitArgs a;
-  a.x = x; a.bs = bs; a.rec = rec; a.pe = pl.pe; a.C = C; a.T = T; a.Tp = (int)tpad(T);
+  a.x = x; a.bs = bs; a.rec = rec; a.pe = pl.pe; a.C = C; a.T = T; a.Tp = (int)tpad(T); a.D = C / heads;
   a.cf = cf < 0 ? nullptr : const_cast<_Float16*>(pl.r[cf]);
   a.pf = pf < 0 ? nullptr : const_cast<_Float16*>(pl.r[pf]);
   hipLaunchKernelGGL(split_kernel, dim3(a.Tp / 64, C / 32, B), dim3(256), 0, s, a);
   STK_CHECK_LAUNCH();
   return STK_OK;
 }
-void base_args(KArgs& a, const Planes& pl, const float* rec, int B, int C, int T, float scale) {
-  a.pl = pl; a.rec = rec; a.B = B; a.C = C; a.T = T; a.Tp = (int)tpad(T); a.scale = scale;
+void base_args(KArgs& a, const Planes& pl, const float* rec, int B, int C, int T, float scale, int heads = 1) {
+  a.pl = pl; a.rec = rec; a.B = B * heads; a.C = C / heads; a.T = T; a.Tp = (int)tpad(T); a.scale = scale; a.H = heads;
 }
 
 }  // namespace
@@ -580,6 +588,109 @@ int stk_attention_long_bwd_f32(const float* q, const float* k, const float* v, l
   if ((rc = split(d_o, ct, rdo, pl, R_DCF, R_DPF, B, C, T, s))) return rc;
   KArgs a = {};
   base_args(a, pl, rec, B, C, T, scale);
+  a.lse = const_cast<float*>(lse); a.delta = delta; a.os = grad_bstride;
+  if (dq) {
+    a.out[0] = dq; a.beta[0] = beta_q;
+    if ((rc = launch<1>(a, s))) return rc;
+  }
+  if (dk || dv) {
+    a.out[0] = dk; a.beta[0] = beta_k; a.out[1] = dv; a.beta[1] = beta_v;
+    if ((rc = launch<2>(a, s))) return rc;
+  }
+  return STK_OK;
+}
+
+}  // extern "C"
+
+// ---- include/stk_attention_mh.h -------------------------------------------------------------------------------------------
+// The streaming form runs the kernels above unchanged on B heads pairs of D = C / heads channels: the planes are split from
+// the whole tensors (one scale per tensor), head-major where the layout is channel-fast, and only the address of an output
+// tile knows that a pair is a slice of an image.  delta's [B, heads, T] rows are those of [B heads, D, T] tensors.
+namespace {
+
+inline int mh_d(int C, int heads) { return heads > 0 && C > 0 && C % heads == 0 ? C / heads : 0; }
+inline bool mh_long_ok(int B, int C, int T, int heads) {
+  const int d = mh_d(C, heads);
+  return B > 0 && d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= TMAX && T % 4 == 0 && (long)B * C * T < 0x7fffffffL;
+}
+inline bool mh_short(int T) { return T <= 256; }
+
+}  // namespace
+
+extern "C" {
+
+int stk_attention_mh_ok(int B, int C, int T, int heads) {
+  return (mh_short(T) ? stk_mh::short_ok(B, C, T, heads) : mh_long_ok(B, C, T, heads)) ? 1 : 0;
+}
+
+long stk_attention_mh_ws_bytes(int B, int C, int T, int heads) {
+  if (B <= 0 || C <= 0 || T <= 0 || heads <= 0 || C % heads) return STK_EINVAL;
+  if (!stk_attention_mh_ok(B, C, T, heads)) return STK_EUNSUPPORTED;
+  return mh_short(T) ? 0 : ws_need(B, C, T);
+}
+
+int stk_attention_mh_fwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse,
+                             float* rec, int B, int C, int T, int heads, float scale, void* ws, long ws_bytes,
+                             void* stream) {
+  if (!q || !k || !v || !o || !lse || !rec || B <= 0 || C <= 0 || T <= 0 || heads <= 0 || C % heads) return STK_EINVAL;
+  if (!stk_attention_mh_ok(B, C, T, heads)) return STK_EUNSUPPORTED;
+  if (mh_short(T)) return stk_mh::short_fwd(q, k, v, qkv_bstride, o, lse, rec, B, C, T, heads, scale, stream);
+  if (!ws || ws_bytes < ws_need(B, C, T)) return STK_EINVAL;
+  if (heads == 1) return stk_attention_long_fwd_f32(q, k, v, qkv_bstride, o, lse, rec, B, C, T, scale, ws, ws_bytes, stream);
+  if (!stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(ws))
+    return STK_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  AmaxArgs m = {};
+  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
+  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  const Planes pl = planes_of(ws, B, C, T);
+  int rc;
+  if ((rc = split(q, qkv_bstride, rec, pl, R_QCF, -1, B, C, T, s, heads))) return rc;
+  if ((rc = split(k, qkv_bstride, rec + NPART, pl, R_KCF, -1, B, C, T, s, heads))) return rc;
+  if ((rc = split(v, qkv_bstride, rec + 2 * NPART, pl, -1, R_VPF, B, C, T, s, heads))) return rc;
+  KArgs a = {};
+  base_args(a, pl, rec, B, C, T, scale, heads);
+  a.out[0] = o; a.os = (long)C * T; a.lse = lse;
+  return launch<0>(a, s);
+}
+
+int stk_attention_mh_bwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, const float* o,
+                             const float* d_o, const float* lse, float* rec, float* delta, float* dq, float beta_q,
+                             float* dk, float beta_k, float* dv, float beta_v, long grad_bstride, int B, int C, int T,
+                             int heads, float scale, void* ws, long ws_bytes, void* stream) {
+  if (!q || !k || !v || !o || !d_o || !lse || !rec || !delta || B <= 0 || C <= 0 || T <= 0 || heads <= 0 || C % heads)
+    return STK_EINVAL;
+  if (!stk_attention_mh_ok(B, C, T, heads)) return STK_EUNSUPPORTED;
+  if (mh_short(T))
+    return stk_mh::short_bwd(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C,
+                             T, heads, scale, stream);
+  if (!ws || ws_bytes < ws_need(B, C, T)) return STK_EINVAL;
+  if (heads == 1)
+    return stk_attention_long_bwd_f32(q, k, v, qkv_bstride, o, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v,
+                                      grad_bstride, B, C, T, scale, ws, ws_bytes, stream);
+  if (!stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) || !stk_aligned16(k) ||
+      !stk_aligned16(v) || !stk_aligned16(d_o) || !stk_aligned16(lse) || !stk_aligned16(delta) || !stk_aligned16(ws))
+    return STK_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const long ct = (long)C * T, bs = qkv_bstride;
+  const int D = C / heads;
+  float* rdo = rec + 3 * NPART;
+  AmaxArgs m = {};
+  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  hipLaunchKernelGGL(delta_kernel, dim3((T + 255) / 256, B * heads), dim3(256), 0, s, o, d_o, delta, D, T);
+  STK_CHECK_LAUNCH();
+  const Planes pl = planes_of(ws, B, C, T);
+  int rc;
+  if ((rc = split(q, bs, rec, pl, R_QCF, R_QPF, B, C, T, s, heads))) return rc;
+  if ((rc = split(k, bs, rec + NPART, pl, R_KCF, R_KPF, B, C, T, s, heads))) return rc;
+  if ((rc = split(v, bs, rec + 2 * NPART, pl, R_VCF, -1, B, C, T, s, heads))) return rc;
+  if ((rc = split(d_o, ct, rdo, pl, R_DCF, R_DPF, B, C, T, s, heads))) return rc;
+  KArgs a = {};
+  base_args(a, pl, rec, B, C, T, scale, heads);
   a.lse = const_cast<float*>(lse); a.delta = delta; a.os = grad_bstride;
   if (dq) {
     a.out[0] = dq; a.beta[0] = beta_q;

@@ -990,9 +990,16 @@ class AttentionCore(Op):
     * otherwise, where the library has include/stk_attention_long.h and stk_attention_long_ok holds, the streaming
       kernels: lse / delta vectors and the fp16 planes of q, k, v, dO in the workspace, no [B,T,T] matrix either;
     * the rest as batched GEMMs around stk_softmax_* with the score and probability matrices in the arena.
-  STK_ATTN_FUSED=0 forces the GEMM form everywhere."""
+  STK_ATTN_FUSED=0 forces the GEMM form everywhere.
 
-  def __init__(self, g, q, k, v, name='attn', qkv=None):
+  `heads` = h > 1: h independent attentions over the contiguous channel slices of width d = C / h (head n of an operand
+  sits n d T floats into its image), score scale d^-0.5.  Planned, in this order, as
+    * the entries of include/stk_attention_mh.h where the library has them and stk_attention_mh_ok holds: one launch per
+      direction for all heads, short or streaming kernels by T, lse / delta of [B, h, T];
+    * the GEMM + softmax form with a host loop over the heads (pointer offsets n d T, batch B, s / p of [B, h, T, T]).
+  heads == 1 is the single-head op above, launch for launch."""
+
+  def __init__(self, g, q, k, v, name='attn', qkv=None, heads=1):
     self.qkv = qkv
     if qkv is not None:
       B, C3, H, W = qkv.shape
@@ -1005,16 +1012,28 @@ class AttentionCore(Op):
       self.inputs = (q, k, v)
     self.B, self.C, self.T = B, C, H * W
     self.bs = (3 if qkv is not None else 1) * C * self.T       # floats between consecutive images of q / k / v
-    self.scale = float(int(C) ** (-0.5))
+    self.heads = heads = int(heads)
+    if heads < 1 or C % heads:
+      raise ValueError(f'{name}: heads = {heads} does not divide C = {C}')
+    self.scale = float(int(C // heads) ** (-0.5))
     lib = g.lib
     allowed = lib is not None and os.environ.get('STK_ATTN_FUSED', '1') != '0'
-    self.fused = bool(allowed and int(lib.attention_ok(B, C, self.T)))
-    self.long = bool(allowed and not self.fused and getattr(lib, 'has_attention_long', False) and
+    self.mh = bool(heads > 1 and allowed and getattr(lib, 'has_attention_mh', False) and
+                   int(lib.attention_mh_ok(B, C, self.T, heads)))
+    self.fused = bool(heads == 1 and allowed and int(lib.attention_ok(B, C, self.T)))
+    self.long = bool(heads == 1 and allowed and not self.fused and getattr(lib, 'has_attention_long', False) and
                      int(lib.attention_long_ok(B, C, self.T)))
-    if self.fused or self.long:
+    if self.mh:
+      self.lse = g.new((B, heads, self.T), needs_grad=False, name=name + '.lse')
+      self.delta = g.new((B, heads, self.T), needs_grad=False, name=name + '.delta')
+      self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
+    elif self.fused or self.long:
       self.lse = g.new((B, self.T), needs_grad=False, name=name + '.lse')
       self.delta = g.new((B, self.T), needs_grad=False, name=name + '.delta')
       self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
+    elif heads > 1:
+      self.s = g.new((B, heads, self.T, self.T), needs_grad=False, name=name + '.s')
+      self.p = g.new((B, heads, self.T, self.T), needs_grad=False, name=name + '.p')
     else:
       self.s = g.new((B, self.T, self.T), needs_grad=False, name=name + '.s')
       self.p = g.new((B, self.T, self.T), needs_grad=False, name=name + '.p')
@@ -1038,6 +1057,12 @@ class AttentionCore(Op):
     B, C, T, bs = self.B, self.C, self.T, self.bs
     lib = rt.lib
     (q, k, v), _, _ = self._qkv(rt)
+    if self.mh:
+      rt.timed('attention_mh.fwd.x2', self.flops, lib.attention_mh_fwd_f32, q, k, v, bs, rt.v(self.o),
+               rt.v(self.lse), rt.v(self.rec), B, C, T, self.heads, self.scale, rt.ws, rt.ws_bytes, rt.stream)
+      return
+    if self.heads > 1:
+      return self._forward_heads(rt, q, k, v)
     if self.fused:
       rt.timed('attention.fwd.x2', self.flops, lib.attention_fwd_f32, q, k, v, bs, rt.v(self.o),
                rt.v(self.lse), rt.v(self.rec), B, C, T, self.scale, rt.stream)
@@ -1054,6 +1079,41 @@ class AttentionCore(Op):
     lib.gemm_f32(v, T, 1, bs, rt.v(self.p), 1, T, T * T, rt.v(self.o), T, 1, C * T,
                  None, 0, C, T, T, B, 1.0, 0.0, rt.stream)
 
+  def _forward_heads(self, rt, q, k, v):
+    """The GEMM + softmax form of `heads` > 1: the single-head launches once per head, on the head's channel slice."""
+    B, C, T, bs, h = self.B, self.C, self.T, self.bs, self.heads
+    d, lib = C // h, rt.lib
+    for n in range(h):
+      off, sp = 4 * n * d * T, 4 * n * T * T                   # bytes to head n of an operand / of s and p
+      lib.gemm_f32(q + off, 1, T, bs, k + off, T, 1, bs, rt.v(self.s) + sp, T, 1, h * T * T,
+                   None, 0, T, T, d, B, 1.0, 0.0, rt.stream)
+    lib.softmax_fwd_f32(rt.v(self.s), rt.v(self.p), B * h * T, T, self.scale, rt.stream)
+    for n in range(h):
+      off, sp = 4 * n * d * T, 4 * n * T * T
+      lib.gemm_f32(v + off, T, 1, bs, rt.v(self.p) + sp, 1, T, h * T * T, rt.v(self.o) + off, T, 1, C * T,
+                   None, 0, d, T, T, B, 1.0, 0.0, rt.stream)
+
+  def _backward_heads(self, rt, go, q, k, v, gq, gk, gv, bq, bk, bv, gs):
+    B, C, T, bs, h = self.B, self.C, self.T, self.bs, self.heads
+    d, lib = C // h, rt.lib
+    dp = rt.v(self.s)                                          # S is dead after the forward softmax: dP, then dS
+    for n in range(h):
+      off, sp = 4 * n * d * T, 4 * n * T * T
+      lib.gemm_f32(go + off, 1, T, C * T, v + off, T, 1, bs, dp + sp, T, 1, h * T * T,
+                   None, 0, T, T, d, B, 1.0, 0.0, rt.stream)
+      if gv is not None:
+        lib.gemm_f32(go + off, T, 1, C * T, rt.v(self.p) + sp, T, 1, h * T * T, gv + off, T, 1, gs,
+                     None, 0, d, T, T, B, 1.0, bv, rt.stream)
+    lib.softmax_bwd_f32(rt.v(self.p), dp, dp, B * h * T, T, self.scale, rt.stream)
+    for n in range(h):
+      off, sp = 4 * n * d * T, 4 * n * T * T
+      if gq is not None:
+        lib.gemm_f32(k + off, T, 1, bs, dp + sp, 1, T, h * T * T, gq + off, T, 1, gs,
+                     None, 0, d, T, T, B, 1.0, bq, rt.stream)
+      if gk is not None:
+        lib.gemm_f32(q + off, T, 1, bs, dp + sp, T, 1, h * T * T, gk + off, T, 1, gs,
+                     None, 0, d, T, T, B, 1.0, bk, rt.stream)
+
   def backward(self, rt):
     B, C, T, bs = self.B, self.C, self.T, self.bs
     lib = rt.lib
@@ -1061,6 +1121,15 @@ class AttentionCore(Op):
     (q, k, v), (gq, gk, gv), (bq, bk, bv) = self._qkv(rt)
     if gq is None and gk is None and gv is None:
       return
+    if self.mh:
+      # a gradient nobody asked for is passed as NULL: the kernels skip it
+      rt.timed('attention_mh.bwd.x2', 2.0 * self.flops, lib.attention_mh_bwd_f32, q, k, v, bs, rt.v(self.o), go,
+               rt.v(self.lse), rt.v(self.rec), rt.v(self.delta), gq, bq if gq is not None else 0.0,
+               gk, bk if gk is not None else 0.0, gv, bv if gv is not None else 0.0,
+               bs if self.qkv is not None else C * T, B, C, T, self.heads, self.scale, rt.ws, rt.ws_bytes, rt.stream)
+      return
+    if self.heads > 1:
+      return self._backward_heads(rt, go, q, k, v, gq, gk, gv, bq, bk, bv, bs if self.qkv is not None else C * T)
     if self.fused:
       # the kernels write all three gradients; one that nobody asked for goes to the workspace (separate tensors only)
       n4 = 4 * B * C * T
@@ -1097,6 +1166,8 @@ class AttentionCore(Op):
                    None, 0, C, T, T, B, 1.0, bk, rt.stream)
 
   def ws_bytes(self, lib):
+    if self.mh:
+      return int(lib.attention_mh_ws_bytes(self.B, self.C, self.T, self.heads))
     if self.long:
       return int(lib.attention_long_ws_bytes(self.B, self.C, self.T))
     return 3 * 4 * self.B * self.C * self.T if (self.fused and self.qkv is None) else 0

@@ -140,6 +140,15 @@ SIGNATURES_ATTN_LONG = {
   'stk_attention_long_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, F, P, L, S],
 }
 _NO_CHECK_ATTN_LONG = {'stk_attention_long_ws_bytes', 'stk_attention_long_ok'}   # its queries (tests/_launch_trace.py reads this)
+# include/stk_attention_mh.h: the attention core with several heads, short and streaming form behind one pair of entries
+# (AttentionCore plans the GEMM form with a host loop over the heads without it).
+SIGNATURES_ATTN_MH = {
+  'stk_attention_mh_ok': [I, I, I, I],
+  'stk_attention_mh_ws_bytes': [I, I, I, I],
+  'stk_attention_mh_fwd_f32': [P, P, P, L, P, P, P, I, I, I, I, F, P, L, S],
+  'stk_attention_mh_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, I, F, P, L, S],
+}
+_NO_CHECK_ATTN_MH = {'stk_attention_mh_ws_bytes', 'stk_attention_mh_ok'}         # its queries
 # include/stk_upconv.h: the FIR-upsampling convolution, Conv2d(up=True) (engine.graph.UpConv refuses to plan without it).
 SIGNATURES_UPCONV = {
   'stk_upconv2d_ws_bytes': [I, I, I, I, I, I, I, I],
@@ -198,6 +207,8 @@ OPTIONAL_HEADERS = (
   Header('has_blocks', 'include/stk_blocks.h', SIGNATURES_BLOCKS, {}, ()),
   Header('has_attention_long', 'include/stk_attention_long.h', SIGNATURES_ATTN_LONG, {'stk_attention_long_ws_bytes': c_long},
          _NO_CHECK_ATTN_LONG),
+  Header('has_attention_mh', 'include/stk_attention_mh.h', SIGNATURES_ATTN_MH, {'stk_attention_mh_ws_bytes': c_long},
+         _NO_CHECK_ATTN_MH),
   Header('has_upconv', 'include/stk_upconv.h', SIGNATURES_UPCONV, {'stk_upconv2d_ws_bytes': c_long}, ()),
   Header('has_impute', 'include/stk_impute.h', SIGNATURES_IMPUTE, {}, ()),
   Header('has_solver', 'include/stk_solver.h', SIGNATURES_SOLVER, {}, ()),

@@ -93,10 +93,17 @@ class Combine(EagerBlock, nn.Module):
 
 
 class AttnBlockpp(EagerBlock, nn.Module):
-  """Single-head self-attention over the H*W positions (models/layerspp.py:75-104)."""
+  """Self-attention over the H*W positions (models/layerspp.py:75-104).  The reference has one head of all `channels`;
+  `num_heads` = h > 1 (absent from the reference) runs h independent attentions over the contiguous slices of
+  channels / h output channels of NIN_0..2, score scale (channels / h)^-0.5, and concatenates their outputs in front of
+  NIN_3.  The parameters, their names and their initial values do not depend on h."""
 
-  def __init__(self, channels, skip_rescale=False, init_scale=0.):
+  def __init__(self, channels, skip_rescale=False, init_scale=0., num_heads=1):
     super().__init__()
+    num_heads = int(num_heads)
+    if num_heads < 1 or channels % num_heads:
+      raise ValueError(f'AttnBlockpp: num_heads = {num_heads} does not divide the C = {channels} channels of the block')
+    self.num_heads = num_heads
     self.GroupNorm_0 = nn.GroupNorm(num_groups=min(channels // 4, 32), num_channels=channels, eps=1e-6)
     self.NIN_0 = NIN(channels, channels)
     self.NIN_1 = NIN(channels, channels)
@@ -126,12 +133,12 @@ class AttnBlockpp(EagerBlock, nn.Module):
       b_all = Tensor((3 * C,), 'param', b0.off, True, name + '.bqkv')
       b_all.goff = b0.off
       qkv = g.conv1x1_t(h, w_all, b_all, 3 * C, name=name + '.qkv')
-      o = g.add(AttentionCore(g, None, None, None, name=name, qkv=qkv))
+      o = g.add(AttentionCore(g, None, None, None, name=name, qkv=qkv, heads=self.num_heads))
     else:
       q = self.NIN_0.emit(g, h, name=name + '.q')
       k = self.NIN_1.emit(g, h, name=name + '.k')
       v = self.NIN_2.emit(g, h, name=name + '.v')
-      o = g.add(AttentionCore(g, q, k, v, name=name))
+      o = g.add(AttentionCore(g, q, k, v, name=name, heads=self.num_heads))
     return self.NIN_3.emit(g, o, res=x, out_div=SQRT2 if self.skip_rescale else 1.0, name=name + '.out')
 
   def _emit_eager(self, g, x):

@@ -109,7 +109,27 @@ class NCSNpp(nn.Module):
     if fourier_feature:          # (models/ncsnpp.py:104-105: a parameter-free module, but it takes a slot of all_modules)
       modules.append(layerspp.FixedFouriereProjection())
 
-    AttnBlock = functools.partial(layerspp.AttnBlockpp, init_scale=init_scale, skip_rescale=skip_rescale)
+    # attention heads (absent from the reference): model.num_heads = h, the same in every attention block, or
+    # model.num_head_channels = d, h = C / d per block; neither: the single head of the reference
+    num_heads = utils.config_option(config, 'model', 'num_heads', None)
+    num_head_channels = utils.config_option(config, 'model', 'num_head_channels', None)
+    if num_heads is not None and num_head_channels is not None:
+      raise ValueError('config.model.num_heads and config.model.num_head_channels are both set: give one of them')
+    if (num_heads is not None and int(num_heads) < 1) or (num_head_channels is not None and int(num_head_channels) < 1):
+      raise ValueError(f'config.model.num_heads = {num_heads} / num_head_channels = {num_head_channels} must be positive')
+
+    def AttnBlock(channels):
+      if num_head_channels is not None:
+        if channels % int(num_head_channels):
+          raise ValueError(f'config.model.num_head_channels = {num_head_channels} does not divide the C = {channels} '
+                           f'channels of attention block all_modules.{len(modules)}')
+        h = channels // int(num_head_channels)
+      else:
+        h = 1 if num_heads is None else int(num_heads)
+        if channels % h:
+          raise ValueError(f'config.model.num_heads = {h} does not divide the C = {channels} channels of attention block '
+                           f'all_modules.{len(modules)}')
+      return layerspp.AttnBlockpp(channels=channels, init_scale=init_scale, skip_rescale=skip_rescale, num_heads=h)
     Upsample = functools.partial(layerspp.Upsample, with_conv=resamp_with_conv, fir=fir, fir_kernel=fir_kernel)
     if progressive == 'output_skip':
       self.pyramid_upsample = layerspp.Upsample(fir=fir, fir_kernel=fir_kernel, with_conv=False)
