@@ -662,8 +662,11 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
   }
 }
 
-inline bool attn_ok(int B, int C, int T) {
-  return B > 0 && C >= 32 && C <= 256 && C % 32 == 0 && T >= 4 && T <= 256 && T % 4 == 0 && (long)B * C * T * 4 < 0x7fffffffL;
+// heads of d = C / heads channels each; one head is the whole image (stk_attention_ok)
+inline bool attn_ok(int B, int C, int T, int heads = 1) {
+  if (B <= 0 || heads <= 0 || C <= 0 || C % heads) return false;
+  const int d = C / heads;
+  return d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= 256 && T % 4 == 0 && (long)B * C * T * 4 < 0x7fffffffL;
 }
 inline bool stride_ok(int B, int C, int T, long bs) {
   return bs >= (long)C * T && bs % 4 == 0 && ((long)(B - 1) * bs + (long)C * T) * 4 < 0x7fffffffL;
@@ -693,15 +696,74 @@ int launch_mh(const Args& a, hipStream_t s) {
   STK_CHECK_LAUNCH();
   return STK_OK;
 }
+// `mh`: the MH instantiations (any number of heads, NULL gradients) instead of the single-head ones
+template <int MODE>
+int launch_either(bool mh, const Args& a, hipStream_t s) { return mh ? launch_mh<MODE>(a, s) : launch<MODE>(a, s); }
+
+// |x| maxima of n [B, C, T] tensors of image stride bs into the records rec, rec + NPART, ...
+int amax(const float* const* x, int n, long bs, float* rec, int B, int C, int T, hipStream_t s) {
+  AmaxArgs m = {};
+  for (int i = 0; i < n; ++i) { m.x[i] = x[i]; m.rec[i] = rec + i * NPART; m.bs4[i] = bs / 4; }
+  m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, n), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
 
 void fwd_args(Args& a, const float* q, const float* k, const float* v, long bs, float* o, float* lse, float* rec, int B, int C,
-              int T, float scale) {
+              int T, int heads, float scale) {
   const long ct = (long)C * T;
   a.x[0] = k; a.rx[0] = rec + NPART; a.y[0] = q; a.ry[0] = rec; a.a[0] = v; a.ra[0] = rec + 2 * NPART;
   a.x[1] = k; a.rx[1] = rec + NPART; a.y[1] = q; a.ry[1] = rec; a.a[1] = v; a.ra[1] = rec + 2 * NPART;
   a.xs[0] = a.xs[1] = a.ys[0] = a.ys[1] = a.as[0] = a.as[1] = bs;
   a.out[0] = o; a.out[1] = o; a.os[0] = a.os[1] = ct; a.beta[0] = a.beta[1] = 0.f; a.lse = lse; a.delta = nullptr;
-  a.B = B; a.C = C; a.T = T; a.scale = scale;
+  a.B = B; a.C = C / heads; a.H = heads; a.T = T; a.scale = scale;
+}
+
+// The one body of each direction, behind the checks of the entries below and of stk_mh.
+int short_fwd_impl(const float* q, const float* k, const float* v, long bs, float* o, float* lse, float* rec, int B, int C,
+                   int T, int heads, bool mh, float scale, hipStream_t s) {
+  const float* qkv[3] = {q, k, v};
+  int rc = amax(qkv, 3, bs, rec, B, C, T, s);
+  if (rc) return rc;
+  Args a = {};
+  fwd_args(a, q, k, v, bs, o, lse, rec, B, C, T, heads, scale);
+  return launch_either<MODE_FWD>(mh, a, s);
+}
+
+// A NULL gradient (mh only) is not computed.
+int short_bwd_impl(const float* q, const float* k, const float* v, long bs, const float* d_o, const float* lse, float* rec,
+                   float* delta, float* dq, float beta_q, float* dk, float beta_k, float* dv, float beta_v, long gs, int B,
+                   int C, int T, int heads, bool mh, float scale, hipStream_t s) {
+  const long ct = (long)C * T;
+  float* rq = rec; float* rk = rec + NPART; float* rv = rec + 2 * NPART; float* rdo = rec + 3 * NPART;
+  int rc = amax(&d_o, 1, ct, rdo, B, C, T, s);
+  if (rc) return rc;
+  Args a = {};
+  a.B = B; a.C = C / heads; a.H = heads; a.T = T; a.scale = scale; a.lse = const_cast<float*>(lse); a.delta = delta;
+  // DQ: rows m = keys: X = (k, v); columns n = queries: Y = (q, do); phase B: dq = k ds.  The kernel also writes delta, so it
+  // runs even when only dk / dv are wanted (and then skips its phase B)
+  a.x[0] = k; a.rx[0] = rk; a.xs[0] = bs; a.x[1] = v; a.rx[1] = rv; a.xs[1] = bs;
+  a.y[0] = q; a.ry[0] = rq; a.ys[0] = bs; a.y[1] = d_o; a.ry[1] = rdo; a.ys[1] = ct;
+  a.a[0] = k; a.ra[0] = rk; a.as[0] = bs; a.a[1] = k; a.ra[1] = rk; a.as[1] = bs;
+  a.out[0] = dq; a.out[1] = dq; a.os[0] = a.os[1] = gs; a.beta[0] = a.beta[1] = beta_q;
+  rc = launch_either<MODE_DQ>(mh, a, s);
+  if (rc || (!dk && !dv)) return rc;
+  // DKV: rows m = queries: X = (q, do); columns n = keys: Y = (k, v); phase B: dv = do p, dk = q ds
+  a.x[0] = q; a.rx[0] = rq; a.xs[0] = bs; a.x[1] = d_o; a.rx[1] = rdo; a.xs[1] = ct;
+  a.y[0] = k; a.ry[0] = rk; a.ys[0] = bs; a.y[1] = v; a.ry[1] = rv; a.ys[1] = bs;
+  a.a[0] = d_o; a.ra[0] = rdo; a.as[0] = ct; a.a[1] = q; a.ra[1] = rq; a.as[1] = bs;
+  a.out[0] = dv; a.out[1] = dk; a.os[0] = a.os[1] = gs; a.beta[0] = beta_v; a.beta[1] = beta_k;
+  return launch_either<MODE_DKV>(mh, a, s);
+}
+
+// what the entries refuse as unsupported once their pointers and sizes are valid
+inline bool fwd_operands_ok(const float* q, const float* k, const float* v, long bs, int B, int C, int T, int heads) {
+  return attn_ok(B, C, T, heads) && stride_ok(B, C, T, bs) && stk_aligned16(q) && stk_aligned16(k) && stk_aligned16(v);
+}
+inline bool bwd_operands_ok(const float* q, const float* k, const float* v, long bs, const float* d_o, long gs, int B, int C,
+                            int T, int heads) {
+  return fwd_operands_ok(q, k, v, bs, B, C, T, heads) && stride_ok(B, C, T, gs) && stk_aligned16(d_o);
 }
 
 }  // namespace
@@ -713,24 +775,15 @@ int stk_attention_ok(int B, int C, int T) { return attn_ok(B, C, T) ? 1 : 0; }
 int stk_attention_fwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse, float* rec,
                           int B, int C, int T, float scale, void* stream) {
   if (!q || !k || !v || !o || !lse || !rec || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
-  if (!attn_ok(B, C, T) || !stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  AmaxArgs m = {};
-  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
-  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  Args a = {};
-  fwd_args(a, q, k, v, qkv_bstride, o, lse, rec, B, C, T, scale);
-  return launch<MODE_FWD>(a, s);
+  if (!fwd_operands_ok(q, k, v, qkv_bstride, B, C, T, 1)) return STK_EUNSUPPORTED;
+  return short_fwd_impl(q, k, v, qkv_bstride, o, lse, rec, B, C, T, 1, false, scale, (hipStream_t)stream);
 }
 
 /* development aid (not in include/stk.h): the forward kernel alone with cycle stamps of workgroup 0 in dbg[0..8) */
 int stk_attention_fwd_debug(const float* q, const float* k, const float* v, float* o, float* lse, float* rec, int B, int C,
                             int T, float scale, long long* dbg, void* stream) {
   Args a = {};
-  fwd_args(a, q, k, v, (long)C * T, o, lse, rec, B, C, T, scale);
+  fwd_args(a, q, k, v, (long)C * T, o, lse, rec, B, C, T, 1, scale);
   a.dbg = dbg;
   return launch<MODE_FWD>(a, (hipStream_t)stream);
 }
@@ -739,96 +792,33 @@ int stk_attention_bwd_f32(const float* q, const float* k, const float* v, long q
                           float* rec, float* delta, float* dq, float beta_q, float* dk, float beta_k, float* dv, float beta_v,
                           long grad_bstride, int B, int C, int T, float scale, void* stream) {
   if (!q || !k || !v || !d_o || !lse || !rec || !delta || !dq || !dk || !dv || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
-  if (!attn_ok(B, C, T) || !stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) ||
-      !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(d_o))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const long ct = (long)C * T;
-  float* rq = rec; float* rk = rec + NPART; float* rv = rec + 2 * NPART; float* rdo = rec + 3 * NPART;
-  AmaxArgs m = {};
-  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  Args a = {};
-  a.B = B; a.C = C; a.T = T; a.scale = scale; a.lse = const_cast<float*>(lse); a.delta = delta;
-  const long bs = qkv_bstride, gs = grad_bstride;
-  // DQ: rows m = keys: X = (k, v); columns n = queries: Y = (q, do); phase B: dq = k ds
-  a.x[0] = k; a.rx[0] = rk; a.xs[0] = bs; a.x[1] = v; a.rx[1] = rv; a.xs[1] = bs;
-  a.y[0] = q; a.ry[0] = rq; a.ys[0] = bs; a.y[1] = d_o; a.ry[1] = rdo; a.ys[1] = ct;
-  a.a[0] = k; a.ra[0] = rk; a.as[0] = bs; a.a[1] = k; a.ra[1] = rk; a.as[1] = bs;
-  a.out[0] = dq; a.out[1] = dq; a.os[0] = a.os[1] = gs; a.beta[0] = a.beta[1] = beta_q;
-  int rc = launch<MODE_DQ>(a, s);
-  if (rc) return rc;
-  // DKV: rows m = queries: X = (q, do); columns n = keys: Y = (k, v); phase B: dv = do p, dk = q ds
-  a.x[0] = q; a.rx[0] = rq; a.xs[0] = bs; a.x[1] = d_o; a.rx[1] = rdo; a.xs[1] = ct;
-  a.y[0] = k; a.ry[0] = rk; a.ys[0] = bs; a.y[1] = v; a.ry[1] = rv; a.ys[1] = bs;
-  a.a[0] = d_o; a.ra[0] = rdo; a.as[0] = ct; a.a[1] = q; a.ra[1] = rq; a.as[1] = bs;
-  a.out[0] = dv; a.out[1] = dk; a.os[0] = a.os[1] = gs; a.beta[0] = beta_v; a.beta[1] = beta_k;
-  return launch<MODE_DKV>(a, s);
+  if (!bwd_operands_ok(q, k, v, qkv_bstride, d_o, grad_bstride, B, C, T, 1)) return STK_EUNSUPPORTED;
+  return short_bwd_impl(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C, T, 1,
+                        false, scale, (hipStream_t)stream);
 }
 
 }  // extern "C"
 
 // ---- the short form of include/stk_attention_mh.h (its entries are in attention_long.hip, which picks the form) ----------
+// One head with every gradient wanted is the single-head entry, kernel instantiations included.
 
 namespace stk_mh {
 
-bool short_ok(int B, int C, int T, int heads) {
-  if (B <= 0 || heads <= 0 || C <= 0 || C % heads) return false;
-  const int d = C / heads;
-  return d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= 256 && T % 4 == 0 && (long)B * C * T * 4 < 0x7fffffffL;
-}
+bool short_ok(int B, int C, int T, int heads) { return attn_ok(B, C, T, heads); }
 
 int short_fwd(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse, float* rec, int B, int C,
               int T, int heads, float scale, void* stream) {
-  if (heads == 1) return stk_attention_fwd_f32(q, k, v, qkv_bstride, o, lse, rec, B, C, T, scale, stream);
-  if (!short_ok(B, C, T, heads) || !stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  AmaxArgs m = {};
-  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
-  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  Args a = {};
-  fwd_args(a, q, k, v, qkv_bstride, o, lse, rec, B, C / heads, T, scale);
-  a.os[0] = a.os[1] = (long)C * T; a.H = heads;
-  return launch_mh<MODE_FWD>(a, s);
+  if (!fwd_operands_ok(q, k, v, qkv_bstride, B, C, T, heads)) return STK_EUNSUPPORTED;
+  return short_fwd_impl(q, k, v, qkv_bstride, o, lse, rec, B, C, T, heads, heads > 1, scale, (hipStream_t)stream);
 }
 
 int short_bwd(const float* q, const float* k, const float* v, long qkv_bstride, const float* d_o, const float* lse, float* rec,
               float* delta, float* dq, float beta_q, float* dk, float beta_k, float* dv, float beta_v, long grad_bstride, int B,
               int C, int T, int heads, float scale, void* stream) {
-  if (heads == 1 && dq && dk && dv)
-    return stk_attention_bwd_f32(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B,
-                                 C, T, scale, stream);
-  if (!short_ok(B, C, T, heads) || !stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) ||
-      !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(d_o))
-    return STK_EUNSUPPORTED;
+  if (!bwd_operands_ok(q, k, v, qkv_bstride, d_o, grad_bstride, B, C, T, heads)) return STK_EUNSUPPORTED;
   if (!dq && !dk && !dv) return STK_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const long ct = (long)C * T;
-  float* rq = rec; float* rk = rec + NPART; float* rv = rec + 2 * NPART; float* rdo = rec + 3 * NPART;
-  AmaxArgs m = {};
-  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(attn_amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  Args a = {};
-  a.B = B; a.C = C / heads; a.H = heads; a.T = T; a.scale = scale; a.lse = const_cast<float*>(lse); a.delta = delta;
-  const long bs = qkv_bstride, gs = grad_bstride;
-  // as stk_attention_bwd_f32; the DQ kernel also writes delta, so it runs even when only dk / dv are wanted (and then
-  // skips its phase B)
-  a.x[0] = k; a.rx[0] = rk; a.xs[0] = bs; a.x[1] = v; a.rx[1] = rv; a.xs[1] = bs;
-  a.y[0] = q; a.ry[0] = rq; a.ys[0] = bs; a.y[1] = d_o; a.ry[1] = rdo; a.ys[1] = ct;
-  a.a[0] = k; a.ra[0] = rk; a.as[0] = bs; a.a[1] = k; a.ra[1] = rk; a.as[1] = bs;
-  a.out[0] = dq; a.out[1] = dq; a.os[0] = a.os[1] = gs; a.beta[0] = a.beta[1] = beta_q;
-  int rc = launch_mh<MODE_DQ>(a, s);
-  if (rc || (!dk && !dv)) return rc;
-  a.x[0] = q; a.rx[0] = rq; a.xs[0] = bs; a.x[1] = d_o; a.rx[1] = rdo; a.xs[1] = ct;
-  a.y[0] = k; a.ry[0] = rk; a.ys[0] = bs; a.y[1] = v; a.ry[1] = rv; a.ys[1] = bs;
-  a.a[0] = d_o; a.ra[0] = rdo; a.as[0] = ct; a.a[1] = q; a.ra[1] = rq; a.as[1] = bs;
-  a.out[0] = dv; a.out[1] = dk; a.os[0] = a.os[1] = gs; a.beta[0] = beta_v; a.beta[1] = beta_k;
-  return launch_mh<MODE_DKV>(a, s);
+  return short_bwd_impl(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C, T,
+                        heads, heads > 1 || !dq || !dk || !dv, scale, (hipStream_t)stream);
 }
 
 }  // namespace stk_mh

@@ -502,13 +502,25 @@ int launch(const KArgs& a, hipStream_t s) {
   return STK_OK;
 }
 
-inline bool long_ok(int B, int C, int T) {
-  return B > 0 && C >= 32 && C <= 256 && C % 32 == 0 && T >= 4 && T <= TMAX && T % 4 == 0 && (long)B * C * T < 0x7fffffffL;
+// D = C / heads channels of one head (0: heads does not divide C); one head is the whole image
+inline int mh_d(int C, int heads) { return heads > 0 && C > 0 && C % heads == 0 ? C / heads : 0; }
+inline bool long_ok(int B, int C, int T, int heads = 1) {
+  const int d = mh_d(C, heads);
+  return B > 0 && d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= TMAX && T % 4 == 0 && (long)B * C * T < 0x7fffffffL;
 }
 inline bool stride_ok(int B, int C, int T, long bs) {
   return bs >= (long)C * T && bs % 4 == 0 && (long)(B - 1) * bs + (long)C * T < 0x7fffffffL;
 }
 inline long ws_need(int B, int C, int T) { return R_COUNT * region_bytes(B, C, T); }
+// what the entries refuse as unsupported once their pointers and sizes are valid (ws_bytes: the entry's own check)
+inline bool fwd_operands_ok(const float* q, const float* k, const float* v, long bs, const void* ws, int B, int C, int T) {
+  return stride_ok(B, C, T, bs) && stk_aligned16(q) && stk_aligned16(k) && stk_aligned16(v) && stk_aligned16(ws);
+}
+inline bool bwd_operands_ok(const float* q, const float* k, const float* v, long bs, const float* d_o, const float* lse,
+                            const float* delta, long gs, const void* ws, int B, int C, int T) {
+  return fwd_operands_ok(q, k, v, bs, ws, B, C, T) && stride_ok(B, C, T, gs) && stk_aligned16(d_o) && stk_aligned16(lse) &&
+         stk_aligned16(delta);
+}
 
 Planes planes_of(void* ws, int B, int C, int T) {
   Planes p;
@@ -517,8 +529,17 @@ Planes planes_of(void* ws, int B, int C, int T) {
   p.pe = rb / 4;                                                   // halves per plane
   return p;
 }
-int split(const float* x, long bs, const float* rec, const Planes& pl, int cf, int pf, int B, int C, int T, hipStream_t s,
-          int heads = 1) {
+// |x| maxima of n [B, C, T] tensors of image stride bs into the records rec, rec + NPART, ...
+int amax(const float* const* x, int n, long bs, float* rec, int B, int C, int T, hipStream_t s) {
+  AmaxArgs m = {};
+  for (int i = 0; i < n; ++i) { m.x[i] = x[i]; m.rec[i] = rec + i * NPART; m.bs4[i] = bs / 4; }
+  m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
+  hipLaunchKernelGGL(amax_kernel, dim3(NPART, n), dim3(1024), 0, s, m);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+int split(const float* x, long bs, const float* rec, const Planes& pl, int cf, int pf, int B, int C, int T, int heads,
+          hipStream_t s) {
   SplitArgs a;
   a.x = x; a.bs = bs; a.rec = rec; a.pe = pl.pe; a.C = C; a.T = T; a.Tp = (int)tpad(T); a.D = C / heads;
   a.cf = cf < 0 ? nullptr : const_cast<_Float16*>(pl.r[cf]);
@@ -527,68 +548,46 @@ int split(const float* x, long bs, const float* rec, const Planes& pl, int cf, i
   STK_CHECK_LAUNCH();
   return STK_OK;
 }
-void base_args(KArgs& a, const Planes& pl, const float* rec, int B, int C, int T, float scale, int heads = 1) {
+void base_args(KArgs& a, const Planes& pl, const float* rec, int B, int C, int T, float scale, int heads) {
   a.pl = pl; a.rec = rec; a.B = B * heads; a.C = C / heads; a.T = T; a.Tp = (int)tpad(T); a.scale = scale; a.H = heads;
 }
 
-}  // namespace
-
-extern "C" {
-
-int stk_attention_long_ok(int B, int C, int T) { return long_ok(B, C, T) ? 1 : 0; }
-
-long stk_attention_long_ws_bytes(int B, int C, int T) { return long_ok(B, C, T) ? ws_need(B, C, T) : STK_EUNSUPPORTED; }
-
-int stk_attention_long_fwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse,
-                               float* rec, int B, int C, int T, float scale, void* ws, long ws_bytes, void* stream) {
-  if (!q || !k || !v || !o || !lse || !rec || !ws || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
-  if (!long_ok(B, C, T) || !stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v) ||
-      !stk_aligned16(ws) || ws_bytes < ws_need(B, C, T))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  AmaxArgs m = {};
-  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
-  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  const Planes pl = planes_of(ws, B, C, T);
+// The one streaming body of each direction, behind the checks of the entries below.  With heads > 1 the kernels above run
+// unchanged on B heads pairs of D = C / heads channels: the planes are split from the whole tensors (one scale per tensor),
+// head-major where the layout is channel-fast, and only the address of an output tile knows that a pair is a slice of an
+// image.  delta's [B, heads, T] rows are those of [B heads, D, T] tensors.
+int long_fwd(const float* q, const float* k, const float* v, long bs, float* o, float* lse, float* rec, int B, int C, int T,
+             int heads, float scale, void* ws, hipStream_t s) {
+  const float* qkv[3] = {q, k, v};
   int rc;
-  if ((rc = split(q, qkv_bstride, rec, pl, R_QCF, -1, B, C, T, s))) return rc;
-  if ((rc = split(k, qkv_bstride, rec + NPART, pl, R_KCF, -1, B, C, T, s))) return rc;
-  if ((rc = split(v, qkv_bstride, rec + 2 * NPART, pl, -1, R_VPF, B, C, T, s))) return rc;
+  if ((rc = amax(qkv, 3, bs, rec, B, C, T, s))) return rc;
+  const Planes pl = planes_of(ws, B, C, T);
+  if ((rc = split(q, bs, rec, pl, R_QCF, -1, B, C, T, heads, s))) return rc;
+  if ((rc = split(k, bs, rec + NPART, pl, R_KCF, -1, B, C, T, heads, s))) return rc;
+  if ((rc = split(v, bs, rec + 2 * NPART, pl, -1, R_VPF, B, C, T, heads, s))) return rc;
   KArgs a = {};
-  base_args(a, pl, rec, B, C, T, scale);
+  base_args(a, pl, rec, B, C, T, scale, heads);
   a.out[0] = o; a.os = (long)C * T; a.lse = lse;
   return launch<0>(a, s);
 }
 
-int stk_attention_long_bwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, const float* o,
-                               const float* d_o, const float* lse, float* rec, float* delta, float* dq, float beta_q,
-                               float* dk, float beta_k, float* dv, float beta_v, long grad_bstride, int B, int C, int T,
-                               float scale, void* ws, long ws_bytes, void* stream) {
-  if (!q || !k || !v || !o || !d_o || !lse || !rec || !delta || !ws || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
-  if (!long_ok(B, C, T) || !stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) ||
-      !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(d_o) || !stk_aligned16(lse) || !stk_aligned16(delta) ||
-      !stk_aligned16(ws) || ws_bytes < ws_need(B, C, T))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const long ct = (long)C * T, bs = qkv_bstride;
+int long_bwd(const float* q, const float* k, const float* v, long bs, const float* o, const float* d_o, const float* lse,
+             float* rec, float* delta, float* dq, float beta_q, float* dk, float beta_k, float* dv, float beta_v, long gs,
+             int B, int C, int T, int heads, float scale, void* ws, hipStream_t s) {
+  const long ct = (long)C * T;
   float* rdo = rec + 3 * NPART;
-  AmaxArgs m = {};
-  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(delta_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, o, d_o, delta, C, T);
+  int rc;
+  if ((rc = amax(&d_o, 1, ct, rdo, B, C, T, s))) return rc;
+  hipLaunchKernelGGL(delta_kernel, dim3((T + 255) / 256, B * heads), dim3(256), 0, s, o, d_o, delta, C / heads, T);
   STK_CHECK_LAUNCH();
   const Planes pl = planes_of(ws, B, C, T);
-  int rc;
-  if ((rc = split(q, bs, rec, pl, R_QCF, R_QPF, B, C, T, s))) return rc;
-  if ((rc = split(k, bs, rec + NPART, pl, R_KCF, R_KPF, B, C, T, s))) return rc;
-  if ((rc = split(v, bs, rec + 2 * NPART, pl, R_VCF, -1, B, C, T, s))) return rc;
-  if ((rc = split(d_o, ct, rdo, pl, R_DCF, R_DPF, B, C, T, s))) return rc;
+  if ((rc = split(q, bs, rec, pl, R_QCF, R_QPF, B, C, T, heads, s))) return rc;
+  if ((rc = split(k, bs, rec + NPART, pl, R_KCF, R_KPF, B, C, T, heads, s))) return rc;
+  if ((rc = split(v, bs, rec + 2 * NPART, pl, R_VCF, -1, B, C, T, heads, s))) return rc;
+  if ((rc = split(d_o, ct, rdo, pl, R_DCF, R_DPF, B, C, T, heads, s))) return rc;
   KArgs a = {};
-  base_args(a, pl, rec, B, C, T, scale);
-  a.lse = const_cast<float*>(lse); a.delta = delta; a.os = grad_bstride;
+  base_args(a, pl, rec, B, C, T, scale, heads);
+  a.lse = const_cast<float*>(lse); a.delta = delta; a.os = gs;
   if (dq) {
     a.out[0] = dq; a.beta[0] = beta_q;
     if ((rc = launch<1>(a, s))) return rc;
@@ -600,27 +599,40 @@ int stk_attention_long_bwd_f32(const float* q, const float* k, const float* v, l
   return STK_OK;
 }
 
-}  // extern "C"
-
-// ---- include/stk_attention_mh.h -------------------------------------------------------------------------------------------
-// The streaming form runs the kernels above unchanged on B heads pairs of D = C / heads channels: the planes are split from
-// the whole tensors (one scale per tensor), head-major where the layout is channel-fast, and only the address of an output
-// tile knows that a pair is a slice of an image.  delta's [B, heads, T] rows are those of [B heads, D, T] tensors.
-namespace {
-
-inline int mh_d(int C, int heads) { return heads > 0 && C > 0 && C % heads == 0 ? C / heads : 0; }
-inline bool mh_long_ok(int B, int C, int T, int heads) {
-  const int d = mh_d(C, heads);
-  return B > 0 && d >= 32 && d <= 256 && d % 32 == 0 && T >= 4 && T <= TMAX && T % 4 == 0 && (long)B * C * T < 0x7fffffffL;
-}
-inline bool mh_short(int T) { return T <= 256; }
+inline bool mh_short(int T) { return T <= 256; }   // include/stk_attention_mh.h: the short form (attention.hip) up to here
 
 }  // namespace
 
 extern "C" {
 
+// ---- include/stk_attention_long.h -------------------------------------------------------------------------------------------
+int stk_attention_long_ok(int B, int C, int T) { return long_ok(B, C, T) ? 1 : 0; }
+
+long stk_attention_long_ws_bytes(int B, int C, int T) { return long_ok(B, C, T) ? ws_need(B, C, T) : STK_EUNSUPPORTED; }
+
+int stk_attention_long_fwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, float* o, float* lse,
+                               float* rec, int B, int C, int T, float scale, void* ws, long ws_bytes, void* stream) {
+  if (!q || !k || !v || !o || !lse || !rec || !ws || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
+  if (!long_ok(B, C, T) || !fwd_operands_ok(q, k, v, qkv_bstride, ws, B, C, T) || ws_bytes < ws_need(B, C, T))
+    return STK_EUNSUPPORTED;
+  return long_fwd(q, k, v, qkv_bstride, o, lse, rec, B, C, T, 1, scale, ws, (hipStream_t)stream);
+}
+
+int stk_attention_long_bwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, const float* o,
+                               const float* d_o, const float* lse, float* rec, float* delta, float* dq, float beta_q,
+                               float* dk, float beta_k, float* dv, float beta_v, long grad_bstride, int B, int C, int T,
+                               float scale, void* ws, long ws_bytes, void* stream) {
+  if (!q || !k || !v || !o || !d_o || !lse || !rec || !delta || !ws || B <= 0 || C <= 0 || T <= 0) return STK_EINVAL;
+  if (!long_ok(B, C, T) || !bwd_operands_ok(q, k, v, qkv_bstride, d_o, lse, delta, grad_bstride, ws, B, C, T) ||
+      ws_bytes < ws_need(B, C, T))
+    return STK_EUNSUPPORTED;
+  return long_bwd(q, k, v, qkv_bstride, o, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C, T, 1,
+                  scale, ws, (hipStream_t)stream);
+}
+
+// ---- include/stk_attention_mh.h: the short form (attention.hip, through attention_mh.h) or the streaming one, by T ------------
 int stk_attention_mh_ok(int B, int C, int T, int heads) {
-  return (mh_short(T) ? stk_mh::short_ok(B, C, T, heads) : mh_long_ok(B, C, T, heads)) ? 1 : 0;
+  return (mh_short(T) ? stk_mh::short_ok(B, C, T, heads) : long_ok(B, C, T, heads)) ? 1 : 0;
 }
 
 long stk_attention_mh_ws_bytes(int B, int C, int T, int heads) {
@@ -636,24 +648,8 @@ int stk_attention_mh_fwd_f32(const float* q, const float* k, const float* v, lon
   if (!stk_attention_mh_ok(B, C, T, heads)) return STK_EUNSUPPORTED;
   if (mh_short(T)) return stk_mh::short_fwd(q, k, v, qkv_bstride, o, lse, rec, B, C, T, heads, scale, stream);
   if (!ws || ws_bytes < ws_need(B, C, T)) return STK_EINVAL;
-  if (heads == 1) return stk_attention_long_fwd_f32(q, k, v, qkv_bstride, o, lse, rec, B, C, T, scale, ws, ws_bytes, stream);
-  if (!stride_ok(B, C, T, qkv_bstride) || !stk_aligned16(q) || !stk_aligned16(k) || !stk_aligned16(v) || !stk_aligned16(ws))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  AmaxArgs m = {};
-  m.x[0] = q; m.x[1] = k; m.x[2] = v; m.rec[0] = rec; m.rec[1] = rec + NPART; m.rec[2] = rec + 2 * NPART;
-  m.bs4[0] = m.bs4[1] = m.bs4[2] = qkv_bstride / 4; m.ct4 = (long)C * T / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 3), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  const Planes pl = planes_of(ws, B, C, T);
-  int rc;
-  if ((rc = split(q, qkv_bstride, rec, pl, R_QCF, -1, B, C, T, s, heads))) return rc;
-  if ((rc = split(k, qkv_bstride, rec + NPART, pl, R_KCF, -1, B, C, T, s, heads))) return rc;
-  if ((rc = split(v, qkv_bstride, rec + 2 * NPART, pl, -1, R_VPF, B, C, T, s, heads))) return rc;
-  KArgs a = {};
-  base_args(a, pl, rec, B, C, T, scale, heads);
-  a.out[0] = o; a.os = (long)C * T; a.lse = lse;
-  return launch<0>(a, s);
+  if (!fwd_operands_ok(q, k, v, qkv_bstride, ws, B, C, T)) return STK_EUNSUPPORTED;
+  return long_fwd(q, k, v, qkv_bstride, o, lse, rec, B, C, T, heads, scale, ws, (hipStream_t)stream);
 }
 
 int stk_attention_mh_bwd_f32(const float* q, const float* k, const float* v, long qkv_bstride, const float* o,
@@ -667,40 +663,9 @@ int stk_attention_mh_bwd_f32(const float* q, const float* k, const float* v, lon
     return stk_mh::short_bwd(q, k, v, qkv_bstride, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C,
                              T, heads, scale, stream);
   if (!ws || ws_bytes < ws_need(B, C, T)) return STK_EINVAL;
-  if (heads == 1)
-    return stk_attention_long_bwd_f32(q, k, v, qkv_bstride, o, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v,
-                                      grad_bstride, B, C, T, scale, ws, ws_bytes, stream);
-  if (!stride_ok(B, C, T, qkv_bstride) || !stride_ok(B, C, T, grad_bstride) || !stk_aligned16(q) || !stk_aligned16(k) ||
-      !stk_aligned16(v) || !stk_aligned16(d_o) || !stk_aligned16(lse) || !stk_aligned16(delta) || !stk_aligned16(ws))
-    return STK_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const long ct = (long)C * T, bs = qkv_bstride;
-  const int D = C / heads;
-  float* rdo = rec + 3 * NPART;
-  AmaxArgs m = {};
-  m.x[0] = d_o; m.rec[0] = rdo; m.bs4[0] = ct / 4; m.ct4 = ct / 4; m.n4 = (long)B * m.ct4;
-  hipLaunchKernelGGL(amax_kernel, dim3(NPART, 1), dim3(1024), 0, s, m);
-  STK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(delta_kernel, dim3((T + 255) / 256, B * heads), dim3(256), 0, s, o, d_o, delta, D, T);
-  STK_CHECK_LAUNCH();
-  const Planes pl = planes_of(ws, B, C, T);
-  int rc;
-  if ((rc = split(q, bs, rec, pl, R_QCF, R_QPF, B, C, T, s, heads))) return rc;
-  if ((rc = split(k, bs, rec + NPART, pl, R_KCF, R_KPF, B, C, T, s, heads))) return rc;
-  if ((rc = split(v, bs, rec + 2 * NPART, pl, R_VCF, -1, B, C, T, s, heads))) return rc;
-  if ((rc = split(d_o, ct, rdo, pl, R_DCF, R_DPF, B, C, T, s, heads))) return rc;
-  KArgs a = {};
-  base_args(a, pl, rec, B, C, T, scale, heads);
-  a.lse = const_cast<float*>(lse); a.delta = delta; a.os = grad_bstride;
-  if (dq) {
-    a.out[0] = dq; a.beta[0] = beta_q;
-    if ((rc = launch<1>(a, s))) return rc;
-  }
-  if (dk || dv) {
-    a.out[0] = dk; a.beta[0] = beta_k; a.out[1] = dv; a.beta[1] = beta_v;
-    if ((rc = launch<2>(a, s))) return rc;
-  }
-  return STK_OK;
+  if (!bwd_operands_ok(q, k, v, qkv_bstride, d_o, lse, delta, grad_bstride, ws, B, C, T)) return STK_EUNSUPPORTED;
+  return long_bwd(q, k, v, qkv_bstride, o, d_o, lse, rec, delta, dq, beta_q, dk, beta_k, dv, beta_v, grad_bstride, B, C, T,
+                  heads, scale, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

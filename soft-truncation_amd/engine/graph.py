@@ -984,7 +984,7 @@ class AttentionCore(Op):
   `qkv`, the channel slices [0,C), [C,2C), [2C,3C) of ONE [B,3C,H,W] tensor (the stacked projection of
   AttnBlockpp.emit), read and differentiated in place through a batch stride of 3 C T.
 
-  Three forms, chosen when the op is planned:
+  Three forms, chosen once when the op is planned (`self.form`: 'short', 'long', 'gemm'; with heads 'mh' or 'gemm'):
     * shapes the library's short fused kernels take (stk_attention_ok, T <= 256: every shipped config) run as one launch
       per direction pair with no [B,T,T] matrix in memory;
     * otherwise, where the library has include/stk_attention_long.h and stk_attention_long_ok holds, the streaming
@@ -1012,31 +1012,30 @@ class AttentionCore(Op):
       self.inputs = (q, k, v)
     self.B, self.C, self.T = B, C, H * W
     self.bs = (3 if qkv is not None else 1) * C * self.T       # floats between consecutive images of q / k / v
+    self.gs = self.bs                                          # ... and of their gradients: in place of q / k / v
     self.heads = heads = int(heads)
     if heads < 1 or C % heads:
       raise ValueError(f'{name}: heads = {heads} does not divide C = {C}')
     self.scale = float(int(C // heads) ** (-0.5))
     lib = g.lib
     allowed = lib is not None and os.environ.get('STK_ATTN_FUSED', '1') != '0'
-    self.mh = bool(heads > 1 and allowed and getattr(lib, 'has_attention_mh', False) and
-                   int(lib.attention_mh_ok(B, C, self.T, heads)))
-    self.fused = bool(heads == 1 and allowed and int(lib.attention_ok(B, C, self.T)))
-    self.long = bool(heads == 1 and allowed and not self.fused and getattr(lib, 'has_attention_long', False) and
-                     int(lib.attention_long_ok(B, C, self.T)))
-    if self.mh:
-      self.lse = g.new((B, heads, self.T), needs_grad=False, name=name + '.lse')
-      self.delta = g.new((B, heads, self.T), needs_grad=False, name=name + '.delta')
-      self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
-    elif self.fused or self.long:
-      self.lse = g.new((B, self.T), needs_grad=False, name=name + '.lse')
-      self.delta = g.new((B, self.T), needs_grad=False, name=name + '.delta')
-      self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
-    elif heads > 1:
-      self.s = g.new((B, heads, self.T, self.T), needs_grad=False, name=name + '.s')
-      self.p = g.new((B, heads, self.T, self.T), needs_grad=False, name=name + '.p')
+    if heads > 1:
+      ok = allowed and getattr(lib, 'has_attention_mh', False) and int(lib.attention_mh_ok(B, C, self.T, heads))
+      self.form = 'mh' if ok else 'gemm'
+    elif allowed and int(lib.attention_ok(B, C, self.T)):
+      self.form = 'short'
+    elif allowed and getattr(lib, 'has_attention_long', False) and int(lib.attention_long_ok(B, C, self.T)):
+      self.form = 'long'
     else:
-      self.s = g.new((B, self.T, self.T), needs_grad=False, name=name + '.s')
-      self.p = g.new((B, self.T, self.T), needs_grad=False, name=name + '.p')
+      self.form = 'gemm'
+    rows = (B,) + ((heads,) if heads > 1 else ()) + (self.T,)             # one softmax row per (image, head, query)
+    if self.form != 'gemm':
+      self.lse = g.new(rows, needs_grad=False, name=name + '.lse')
+      self.delta = g.new(rows, needs_grad=False, name=name + '.delta')
+      self.rec = g.new((1024,), needs_grad=False, name=name + '.rec')      # scale records of q, k, v, do
+    else:
+      self.s = g.new(rows + (self.T,), needs_grad=False, name=name + '.s')
+      self.p = g.new(rows + (self.T,), needs_grad=False, name=name + '.p')
     self.o = g.new((B, C, H, W), name=name + '.o')
     self.y = self.o
     # algorithmic FLOPs: forward 2 GEMMs, backward 4 (+ 3 recomputed by the fused kernels, not counted)
@@ -1053,124 +1052,82 @@ class AttentionCore(Op):
     return ((rt.v(self.q), rt.v(self.k), rt.v(self.vv)), (rt.g(self.q), rt.g(self.k), rt.g(self.vv)),
             (self.b(self.q), self.b(self.k), self.b(self.vv)))
 
+  fused = property(lambda self: self.form == 'short')          # the three fused forms, as the booleans they used to be
+  long = property(lambda self: self.form == 'long')
+  mh = property(lambda self: self.form == 'mh')
+  _STEM = {'short': 'attention', 'long': 'attention_long', 'mh': 'attention_mh'}   # of a fused form's entries and labels
+
+  def _fused(self, rt, direction, flops, *operands):
+    """The one launch of a fused form: its operands, then B, C, T[, heads], scale[, workspace], stream."""
+    stem = self._STEM[self.form]
+    args = operands + (self.B, self.C, self.T) + ((self.heads,) if self.form == 'mh' else ()) + (self.scale,)
+    if self.form != 'short':
+      args += (rt.ws, rt.ws_bytes)
+    rt.timed(f'{stem}.{direction}.x2', flops, getattr(rt.lib, f'{stem}_{direction}_f32'), *args, rt.stream)
+
   def forward(self, rt):
-    B, C, T, bs = self.B, self.C, self.T, self.bs
+    B, T, bs, h = self.B, self.T, self.bs, self.heads
     lib = rt.lib
     (q, k, v), _, _ = self._qkv(rt)
-    if self.mh:
-      rt.timed('attention_mh.fwd.x2', self.flops, lib.attention_mh_fwd_f32, q, k, v, bs, rt.v(self.o),
-               rt.v(self.lse), rt.v(self.rec), B, C, T, self.heads, self.scale, rt.ws, rt.ws_bytes, rt.stream)
-      return
-    if self.heads > 1:
-      return self._forward_heads(rt, q, k, v)
-    if self.fused:
-      rt.timed('attention.fwd.x2', self.flops, lib.attention_fwd_f32, q, k, v, bs, rt.v(self.o),
-               rt.v(self.lse), rt.v(self.rec), B, C, T, self.scale, rt.stream)
-      return
-    if self.long:
-      rt.timed('attention_long.fwd.x2', self.flops, lib.attention_long_fwd_f32, q, k, v, bs, rt.v(self.o),
-               rt.v(self.lse), rt.v(self.rec), B, C, T, self.scale, rt.ws, rt.ws_bytes, rt.stream)
-      return
-    # S[b][t][t'] = sum_c Q[b][c][t] K[b][c][t']
-    lib.gemm_f32(q, 1, T, bs, k, T, 1, bs, rt.v(self.s), T, 1, T * T,
-                 None, 0, T, T, C, B, 1.0, 0.0, rt.stream)
-    lib.softmax_fwd_f32(rt.v(self.s), rt.v(self.p), B * T, T, self.scale, rt.stream)
-    # O[b][c][t] = sum_t' V[b][c][t'] P[b][t][t']
-    lib.gemm_f32(v, T, 1, bs, rt.v(self.p), 1, T, T * T, rt.v(self.o), T, 1, C * T,
-                 None, 0, C, T, T, B, 1.0, 0.0, rt.stream)
-
-  def _forward_heads(self, rt, q, k, v):
-    """The GEMM + softmax form of `heads` > 1: the single-head launches once per head, on the head's channel slice."""
-    B, C, T, bs, h = self.B, self.C, self.T, self.bs, self.heads
-    d, lib = C // h, rt.lib
-    for n in range(h):
+    if self.form != 'gemm':
+      return self._fused(rt, 'fwd', self.flops, q, k, v, bs, rt.v(self.o), rt.v(self.lse), rt.v(self.rec))
+    # per head n, on its channel slice of width d (one head: the whole image)
+    d = self.C // h
+    for n in range(h):   # S[b][n][t][t'] = sum_c Q[b][n d + c][t] K[b][n d + c][t']
       off, sp = 4 * n * d * T, 4 * n * T * T                   # bytes to head n of an operand / of s and p
       lib.gemm_f32(q + off, 1, T, bs, k + off, T, 1, bs, rt.v(self.s) + sp, T, 1, h * T * T,
                    None, 0, T, T, d, B, 1.0, 0.0, rt.stream)
     lib.softmax_fwd_f32(rt.v(self.s), rt.v(self.p), B * h * T, T, self.scale, rt.stream)
-    for n in range(h):
+    for n in range(h):   # O[b][n d + c][t] = sum_t' V[b][n d + c][t'] P[b][n][t][t']
       off, sp = 4 * n * d * T, 4 * n * T * T
-      lib.gemm_f32(v + off, T, 1, bs, rt.v(self.p) + sp, 1, T, h * T * T, rt.v(self.o) + off, T, 1, C * T,
+      lib.gemm_f32(v + off, T, 1, bs, rt.v(self.p) + sp, 1, T, h * T * T, rt.v(self.o) + off, T, 1, self.C * T,
                    None, 0, d, T, T, B, 1.0, 0.0, rt.stream)
 
-  def _backward_heads(self, rt, go, q, k, v, gq, gk, gv, bq, bk, bv, gs):
-    B, C, T, bs, h = self.B, self.C, self.T, self.bs, self.heads
-    d, lib = C // h, rt.lib
-    dp = rt.v(self.s)                                          # S is dead after the forward softmax: dP, then dS
+  def backward(self, rt):
+    B, C, T, bs, gs, h = self.B, self.C, self.T, self.bs, self.gs, self.heads
+    lib = rt.lib
+    go = rt.g(self.o)
+    (q, k, v), grads, betas = self._qkv(rt)
+    if all(g is None for g in grads):
+      return
+    if self.form != 'gemm':
+      # a gradient nobody asked for is passed as NULL: the kernels skip it.  The short single-head entry takes no NULL and
+      # writes all three; there such a gradient goes to the workspace (separate tensors only)
+      short = self.form == 'short'
+      spare = [rt.ws + i * 4 * B * C * T if short else None for i in range(3)]
+      gb = []
+      for g, beta, unwanted in zip(grads, betas, spare):
+        gb += [g, beta] if g is not None else [unwanted, 0.0]
+      o = () if short else (rt.v(self.o),)                     # delta from o and dO (the short kernels: from p and dP)
+      return self._fused(rt, 'bwd', 2.0 * self.flops, q, k, v, bs, *o, go, rt.v(self.lse), rt.v(self.rec),
+                         rt.v(self.delta), *gb, gs)
+    (gq, gk, gv), (bq, bk, bv) = grads, betas
+    d = C // h
+    dp = rt.v(self.s)   # S is dead after the forward softmax: reuse it for dP, then dS
     for n in range(h):
       off, sp = 4 * n * d * T, 4 * n * T * T
+      # dP[b][n][t][t'] = sum_c dO[b][n d + c][t] V[b][n d + c][t']
       lib.gemm_f32(go + off, 1, T, C * T, v + off, T, 1, bs, dp + sp, T, 1, h * T * T,
                    None, 0, T, T, d, B, 1.0, 0.0, rt.stream)
-      if gv is not None:
+      if gv is not None:  # dV[b][n d + c][t'] = sum_t dO[b][n d + c][t] P[b][n][t][t']
         lib.gemm_f32(go + off, T, 1, C * T, rt.v(self.p) + sp, T, 1, h * T * T, gv + off, T, 1, gs,
                      None, 0, d, T, T, B, 1.0, bv, rt.stream)
-    lib.softmax_bwd_f32(rt.v(self.p), dp, dp, B * h * T, T, self.scale, rt.stream)
+    lib.softmax_bwd_f32(rt.v(self.p), dp, dp, B * h * T, T, self.scale, rt.stream)   # dS in place
     for n in range(h):
       off, sp = 4 * n * d * T, 4 * n * T * T
-      if gq is not None:
+      if gq is not None:  # dQ[b][n d + c][t] = sum_t' K[b][n d + c][t'] dS[b][n][t][t']
         lib.gemm_f32(k + off, T, 1, bs, dp + sp, 1, T, h * T * T, gq + off, T, 1, gs,
                      None, 0, d, T, T, B, 1.0, bq, rt.stream)
-      if gk is not None:
+      if gk is not None:  # dK[b][n d + c][t'] = sum_t Q[b][n d + c][t] dS[b][n][t][t']
         lib.gemm_f32(q + off, T, 1, bs, dp + sp, T, 1, h * T * T, gk + off, T, 1, gs,
                      None, 0, d, T, T, B, 1.0, bk, rt.stream)
 
-  def backward(self, rt):
-    B, C, T, bs = self.B, self.C, self.T, self.bs
-    lib = rt.lib
-    go = rt.g(self.o)
-    (q, k, v), (gq, gk, gv), (bq, bk, bv) = self._qkv(rt)
-    if gq is None and gk is None and gv is None:
-      return
-    if self.mh:
-      # a gradient nobody asked for is passed as NULL: the kernels skip it
-      rt.timed('attention_mh.bwd.x2', 2.0 * self.flops, lib.attention_mh_bwd_f32, q, k, v, bs, rt.v(self.o), go,
-               rt.v(self.lse), rt.v(self.rec), rt.v(self.delta), gq, bq if gq is not None else 0.0,
-               gk, bk if gk is not None else 0.0, gv, bv if gv is not None else 0.0,
-               bs if self.qkv is not None else C * T, B, C, T, self.heads, self.scale, rt.ws, rt.ws_bytes, rt.stream)
-      return
-    if self.heads > 1:
-      return self._backward_heads(rt, go, q, k, v, gq, gk, gv, bq, bk, bv, bs if self.qkv is not None else C * T)
-    if self.fused:
-      # the kernels write all three gradients; one that nobody asked for goes to the workspace (separate tensors only)
-      n4 = 4 * B * C * T
-      gs = bs if self.qkv is not None else C * T
-      spare = [rt.ws + i * n4 for i in range(3)]
-      rt.timed('attention.bwd.x2', 2.0 * self.flops, lib.attention_bwd_f32, q, k, v, bs, go,
-               rt.v(self.lse), rt.v(self.rec), rt.v(self.delta),
-               gq if gq is not None else spare[0], bq if gq is not None else 0.0,
-               gk if gk is not None else spare[1], bk if gk is not None else 0.0,
-               gv if gv is not None else spare[2], bv if gv is not None else 0.0,
-               gs, B, C, T, self.scale, rt.stream)
-      return
-    gs = bs if self.qkv is not None else C * T
-    if self.long:
-      # a gradient nobody asked for is passed as NULL: the kernels skip it
-      rt.timed('attention_long.bwd.x2', 2.0 * self.flops, lib.attention_long_bwd_f32, q, k, v, bs, rt.v(self.o), go,
-               rt.v(self.lse), rt.v(self.rec), rt.v(self.delta), gq, bq if gq is not None else 0.0,
-               gk, bk if gk is not None else 0.0, gv, bv if gv is not None else 0.0,
-               gs, B, C, T, self.scale, rt.ws, rt.ws_bytes, rt.stream)
-      return
-    dp = rt.v(self.s)   # S is dead after the forward softmax: reuse it for dP, then dS
-    # dP[b][t][t'] = sum_c dO[b][c][t] V[b][c][t']
-    lib.gemm_f32(go, 1, T, C * T, v, T, 1, bs, dp, T, 1, T * T,
-                 None, 0, T, T, C, B, 1.0, 0.0, rt.stream)
-    if gv is not None:  # dV[b][c][t'] = sum_t dO[b][c][t] P[b][t][t']
-      lib.gemm_f32(go, T, 1, C * T, rt.v(self.p), T, 1, T * T, gv, T, 1, gs,
-                   None, 0, C, T, T, B, 1.0, bv, rt.stream)
-    lib.softmax_bwd_f32(rt.v(self.p), dp, dp, B * T, T, self.scale, rt.stream)   # dS in place
-    if gq is not None:  # dQ[b][c][t] = sum_t' K[b][c][t'] dS[b][t][t']
-      lib.gemm_f32(k, T, 1, bs, dp, 1, T, T * T, gq, T, 1, gs,
-                   None, 0, C, T, T, B, 1.0, bq, rt.stream)
-    if gk is not None:  # dK[b][c][t'] = sum_t Q[b][c][t] dS[b][t][t']
-      lib.gemm_f32(q, T, 1, bs, dp, T, 1, T * T, gk, T, 1, gs,
-                   None, 0, C, T, T, B, 1.0, bk, rt.stream)
-
   def ws_bytes(self, lib):
-    if self.mh:
+    if self.form == 'mh':
       return int(lib.attention_mh_ws_bytes(self.B, self.C, self.T, self.heads))
-    if self.long:
+    if self.form == 'long':
       return int(lib.attention_long_ws_bytes(self.B, self.C, self.T))
-    return 3 * 4 * self.B * self.C * self.T if (self.fused and self.qkv is None) else 0
+    return 3 * 4 * self.B * self.C * self.T if (self.form == 'short' and self.qkv is None) else 0
 
 
 class RowScale(Op):

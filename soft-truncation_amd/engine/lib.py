@@ -139,7 +139,7 @@ SIGNATURES_ATTN_LONG = {
   'stk_attention_long_fwd_f32': [P, P, P, L, P, P, P, I, I, I, F, P, L, S],
   'stk_attention_long_bwd_f32': [P, P, P, L, P, P, P, P, P, P, F, P, F, P, F, L, I, I, I, F, P, L, S],
 }
-_NO_CHECK_ATTN_LONG = {'stk_attention_long_ws_bytes', 'stk_attention_long_ok'}   # its queries (tests/_launch_trace.py reads this)
+_NO_CHECK_ATTN_LONG = {'stk_attention_long_ws_bytes', 'stk_attention_long_ok'}   # its queries
 # include/stk_attention_mh.h: the attention core with several heads, short and streaming form behind one pair of entries
 # (AttentionCore plans the GEMM form with a host loop over the heads without it).
 SIGNATURES_ATTN_MH = {

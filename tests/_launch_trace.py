@@ -10,7 +10,7 @@ import numpy as np
 
 SWITCHES = ('STK_PLANES', 'STK_PLANES_WGRAD', 'STK_X_RECORDS', 'STK_SHARED_DY', 'STK_RES_VIA', 'STK_DY_PRODUCER',
             'STK_GN_FOLD_BATCH', 'STK_WGRAD_STREAM')
-TINY = ('vp', 'rve', 've', 'wide', 've_cat', 'vp_ff')
+TINY = ('vp', 'rve', 've', 'wide', 'wide_mh', 've_cat', 'vp_ff')
 SHIPPED = ('cifar10_ddpmpp_nll_st', 'imagenet32_ddpmpp_st', 'celeba_uncsnpp_st', 'celebahq_uncsnpp_st')
 FULL_TEXT = ('wide',)             # models whose traces the fixture keeps as text (the others: count and digest); `wide`
                                   # alone is 400 KB of text in all modes, and it is the family that takes every fused path
@@ -25,12 +25,12 @@ SEED = 0x5EED
 def is_launch(L, name):
   """Is entry `name` (without the stk_ prefix) of engine/lib.py a launch, i.e. does it take a stream as its last argument?
   (The pointer and the stream type are the same ctypes class, so the queries that end in a pointer are told apart by
-  the tables that bind them unchecked.)"""
+  L._NO_CHECK, the entries of every header that are bound unchecked.)"""
   full = 'stk_' + name
-  for table in (L.SIGNATURES, L.SIGNATURES_FP16, L.SIGNATURES_FP16_TRAIN, L.SIGNATURES_BLOCKS, L.SIGNATURES_ATTN_LONG):
+  for table in (L.SIGNATURES, *(h.table for h in L.OPTIONAL_HEADERS)):
     row = table.get(full)
     if row is not None:
-      return bool(row) and row[-1] is L.S and full not in L._NO_CHECK and full not in L._NO_CHECK_ATTN_LONG
+      return bool(row) and row[-1] is L.S and full not in L._NO_CHECK
   return False                     # not an entry of the C ABI at all (a helper of StkLib)
 
 

@@ -17,10 +17,12 @@ def tiny_config(st, family, dropout=0.0, device='cpu'):
     cfg = st.configs.tiny(st.configs.celeba_uncsnpp_st(), dropout=dropout)
   elif family == 've':      # NCSN++ 256-style: fourier, FIR, input_skip / output_skip, VE SDE
     cfg = st.configs.tiny(st.configs.celebahq_uncsnpp_st(), ch_mult=(1, 1, 2), dropout=dropout)
-  elif family == 'wide':    # DDPM++ with enough channels (96 / 192) for the split (fp16 two-way) conv kernels, their K-split and
-    # few-tile variants and the prepared-weight path; the other families stay on the f32-input kernels
+  elif family in ('wide', 'wide_mh'):   # DDPM++ with enough channels (96 / 192) for the split (fp16 two-way) conv kernels, their
+    # K-split and few-tile variants and the prepared-weight path; the other families stay on the f32-input kernels
     cfg = st.configs.tiny(st.configs.cifar10_ddpmpp_nll_st(), nf=96, ch_mult=(1, 2), num_res_blocks=1, image_size=16,
                           attn_resolutions=(8,), dropout=dropout)
+    if family == 'wide_mh':   # ... with two heads: attention at C = 192, d = 96, T = 64
+      cfg.model.num_heads = 2
   elif family in ('vp_elu', 'vp_relu', 'vp_lrelu'):   # the other activations of layers.get_act (models/layers.py:29-41)
     cfg = st.configs.tiny(st.configs.cifar10_ddpmpp_nll_st(), dropout=dropout)
     cfg.model.nonlinearity = family[3:]

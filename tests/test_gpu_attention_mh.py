@@ -124,7 +124,8 @@ def test_attention_mh_accumulates_with_beta_1(hip_lib, shape):
     check(run_mh(hip_lib, q, k, v, do, heads, stacked=stacked, beta=1.0, g0=g0), want, f'{shape} beta=1 stacked={stacked}')
 
 
-@pytest.mark.parametrize('shape', [(2, 128, 2, 64), (1, 256, 4, 256), (2, 128, 4, 320), (2, 128, 1, 64)], ids=str)
+@pytest.mark.parametrize('shape', [(2, 128, 2, 64), (1, 256, 4, 256), (2, 128, 4, 320), (2, 128, 1, 64),
+                                   (2, 64, 1, 320)], ids=str)
 def test_attention_mh_null_gradients(hip_lib, shape):
   """Each gradient NULL in turn: the other two are those of the full call bit for bit, the missing one is not touched."""
   B, C, heads, T = shape
