@@ -27,8 +27,8 @@
 // on each side ([ROWS][COLS + 2] pixel slots, <= 48: three DMA instructions per plane instead of two), the x tile loses its
 // halo columns ([ROWS + 2][COLS] slots, <= 96: six instructions per plane instead of seven).  Measured (MI355X, batch 128,
 // kernel + reduce, 256 workgroups, profiles/r06_x2w.txt): 128 -> 128 @ 32 x 32 138.8 -> 132.9 us, 384 -> 128 397.3 -> 373.5, the
-// 16- / 8- / 4-wide maps within 2 %; in the step -0.04 ms: with ONE workgroup per CU the kernel is bound by the latency of its
-// LDS-DMA -- or so it seemed: a third LDS stage bought nothing either (STAGES below).
+// 16- / 8- / 4-wide maps within 2 %; in the step -0.04 ms: with ONE workgroup per CU the kernel was bound by the latency of its
+// LDS-DMA, which a compiler-inserted wait kept it from hiding ("The ring" below).
 #pragma once
 
 namespace x2w {
@@ -51,6 +51,22 @@ __device__ __forceinline__ halfx8 cat(s4 lo, s4 hi) {
   return __builtin_bit_cast(halfx8, v);
 }
 
+// The staging DMA: 64 lanes x 16 bytes from the buffer `rs` (byte offset `voff` per lane + `soff`; bit 31 of voff set = out of
+// range = zeros) to the 1024 LDS bytes at `dst`.  Issued as an asm statement on purpose: see "The ring" at wgrad_kernel.  M0 (the LDS
+// base of the DMA) is written and restored inside the statement; the s_nop covers the M0 -> LDS-DMA wait state and the five a
+// VALU-written SGPR needs before a buffer instruction reads it, whatever code precedes the statement.  hipcc counts nothing of it:
+// the kernel waits for these loads itself (vmcnt(0) at the loop head; a plain __syncthreads() does not).
+__device__ __forceinline__ u32x4 rsrc_words(const void* base, long bytes) {      // = x2::make_rsrc, as the four SGPRs
+  const unsigned long p = reinterpret_cast<unsigned long>(base);
+  return u32x4{(unsigned)p, (unsigned)(p >> 32) & 0xffffu, (unsigned)bytes, 0x00020000u};
+}
+__device__ __forceinline__ void dma16(u32x4 rs, const unsigned char* dst, unsigned voff, unsigned soff) {
+  const unsigned lds_addr = (unsigned)(unsigned long)(lds_void*)dst;
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
+}
+
 constexpr int A_INSTR = 3;
 constexpr int A_BLK = A_INSTR * 16 * 64;    // 3072: 48 pixel slots of one 32-channel block of dy
 constexpr int A_PLANE = 4 * A_BLK;          // 12288
@@ -64,14 +80,30 @@ constexpr int BUF = 2 * A_PLANE + 2 * B_PLANE;   // 36864 per stage
 // split's chunks alternately, each with its own LDS stages; after the last chunk group 1 hands its 144 accumulators per thread
 // to group 0 through the (now free) LDS in three rounds of three taps, and group 0 writes the slab: half the K split and slab
 // traffic at the same eight waves per CU.  The sum of the two groups is taken in a fixed order (group 0 + group 1).
-// STAGES = 2: LDS stages of the DMA ring.  Three stages (two chunks in flight, 110 KB of LDS) were measured in round 6 and bought
-// nothing -- 128 -> 128 @ 32 x 32 at 256 workgroups 134.4 (two) / 135.9 us (three), 384 -> 128 378.2 / 380.8 -- and cost the step
-// 0.2 ms (35.82 -> 35.99 / 36.04 ms: more LDS, 296 instead of 209 registers, less room for the main chain's waves on the CU), so
-// the kernel is not waiting for its DMA either (profiles/r06_x2w.txt).  Also measured: the next chunk's nine DMA instructions issued
-// BETWEEN the MFMA groups of the current chunk instead of in a burst in front of them (an LDS-DMA costs its wave 60-180 cycles of issue,
-// and a SIMD holds ONE wave of this kernel in the two-stream geometry): seven times SLOWER, because hipcc then puts an s_waitcnt vmcnt(0)
-// in front of every DMA and every following fragment read (it cannot prove that the DMA's LDS bytes are not the ones being read, even
-// with the two stages as two __shared__ objects), which makes every DMA synchronous.  The burst at the chunk boundary stays.
+// The ring.  STAGES = 2 LDS stages: at the head of round i every wave waits for its own DMAs of chunk i (vmcnt(0)), then the
+// workgroup's barrier, then the burst of DMAs for chunk i + 1 into the other stage, then the fragment reads and MFMAs of chunk i.
+//   RAW (a fragment read sees the DMA's bytes): every wave has waited for the loads it issued, and the barrier follows: all of
+//     chunk i has landed before anybody reads it.  The halo slots zeroed once (below) are written and read by the same wave.
+//   WAR (the burst overwrites the stage read in round i - 1): the barrier follows every wave's last fragment read of that stage --
+//     a wave's MFMAs of round i - 1 need all its reads, and it reaches the barrier behind them.
+//   Both groups of GROUPS = 2 and dead waves run every barrier; every skipped DMA or chunk is skipped by a whole wave or group.
+// Until this was written as it is now the ring was SYNCHRONOUS.  With the DMA as __builtin_amdgcn_raw_ptr_buffer_load_lds, hipcc
+// counts it as an LDS write it cannot tell from the bytes the fragment reads address (one __shared__ array, run-time stage index;
+// two __shared__ objects did not help) and puts an s_waitcnt vmcnt(0) in front of the FIRST fragment read of chunk i -- i.e. behind
+// the burst for chunk i + 1 it has just issued: every chunk paid a full DMA round trip and then its MFMAs, one wave per SIMD, nothing
+// to hide it (disassembly before / after: profiles/x2w_prefetch.txt).  That one wait explains what round 6 measured and misread as
+// "not waiting for its DMA": a third stage gave +-0 (134.4 / 135.9 us, -0.2 ms in the step for its LDS) because it cannot help a
+// synchronous ring; the 128 x 64 tile was faster alone because it has fewer round trips per MFMA; two groups help on the 16- / 8-wide
+// maps because they hide each other's waits; the DMAs interleaved between the MFMA groups were seven times slower because the same
+// wait then stood behind each of the nine.  As an asm statement (dma16) the DMA is outside hipcc's counters and alias analysis:
+// the protocol above is the only synchronisation, and the loop has ONE vmcnt wait, at its head.  Measured (MI355X, batch 128,
+// kernel + reduce, 256 workgroups, us, before -> asynchronous -> and without the dead DMAs below): 128 -> 128 @ 32 x 32 134.3 ->
+// 126.2 -> 120.8 (2.10 -> 1.97 -> 1.89 us per chunk), 384 -> 128 373.3 -> 316.3 -> 307.2, 256 -> 256 @ 16 x 16 176.4 -> 166.6 -> 156.4,
+// @ 8 x 8 63.3 -> 59.6 -> 59.2, @ 4 x 4 within 1 %; same bits.  In the step 37.75 -> 37.21 -> 36.99 ms (CIFAR-10 net), the 64 x 64 net
+// 120.8 -> 118.4, the 256 x 256 net 37.50 -> 37.09.  No register and no LDS byte more.  (A third stage has not been measured again.)
+// Dead DMAs.  A stage issues only instructions that can carry data: the x tile B_LIVE = 6 / 4 / 3 / 3 per plane (COLS = 32 / 16 / 8 /
+// 4) of the B_INSTR its slots are laid out for, and the dy tile two instead of three per plane where the map is exactly COLS wide
+// (a_whole_rows in the kernel).  An LDS-DMA costs its wave 60-180 cycles of issue, in front of the chunk's MFMAs.
 // FORM = GROUPS | X1_FORM (wgrad_kernel<COLS, GROUPS | X1_FORM>): the weight gradient of the fp16 training mode
 // (include/stk_fp16_train.h), ONE product per element, hi(dy) hi(x) -- only split 0 of both operands is DMA'd (the split-1
 // slots of the stages stay unused) and only the SA = SB = 0 MFMA of the three is issued: half the DMA bytes, 9 instead of 27
@@ -111,11 +143,19 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
   const int c_last = min(a.nchunks_total, c_begin + a.chunks_per_split) - 1;
 
   // ---- DMA sources ----------------------------------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t a_rs = x2::make_rsrc(a.dypl, 2L * a.dy_ps);
-  const __amdgpu_buffer_rsrc_t b_rs = x2::make_rsrc(a.xpl, 2L * a.x_ps);
+  const u32x4 a_rs = rsrc_words(a.dypl, 2L * a.dy_ps);
+  const u32x4 b_rs = rsrc_words(a.xpl, 2L * a.x_ps);
   const int piece = (lane & 3) * 16;
-  // dy tile of this wave's block: slot s = 16 j + lane / 4 = (row r, column c) holds map pixel (y0 + r, x0 + c - 1)
-  int a_rel[A_INSTR], a_c[A_INSTR];
+  // dy tile of this wave's block: slot s = 16 j + lane / 4 = (row r, column c) holds map pixel (y0 + r, x0 + c - 1) ...
+  // ... unless the map is exactly COLS wide (the 32- and 16-wide maps; wgrad_kernel<16> is launched for W = 16 only): then x0 = 0,
+  // the two halo columns of every tile row lie outside the map whatever the chunk, and the chunk's 32 pixels are 2048 consecutive
+  // bytes of the plane.  TWO instructions move them (instruction j pixels 16 j ..., to the slots behind their row's left halo slot)
+  // instead of three, and the halo slots are zeroed ONCE in front of the loop instead of by every stage's range check.  Same slots,
+  // same fragment addresses, and the per-lane registers of the three-instruction form (a_c = 1: always inside the map), which
+  // W > COLS keeps (COLS = 32 only: there the halo columns are pixels).
+  const bool a_whole_rows = COLS == 16 || (COLS == 32 && a.W == 32);
+  const int a_instr = a_whole_rows ? 2 : A_INSTR;
+  int a_rel[A_INSTR], a_c[A_INSTR], a_dst[A_INSTR];
 #pragma unroll
   for (int j = 0; j < A_INSTR; ++j) {
     const int sl = 16 * j + (lane >> 2);
@@ -123,17 +163,27 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
     a_c[j] = sl - r * TPA;
     int img = 0;
     if (TWO) { img = r >> 2; r &= 3; }                                  // next image: Cob blocks on
-    if (sl >= ROWS * TPA || !co_live) a_c[j] = -1000000;                // never inside the map
+    if (sl >= ROWS * TPA) a_c[j] = -1000000;                            // never inside the map
     a_rel[j] = (img * a.Cob * a.HW + r * a.W + a_c[j] - 1) * 64 + piece;
+    a_dst[j] = wid * A_BLK + j * 1024;
+    if (a_whole_rows) {                                                  // (workgroup-uniform)
+      a_c[j] = 1;
+      a_rel[j] = sl * 64 + piece;                                        // pixel 16 j + lane / 4 of the chunk
+      a_dst[j] = wid * A_BLK + ((16 * j / COLS) * TPA + 16 * j % COLS + 1) * 64;
+    }
+    if (!co_live) { a_c[j] = -1000000; a_rel[j] = -1000000 * 64; }       // dead wave: DMA of zeros
   }
-  // x tile: slot s = 16 j + lane / 4 = (row ty, column tx) holds map pixel (y0 - 1 + ty, x0 + tx).  The 12 instructions (6 per
-  // plane) go round the four waves, three each -- every wave issues the same number per stage (the vmcnt of the ring)
-  int b_rel[3], b_ty[3], b_dst[3]; unsigned b_pl[3];
+  // x tile: slot s = 16 j + lane / 4 = (row ty, column tx) holds map pixel (y0 - 1 + ty, x0 + tx).  Only the B_LIVE instructions per
+  // plane whose slots are inside the [TRB][COLS] tile are issued (6 / 4 / 3 / 3 of the B_INSTR laid out, for COLS = 32 / 16 / 8 / 4);
+  // the NS B_LIVE of a stage go round the four waves.  The waves need not issue equally many: each waits for vmcnt(0).
+  constexpr int B_LIVE = TRB * COLS / 16, B_ALL = NS * B_LIVE, B_WAVE = (B_ALL + 3) / 4;
+  static_assert(B_LIVE * 16 == TRB * COLS && B_LIVE <= B_INSTR, "the x tile is whole instructions");
+  int b_rel[B_WAVE], b_ty[B_WAVE], b_dst[B_WAVE]; unsigned b_pl[B_WAVE];
 #pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    const int idx = wid + 4 * u, j = idx % B_INSTR, pl = idx / B_INSTR;
+  for (int u = 0; u < B_WAVE; ++u) {
+    const int idx = wid + 4 * u, j = idx % B_LIVE, pl = idx / B_LIVE;    // idx >= B_ALL: not issued (stage)
     const int sl = 16 * j + (lane >> 2);
-    b_ty[u] = sl / COLS;
+    b_ty[u] = COLS >= 16 ? 16 * j / COLS : sl / COLS;                    // COLS >= 16: an instruction is inside ONE tile row (wave-uniform)
     const int tx = sl - b_ty[u] * COLS;
     int img = 0;
     if (TWO) { img = b_ty[u] / 6; b_ty[u] -= 6 * img; }                 // row inside its image's tile
@@ -149,20 +199,22 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
     const int a_chunk = ((b * a.Cob + co_blk) * a.HW + hw0) * 64;
 #pragma unroll
     for (int j = 0; j < A_INSTR; ++j) {
+      if (j >= a_instr) continue;                                        // (workgroup-uniform)
+      // inside the map?  COLS = 32 has ONE tile row, so a_rel is 64 (column - 1) + piece: tested on the bytes, without a_c's registers
       const int xx = x0 + a_c[j] - 1;
-      const unsigned vo = (xx >= 0 && xx < a.W) ? (unsigned)(a_chunk + a_rel[j]) : 0x80000000u;    // outside the map: DMA of zeros
+      const bool in = COLS == 32 ? (unsigned)(x0 * 64 + a_rel[j]) < (unsigned)(a.W * 64) : (xx >= 0 && xx < a.W);
+      const unsigned vo = in ? (unsigned)(a_chunk + a_rel[j]) : 0x80000000u;                       // outside the map: DMA of zeros
 #pragma unroll
       for (int s = 0; s < NS; ++s)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (lds_void*)(buf + s * A_PLANE + wid * A_BLK + j * 1024), 16,
-                                                 (int)vo, (int)(s * (unsigned)a.dy_ps), 0, 0);
+        dma16(a_rs, buf + s * A_PLANE + a_dst[j], vo, s * (unsigned)a.dy_ps);
     }
     const int b_chunk = ((b * a.Cib + tci) * a.HW + hw0) * 64;
 #pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      if (X1 && b_pl[u]) continue;                                       // split 1 of x (wave-uniform)
+    for (int u = 0; u < B_WAVE; ++u) {
+      if (4 * u + 3 >= B_ALL && wid + 4 * u >= B_ALL) continue;          // nothing left for this wave (wave-uniform)
       const int yy = y0 + b_ty[u] - 1;
       const unsigned vo = (yy >= 0 && yy < a.H) ? (unsigned)(b_chunk + b_rel[u]) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (lds_void*)(buf + b_dst[u]), 16, (int)vo, (int)(b_pl[u] * (unsigned)a.x_ps), 0, 0);
+      dma16(b_rs, buf + b_dst[u], vo, b_pl[u] * (unsigned)a.x_ps);
     }
   };
 
@@ -218,6 +270,16 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
   // group g takes chunks c_begin + g, c_begin + g + GROUPS, ...; both groups run the same number of barrier rounds.  The ring keeps
   // STAGES - 1 chunks in flight: chunk i of this group lives in stage i % STAGES.
   const int rounds = (c_last - c_begin + GROUPS) / GROUPS;
+  if (a_whole_rows) {
+    // the halo-column slots no stage writes: 2 per tile row, of this wave's block, in every plane of every stage -- 64 bytes each,
+    // 16 per lane.  Each wave zeroes the slots it alone reads, and reads them behind the loop's barriers.
+    constexpr int NH = COLS >= 16 ? STAGES * NS * ROWS * 2 : 0;                                // 8 / 16 slots (COLS = 32 / 16)
+    static_assert(NH * 4 <= 64, "one store per lane");
+    const int h = lane >> 2, side = h & 1, r = (h >> 1) % ROWS, sp = (h >> 1) / ROWS;          // sp = stage * NS + plane
+    if (h < NH)
+      *reinterpret_cast<uint4*>(lds + (sp / NS) * BUF + (sp % NS) * A_PLANE + wid * A_BLK + (r * TPA + side * (TPA - 1)) * 64 + piece) =
+          make_uint4(0u, 0u, 0u, 0u);
+  }
 #pragma unroll
   for (int i = 0; i < STAGES - 1; ++i)
     if (c_begin + i * GROUPS + grp <= c_last) stage(c_begin + i * GROUPS + grp, lds + i * BUF);
@@ -232,8 +294,12 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
     if (c <= c_last) compute(lds + cur * BUF);
     cur = cur + 1 == STAGES ? 0 : cur + 1;
   }
-  const float sa = x2::pow2_scale_of(amax_dy.reduce(red_amax[0][grp], tid));
-  const float sb = x2::pow2_scale_of(amax_x.reduce(red_amax[1][grp], tid));
+  // (the lane index taken afresh behind the loop -- the count the wave reductions below take anyway -- is two registers the loop
+  // does not carry: what the MFMA loop holds decides how many the kernel asks for)
+  const int lane_late = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int tid_late = wid * 64 + lane_late;
+  const float sa = x2::pow2_scale_of(amax_dy.reduce(red_amax[0][grp], tid_late));
+  const float sb = x2::pow2_scale_of(amax_x.reduce(red_amax[1][grp], tid_late));
   const float unscale = 1.f / (sa * sb);
   if (GROUPS == 2) {
     // group 1 -> group 0, three taps (48 floats per thread, 48 KB) per round through group 0's stages; element (t, e) of
@@ -246,14 +312,14 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
 #pragma unroll
         for (int t = 0; t < 3; ++t)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) xch[(16 * t + e) * 256 + tid] = acc[3 * r + t][e];
+          for (int e = 0; e < 16; ++e) xch[(16 * t + e) * 256 + tid_late] = acc[3 * r + t][e];
       }
       __syncthreads();
       if (grp == 0) {
 #pragma unroll
         for (int t = 0; t < 3; ++t)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) acc[3 * r + t][e] += xch[(16 * t + e) * 256 + tid];
+          for (int e = 0; e < 16; ++e) acc[3 * r + t][e] += xch[(16 * t + e) * 256 + tid_late];
       }
     }
     if (grp == 1) return;
@@ -261,7 +327,7 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
 
   // partial slab of split zs as [tap][Cout][Cin] (lanes = ci, contiguous); splitk_reduce_kernel re-lays it out
   float* slab = a.part + (long)zs * a.part_stride;
-  const int fk = lane >> 5, fc = lane & 31;
+  const int fk = lane_late >> 5, fc = lane_late & 31;
   const int ci = tci * 32 + fc;
   if (co_live && ci < a.Cin) {
 #pragma unroll
@@ -274,11 +340,13 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
   }
 }
 
-// What bounds this kernel ALONE is its LDS-DMA traffic: chunks x tiles x 36 KB per launch pass from the Infinity Cache into LDS (both
-// operands are activations; every 128 x 32 tile re-reads all of dy), and every shape lands at 4.5-5.2 TB/s of it.  A 128 x 64-tile variant
-// (eight waves sharing one dy tile, -33 % bytes per MFMA) confirmed it -- 133 -> 121 us, 376 -> 317, 0.455 of 833 on 512 -> 256 @ 16 x 16 --
-// and LOST inside the step at every workgroup count (+0.5 ... +3 ms): eight 214-register waves and 98 KB of LDS leave no room on a CU for the
-// main chain's waves.  Measured and removed in round 6 (profiles/r06_x2w.txt block 4; git history).  (A register diet to 192 per lane, so that
+// What bounded this kernel ALONE, until its ring became asynchronous ("The ring" above), was the LATENCY of its LDS-DMA, paid once per
+// chunk -- not the Infinity Cache -> LDS rate round 6 read out of "every shape lands at 4.5-5.2 TB/s" (chunks x tiles x 36 KB per launch; with
+// one round trip per 36 KB chunk and nothing in flight beside it, a latency reads as a rate).  The 128 x 64-tile variant of round 6 (eight
+// waves sharing one dy tile: 133 -> 121 us, 376 -> 317) was faster alone because it has half the round trips per MFMA, and LOST inside the step
+// at every workgroup count (+0.5 ... +3 ms): eight 214-register waves and 98 KB of LDS leave no room on a CU for the main chain's waves.
+// Measured and removed in round 6 (profiles/r06_x2w.txt block 4; git history).  The asynchronous ring reaches the same 121 us / 307 us with
+// the narrow tile's footprint.  What bounds it now has not been measured.  (A register diet to 192 per lane, so that
 // TWO of the main chain's 160-register GEMM waves fit beside one of this kernel's on a SIMD, did not get past the compiler: it fills the
 // 256-register budget of the launch bounds with hoisted fragment reads whatever the source says, and ignores amdgpu_num_vgpr.)
 
