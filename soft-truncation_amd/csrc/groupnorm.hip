@@ -30,10 +30,15 @@
 //    activation, dropout), gn_du (backward), gn_bound_load / gn_bound_fold (the a-priori bound of |y|), gn_amax_wave /
 //    gn_amax_commit (block maxima into a scale record).  The kernels that write planes split their output by the rule of
 //    split.h, the one the convolutions that read them assume.
+//  * Scale-shift conditioning (include/stk_adagn.h): y = act(GroupNorm(x) (1 + s_nc) + b_nc) is, per sample, this layer with the
+//    affine pair gamma' = gamma (1 + s), beta' = beta (1 + s) + b.  The fp32 kernels carry a MOD template flag that forms the pair
+//    where they load (gamma, beta) (gn_affine); the plain instantiations are what they were.  gn_mod_fold_kernel turns the
+//    backward's per-(sample, channel) sums -- d(beta'), d(gamma') -- into d(s), d(b), d(gamma), d(beta).
 #include <type_traits>
 
 #include "common.h"
 #include "split.h"
+#include "stk_adagn.h"
 
 namespace {
 
@@ -44,6 +49,7 @@ struct GnArgs {
   int N, HW, G, cpg;
   int act; float drop_p; float keep_scale; unsigned drop_thr;     // drop_thr = stk_drop_threshold(drop_p)
   unsigned long long seed; const unsigned long long* seed_dev;
+  const float* mod; int mod_stride;      // the MOD kernels only (include/stk_adagn.h): per-sample (scale, shift) rows
 };
 
 // optional by-products of the flat backward kernel (stk_gn_bwd_out_f32); all NULL = none
@@ -79,6 +85,25 @@ __device__ __forceinline__ void group_segments(const GnArgs& a, int n, int g, Se
 // Channel c of sample n in the (never materialised) concat: its HW run in x1 or x2
 __device__ __forceinline__ const float* gn_chan(const GnArgs& a, int n, int c) {
   return c < a.C1 ? a.x1 + ((long)n * a.C1 + c) * a.HW : a.x2 + ((long)n * a.C2 + (c - a.C1)) * a.HW;
+}
+// The affine pair of channel c of sample n.  MOD (include/stk_adagn.h): the layer's own pair modulated by the sample's row of
+// `mod`, gamma' = gamma (1 + s), beta' = beta (1 + s) + b -- per sample the modulated layer IS a GroupNorm with (gamma', beta'),
+// so every element body below serves it unchanged.  s = b = 0 returns (gamma, beta) bit for bit.
+template <bool MOD>
+__device__ __forceinline__ void gn_affine(const GnArgs& a, int n, int c, float& ga, float& be) {
+  ga = a.gamma[c]; be = a.beta[c];
+  if (MOD) {
+    const float* m = a.mod + (long)n * a.mod_stride;
+    const float s1 = 1.f + m[c];
+    ga *= s1;
+    be = be * s1 + m[a.C1 + a.C2 + c];
+  }
+}
+template <bool MOD>
+__device__ __forceinline__ float gn_gamma(const GnArgs& a, int n, int c) {
+  float ga, be;
+  gn_affine<MOD>(a, n, c, ga, be);
+  return ga;
 }
 // dx = ob * dx + r for one float4 of a gradient (ob == 0 never reads dx): r += ob * (what is there); the caller stores
 __device__ __forceinline__ void gn_dx_accum(float (&r)[4], float ob, const float4* dx) {
@@ -251,7 +276,7 @@ __device__ __forceinline__ void gn_stats_regs(const float4 (&v)[NITEMS], int L4,
 // Register-resident forward for groups of up to 16384 elements (every group of the 32x32 / 64x64 networks): a thread
 // keeps its <= 4 float4 of the group, so the group is read ONCE (the looping kernel below reads it for the statistics
 // and again for the normalisation; measured 1.6x the tensor at the memory side).  Same arithmetic as gn_fwd_kernel.
-template <int IPT>
+template <int IPT, bool MOD = false>
 __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __restrict__ y, float* __restrict__ mean_out,
                                                            float* __restrict__ rstd_out, float eps) {
   __shared__ float red[48];
@@ -288,7 +313,8 @@ __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __re
     float4* o4 = reinterpret_cast<float4*>(y + ((long)n * C + c_first) * a.HW);
     const unsigned long long flat0 = ((unsigned long long)n * C + c_first) * a.HW;
     const int c = c_first + (i * 4) / a.HW;
-    const float ga = a.gamma[c], be = a.beta[c];
+    float ga, be;
+    gn_affine<MOD>(a, n, c, ga, be);
     float r[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
     gn_out4(a, r, mean, rstd, ga, be, seed, flat0 + (unsigned long long)(i * 4));
     o4[i] = make_float4(r[0], r[1], r[2], r[3]);
@@ -296,7 +322,7 @@ __global__ __launch_bounds__(1024) void gn_fwd_flat_kernel(GnArgs a, float* __re
 }
 
 // VEC: 4 when HW % 4 == 0 and all pointers are 16-B aligned, else 1.
-template <int VEC>
+template <int VEC, bool MOD = false>
 __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict__ y, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, float eps) {
   __shared__ float red0[4], red[16];
@@ -367,7 +393,8 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict
       float4* o4 = reinterpret_cast<float4*>(o);
       for (int i = threadIdx.x; i < (len >> 2); i += 256) {
         const int c = seg[q].c_first + (i * 4) / a.HW;
-        const float ga = a.gamma[c], be = a.beta[c];
+        float ga, be;
+        gn_affine<MOD>(a, n, c, ga, be);
         const float4 v = p4[i];
         float r[4] = {v.x, v.y, v.z, v.w};
         gn_out4(a, r, mean, rstd, ga, be, seed, flat0 + (unsigned long long)(i * 4));
@@ -376,7 +403,9 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a, float* __restrict
     } else {
       for (int i = threadIdx.x; i < len; i += 256) {
         const int c = seg[q].c_first + i / a.HW;
-        float t = gn_act_out(a, p[i], mean, rstd, a.gamma[c], a.beta[c]);
+        float ga, be;
+        gn_affine<MOD>(a, n, c, ga, be);
+        float t = gn_act_out(a, p[i], mean, rstd, ga, be);
         if (a.drop_p > 0.f) t = stk_keep(seed, flat0 + (unsigned long long)i, a.drop_thr) ? t * a.keep_scale : 0.f;
         o[i] = t;
       }
@@ -415,6 +444,7 @@ __device__ __forceinline__ float gn_du(const GnArgs& a, float xv, float dyv, flo
   return go;
 }
 
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void gn_bwd_kernel(GnArgs a, const float* __restrict__ dy,
                                                      const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                                                      float* __restrict__ dx1, float beta1, float* __restrict__ dx2,
@@ -432,7 +462,8 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnArgs a, const float* __re
     const float* xp = c < a.C1 ? a.x1 + ((long)n * a.C1 + c) * a.HW : a.x2 + ((long)n * a.C2 + (c - a.C1)) * a.HW;
     const float* dp = dy + ((long)n * C + c) * a.HW;
     const unsigned long long flat0 = ((unsigned long long)n * C + c) * a.HW;
-    const float ga = a.gamma[c], be = a.beta[c];
+    float ga, be;
+    gn_affine<MOD>(a, n, c, ga, be);
     float cs[2] = {0.f, 0.f};
     for (int i = threadIdx.x; i < a.HW; i += 256) {
       float xhat;
@@ -467,7 +498,8 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnArgs a, const float* __re
     if (!op) continue;
     const float* dp = dy + ((long)n * C + c) * a.HW;
     const unsigned long long flat0 = ((unsigned long long)n * C + c) * a.HW;
-    const float ga = a.gamma[c], be = a.beta[c];
+    float ga, be;
+    gn_affine<MOD>(a, n, c, ga, be);
     for (int i = threadIdx.x; i < a.HW; i += 256) {
       float xhat;
       const float du = gn_du(a, xp[i], dp[i], mean, rstd, ga, be, seed, flat0 + i, xhat);
@@ -483,7 +515,7 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnArgs a, const float* __re
 // (algorithmic traffic: read x, read dy, write dx).  Per-channel sums come from a segmented wave reduction (a wave
 // covers one channel or 64/(HW/4) whole channels) written to fixed LDS slots and folded in slot order -- no
 // atomics, so results are reproducible.  blockDim = 64/128/256 so small groups do not idle lanes.
-template <int IPT, bool WANT>
+template <int IPT, bool WANT, bool MOD = false>
 __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float* __restrict__ dy,
                                                           const float* __restrict__ mean_in,
                                                           const float* __restrict__ rstd_in, float* __restrict__ dx1,
@@ -513,7 +545,8 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
     const unsigned long long flat = ((((unsigned long long)n * C + c)) << hw_log2) + off;
     const float4 xv = *reinterpret_cast<const float4*>(xp);
     const float4 dv = *reinterpret_cast<const float4*>(dy + flat);
-    const float ga = a.gamma[c], be = a.beta[c];
+    float ga, be;
+    gn_affine<MOD>(a, n, c, ga, be);
     gam[k] = ga;
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
     float cs0 = 0.f, cs1 = 0.f;
@@ -549,7 +582,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_flat_kernel(GnArgs a, const float
   __syncthreads();
   float g0 = 0.f, g1 = 0.f;
   for (int cl = 0; cl < a.cpg; ++cl) {
-    const float ga = a.gamma[c0 + cl];
+    const float ga = gn_gamma<MOD>(a, n, c0 + cl);
     g0 += ga * s_ch[2 * cl];
     g1 += ga * s_ch[2 * cl + 1];
   }
@@ -648,6 +681,7 @@ __device__ __forceinline__ void gn_fold_chunks(const float* __restrict__ part, l
   rstd = 1.f / sqrtf(var + eps);
 }
 
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float* __restrict__ part, int Sc,
                                                            float* __restrict__ y, float* __restrict__ mean_out,
                                                            float* __restrict__ rstd_out, float eps) {
@@ -662,7 +696,8 @@ __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float
   gn_fold_chunks(part, ((long)n * C + g * a.cpg) * Sc, a.cpg * Sc, eps, red0, red, mean, rstd);
   if (threadIdx.x == 0 && k == 0 && c == g * a.cpg) { mean_out[n * a.G + g] = mean; rstd_out[n * a.G + g] = rstd; }
   const unsigned long long seed = gn_seed(a);
-  const float ga = a.gamma[c], be = a.beta[c];
+  float ga, be;
+  gn_affine<MOD>(a, n, c, ga, be);
   const long coff = (long)k * GN_CHUNK;
   const float4* p4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
   float4* o4 = reinterpret_cast<float4*>(y + ((long)n * C + c) * a.HW + coff);
@@ -678,6 +713,7 @@ __global__ __launch_bounds__(256) void gn_split_fwd_kernel(GnArgs a, const float
 }
 
 // backward partials of one chunk: sum du, sum du * xhat
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void gn_split_bwd_part_kernel(GnArgs a, const float* __restrict__ dy,
                                                                 const float* __restrict__ mean_in,
                                                                 const float* __restrict__ rstd_in,
@@ -687,7 +723,8 @@ __global__ __launch_bounds__(256) void gn_split_bwd_part_kernel(GnArgs a, const 
   const int C = a.C1 + a.C2, n = nc / C, c = nc - n * C, g = c / a.cpg;
   const float mean = mean_in[n * a.G + g], rstd = rstd_in[n * a.G + g];
   const unsigned long long seed = gn_seed(a);
-  const float ga = a.gamma[c], be = a.beta[c];
+  float ga, be;
+  gn_affine<MOD>(a, n, c, ga, be);
   const long coff = (long)k * GN_CHUNK;
   const float4* x4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
   const float4* d4 = reinterpret_cast<const float4*>(dy + ((long)n * C + c) * a.HW + coff);
@@ -710,6 +747,7 @@ __global__ __launch_bounds__(256) void gn_split_bwd_part_kernel(GnArgs a, const 
   if (threadIdx.x == 0) { part[(long)blockIdx.x * 2] = s[0]; part[(long)blockIdx.x * 2 + 1] = s[1]; }
 }
 
+template <bool MOD = false>
 __global__ __launch_bounds__(256) void gn_split_bwd_kernel(GnArgs a, const float* __restrict__ dy,
                                                            const float* __restrict__ mean_in,
                                                            const float* __restrict__ rstd_in, const float* __restrict__ part,
@@ -724,7 +762,7 @@ __global__ __launch_bounds__(256) void gn_split_bwd_kernel(GnArgs a, const float
   float s[2] = {0.f, 0.f};
   const long pbase = ((long)n * C + g * a.cpg) * Sc;
   for (int i = threadIdx.x; i < a.cpg * Sc; i += 256) {
-    const float gc = a.gamma[g * a.cpg + i / Sc];
+    const float gc = gn_gamma<MOD>(a, n, g * a.cpg + i / Sc);
     s[0] += gc * part[(pbase + i) * 2];
     s[1] += gc * part[(pbase + i) * 2 + 1];
   }
@@ -743,7 +781,8 @@ __global__ __launch_bounds__(256) void gn_split_bwd_kernel(GnArgs a, const float
   else { op = dx2 ? dx2 + ((long)n * a.C2 + (c - a.C1)) * a.HW : nullptr; ob = beta2; }
   if (!op) return;
   const unsigned long long seed = gn_seed(a);
-  const float ga = a.gamma[c], be = a.beta[c];
+  float ga, be;
+  gn_affine<MOD>(a, n, c, ga, be);
   const long coff = (long)k * GN_CHUNK;
   const float4* x4 = reinterpret_cast<const float4*>(gn_chan(a, n, c) + coff);
   const float4* d4 = reinterpret_cast<const float4*>(dy + ((long)n * C + c) * a.HW + coff);
@@ -790,6 +829,43 @@ __global__ __launch_bounds__(256) void gn_param_grad_kernel(const float* __restr
       sb += v.x;
       sg += v.y;
     }
+  redb[threadIdx.x] = sb;
+  redg[threadIdx.x] = sg;
+  __syncthreads();
+  if (part == 0 && c < C) {
+    float tb = 0.f, tg = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { tb += redb[q * 32 + cl]; tg += redg[q * 32 + cl]; }
+    if (dgamma) dgamma[c] += tg;
+    if (dbeta) dbeta[c] += tb;
+  }
+}
+
+// The fold of the modulated layer (include/stk_adagn.h) over the same [N][C][2] sums, which for it are d(beta')[n,c] and
+// d(gamma')[n,c]:  dmod[n][c] = dgamma' gamma + dbeta' beta,  dmod[n][C + c] = dbeta'  (written, row stride mod_stride),
+// dgamma[c] += sum_n dgamma' (1 + s),  dbeta[c] += sum_n dbeta' (1 + s).  The geometry and the summation order of
+// gn_param_grad_kernel: 32 channels per block, n in 8 interleaved runs, folded in run order.
+__global__ __launch_bounds__(256) void gn_mod_fold_kernel(const float* __restrict__ ws, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ mod,
+                                                          int mod_stride, float* __restrict__ dmod, float* __restrict__ dgamma,
+                                                          float* __restrict__ dbeta, int N, int C) {
+  __shared__ float redb[256], redg[256];
+  const int cl = threadIdx.x & 31, part = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + cl;
+  float sb = 0.f, sg = 0.f;
+  if (c < C) {
+    const float ga = gamma[c], be = beta[c];
+    for (int n = part; n < N; n += 8) {
+      const float2 v = *reinterpret_cast<const float2*>(ws + ((long)n * C + c) * 2);
+      const float s1 = 1.f + mod[(long)n * mod_stride + c];
+      if (dmod) {
+        dmod[(long)n * mod_stride + c] = v.y * ga + v.x * be;
+        dmod[(long)n * mod_stride + C + c] = v.x;
+      }
+      sb += v.x * s1;
+      sg += v.y * s1;
+    }
+  }
   redb[threadIdx.x] = sb;
   redg[threadIdx.x] = sg;
   __syncthreads();
@@ -1148,6 +1224,7 @@ static inline GnArgs gn_args(const float* x1, int C1, const float* x2, int C2, c
   a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.gamma = gamma; a.beta = beta;
   a.N = N; a.HW = HW; a.G = G; a.cpg = (C1 + C2) / G; a.act = act; a.drop_p = drop_p; a.keep_scale = 1.f / (1.f - drop_p); a.drop_thr = stk_drop_threshold(drop_p);
   a.seed = seed; a.seed_dev = seed_dev;
+  a.mod = nullptr; a.mod_stride = 0;
   return a;
 }
 
@@ -1167,6 +1244,77 @@ static inline void gn_pick(int n, F&& f) {
   else gn_pick<Rest...>(n, f);
 }
 
+/* The forward of the checked arguments `a`: one routing for the plain layer and the modulated one (MOD, a.mod set). */
+template <bool MOD>
+static int gn_fwd_launch(const GnArgs& a, float* y, float* mean, float* rstd, float eps, float* ws, hipStream_t s) {
+  const int C = a.C1 + a.C2, N = a.N, HW = a.HW, G = a.G;
+  const bool vec = (HW & 3) == 0 && stk_aligned16(a.x1) && stk_aligned16(y) && (!a.x2 || stk_aligned16(a.x2));
+  if (ws && vec && gn_split_ok(HW, a.cpg)) {
+    const int Sc = HW / GN_CHUNK;
+    const dim3 grid((unsigned)((long)N * C * Sc));
+    hipLaunchKernelGGL(gn_split_stats_kernel, grid, dim3(256), 0, s, a, ws, Sc);
+    STK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gn_split_fwd_kernel<MOD>, grid, dim3(256), 0, s, a, ws, Sc, y, mean, rstd, eps);
+    STK_CHECK_LAUNCH();
+    return STK_OK;
+  }
+  const long L = (long)a.cpg * HW;
+  if (vec && L <= 16384) {
+    const int L4 = (int)(L >> 2);
+    int T = 64;
+    while (T < 1024 && T * 4 < L4) T <<= 1;
+    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
+      hipLaunchKernelGGL((gn_fwd_flat_kernel<decltype(ipt)::value, MOD>), dim3(N * G), dim3(T), 0, s, a, y, mean, rstd, eps);
+    });
+  } else if (vec)
+    hipLaunchKernelGGL((gn_fwd_kernel<4, MOD>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
+  else
+    hipLaunchKernelGGL((gn_fwd_kernel<1, MOD>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
+/* The backward up to the per-(sample, channel) sums in ws[N][C][2] and dx: one routing for the plain layer and the
+ * modulated one (MOD, a.mod set; it has no by-products). */
+template <bool MOD>
+static int gn_bwd_launch(const GnArgs& a, const float* dy, const float* mean, const float* rstd, float* dx1, float dx1_beta,
+                         float* dx2, float dx2_beta, float* ws, hipStream_t s, const GnBwdOut& out) {
+  const int C = a.C1 + a.C2, N = a.N, HW = a.HW, G = a.G;
+  const float* x1 = a.x1;
+  const float* x2 = a.x2;
+  const long L = (long)a.cpg * HW;
+  int hw_log2 = 0;
+  while ((1 << hw_log2) < HW) ++hw_log2;
+  const bool al16 = stk_aligned16(x1) && stk_aligned16(dy) && (!x2 || stk_aligned16(x2)) && (!dx1 || stk_aligned16(dx1)) &&
+                    (!dx2 || stk_aligned16(dx2));
+  const bool flat = al16 && (1 << hw_log2) == HW && HW >= 16 && L <= 16384 && a.cpg <= 512;
+  if (al16 && gn_split_ok(HW, a.cpg)) {
+    const int Sc = HW / GN_CHUNK;
+    float* part = ws + 2L * N * C;                       // after the [N][C][2] channel sums
+    const dim3 grid((unsigned)((long)N * C * Sc));
+    hipLaunchKernelGGL(gn_split_bwd_part_kernel<MOD>, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc);
+    STK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gn_split_bwd_kernel<MOD>, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc, dx1, dx1_beta, dx2, dx2_beta, ws);
+  } else if (flat) {
+    const int L4 = (int)(L >> 2);
+    const int tgt = 4;          // float4 per thread (measured best of 1..4 on the 32x32 / 16x16 layers)
+    int T = 64;
+    while (T < 1024 && T * tgt < L4) T <<= 1;
+    const bool want = out.sum || out.temb || out.amax || out.add;
+    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
+      constexpr int IPT = decltype(ipt)::value;
+      auto kernel = gn_bwd_flat_kernel<IPT, false, MOD>;
+      if constexpr (!MOD)
+        if (want) kernel = gn_bwd_flat_kernel<IPT, true, false>;
+      hipLaunchKernelGGL(kernel, dim3(N * G), dim3(T), 0, s, a, dy, mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws, hw_log2, out);
+    });
+  } else {
+    hipLaunchKernelGGL(gn_bwd_kernel<MOD>, dim3(N * G), dim3(256), 0, s, a, dy, mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws);
+  }
+  STK_CHECK_LAUNCH();
+  return STK_OK;
+}
+
 extern "C" {
 
 int stk_gn_bound_f32(const float* gamma, const float* beta, int C, int G, int HW, float drop_p, float* rec, void* stream) {
@@ -1181,33 +1329,8 @@ int stk_gn_fwd_f32(const float* x1, int C1, const float* x2, int C2, const float
                    float* mean, float* rstd, int N, int HW, int G, float eps, int act, float drop_p,
                    unsigned long long seed, const unsigned long long* seed_dev, float* ws, void* stream) {
   if (!y || !mean || !rstd || !gn_check_common(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p)) return STK_EINVAL;
-  const int C = C1 + C2;
-  const GnArgs a = gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = (HW & 3) == 0 && stk_aligned16(x1) && stk_aligned16(y) && (!x2 || stk_aligned16(x2));
-  if (ws && vec && gn_split_ok(HW, a.cpg)) {
-    const int Sc = HW / GN_CHUNK;
-    const dim3 grid((unsigned)((long)N * C * Sc));
-    hipLaunchKernelGGL(gn_split_stats_kernel, grid, dim3(256), 0, s, a, ws, Sc);
-    STK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_split_fwd_kernel, grid, dim3(256), 0, s, a, ws, Sc, y, mean, rstd, eps);
-    STK_CHECK_LAUNCH();
-    return STK_OK;
-  }
-  const long L = (long)a.cpg * HW;
-  if (vec && L <= 16384) {
-    const int L4 = (int)(L >> 2);
-    int T = 64;
-    while (T < 1024 && T * 4 < L4) T <<= 1;
-    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
-      hipLaunchKernelGGL((gn_fwd_flat_kernel<decltype(ipt)::value>), dim3(N * G), dim3(T), 0, s, a, y, mean, rstd, eps);
-    });
-  } else if (vec)
-    hipLaunchKernelGGL((gn_fwd_kernel<4>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
-  else
-    hipLaunchKernelGGL((gn_fwd_kernel<1>), dim3(N * G), dim3(256), 0, s, a, y, mean, rstd, eps);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  return gn_fwd_launch<false>(gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev), y, mean, rstd, eps, ws,
+                              (hipStream_t)stream);
 }
 
 /* = stk_gn_fwd_f32 (y may be NULL when no consumer reads the fp32 copy) + stk_gn_bound_f32 (rec) +
@@ -1299,36 +1422,10 @@ static int gn_bwd_impl(const float* dy, const float* x1, int C1, const float* x2
                        unsigned long long seed, const unsigned long long* seed_dev, void* stream, GnBwdOut out) {
   if (!dy || !mean || !rstd || !ws || !gn_check_common(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p)) return STK_EINVAL;
   const int C = C1 + C2;
-  const GnArgs a = gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
   hipStream_t s = (hipStream_t)stream;
-  const long L = (long)a.cpg * HW;
-  int hw_log2 = 0;
-  while ((1 << hw_log2) < HW) ++hw_log2;
-  const bool al16 = stk_aligned16(x1) && stk_aligned16(dy) && (!x2 || stk_aligned16(x2)) && (!dx1 || stk_aligned16(dx1)) &&
-                    (!dx2 || stk_aligned16(dx2));
-  const bool flat = al16 && (1 << hw_log2) == HW && HW >= 16 && L <= 16384 && a.cpg <= 512;
-  if (al16 && gn_split_ok(HW, a.cpg)) {
-    const int Sc = HW / GN_CHUNK;
-    float* part = ws + 2L * N * C;                       // after the [N][C][2] channel sums
-    const dim3 grid((unsigned)((long)N * C * Sc));
-    hipLaunchKernelGGL(gn_split_bwd_part_kernel, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc);
-    STK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_split_bwd_kernel, grid, dim3(256), 0, s, a, dy, mean, rstd, part, Sc, dx1, dx1_beta, dx2, dx2_beta, ws);
-  } else if (flat) {
-    const int L4 = (int)(L >> 2);
-    const int tgt = 4;          // float4 per thread (measured best of 1..4 on the 32x32 / 16x16 layers)
-    int T = 64;
-    while (T < 1024 && T * tgt < L4) T <<= 1;
-    const bool want = out.sum || out.temb || out.amax || out.add;
-    gn_pick<1, 2, 3, 4>(stk_cdiv(L4, T), [&](auto ipt) {
-      constexpr int IPT = decltype(ipt)::value;
-      hipLaunchKernelGGL((want ? gn_bwd_flat_kernel<IPT, true> : gn_bwd_flat_kernel<IPT, false>), dim3(N * G), dim3(T), 0, s, a, dy,
-                         mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws, hw_log2, out);
-    });
-  } else {
-    hipLaunchKernelGGL(gn_bwd_kernel, dim3(N * G), dim3(256), 0, s, a, dy, mean, rstd, dx1, dx1_beta, dx2, dx2_beta, ws);
-  }
-  STK_CHECK_LAUNCH();
+  const int rc = gn_bwd_launch<false>(gn_args(x1, C1, x2, C2, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev), dy, mean, rstd,
+                                      dx1, dx1_beta, dx2, dx2_beta, ws, s, out);
+  if (rc) return rc;
   if (dgamma || dbeta) {
     hipLaunchKernelGGL(gn_param_grad_kernel, dim3(stk_cdiv(C, 32)), dim3(256), 0, s, ws, dgamma, dbeta, N, C,
                        (const StkGnFoldDesc*)nullptr);
@@ -1373,6 +1470,48 @@ long stk_gn_ws_bytes(int N, int C, int HW, int G) {
   long f = 2L * N * C;                                   // backward: per-(sample, channel) sums
   if (gn_split_ok(HW, C / G)) f += 2L * N * C * (HW / GN_CHUNK);     // per-chunk partials (forward and backward)
   return f * 4;
+}
+
+/* ---- include/stk_adagn.h: GroupNorm whose affine part is modulated per sample (single source) ---- */
+int stk_gn_mod_ok(int C, int HW, int G) { return C > 0 && HW > 0 && G > 0 && C % G == 0 ? 1 : 0; }
+
+long stk_gn_mod_ws_bytes(int N, int C, int HW, int G) { return stk_gn_ws_bytes(N, C, HW, G); }
+
+static inline GnArgs gn_mod_args(const float* x, const float* gamma, const float* beta, const float* mod, int mod_stride, int N,
+                                 int C, int HW, int G, int act, float drop_p, unsigned long long seed,
+                                 const unsigned long long* seed_dev) {
+  GnArgs a = gn_args(x, C, nullptr, 0, gamma, beta, N, HW, G, act, drop_p, seed, seed_dev);
+  a.mod = mod; a.mod_stride = mod_stride;
+  return a;
+}
+
+int stk_gn_mod_fwd_f32(const float* x, const float* gamma, const float* beta, const float* mod, int mod_stride, float* y,
+                       float* mean, float* rstd, int N, int C, int HW, int G, float eps, int act, float drop_p,
+                       unsigned long long seed, const unsigned long long* seed_dev, float* ws, void* stream) {
+  if (!y || !mean || !rstd || !mod || mod_stride < 2 * C || !gn_check_common(x, C, nullptr, 0, gamma, beta, N, HW, G, act, drop_p))
+    return STK_EINVAL;
+  return gn_fwd_launch<true>(gn_mod_args(x, gamma, beta, mod, mod_stride, N, C, HW, G, act, drop_p, seed, seed_dev), y, mean, rstd,
+                             eps, ws, (hipStream_t)stream);
+}
+
+int stk_gn_mod_bwd_f32(const float* dy, const float* x, const float* gamma, const float* beta, const float* mod, int mod_stride,
+                       const float* mean, const float* rstd, float* dx, float dx_beta, float* dmod, float* dgamma, float* dbeta,
+                       float* ws, int N, int C, int HW, int G, int act, float drop_p, unsigned long long seed,
+                       const unsigned long long* seed_dev, void* stream) {
+  if (!dy || !mean || !rstd || !ws || !mod || mod_stride < 2 * C ||
+      !gn_check_common(x, C, nullptr, 0, gamma, beta, N, HW, G, act, drop_p))
+    return STK_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const GnBwdOut none = {nullptr, nullptr, 0, 1.f, nullptr, nullptr, 0.f};
+  const int rc = gn_bwd_launch<true>(gn_mod_args(x, gamma, beta, mod, mod_stride, N, C, HW, G, act, drop_p, seed, seed_dev), dy, mean,
+                                     rstd, dx, dx_beta, nullptr, 0.f, ws, s, none);
+  if (rc) return rc;
+  if (dmod || dgamma || dbeta) {
+    hipLaunchKernelGGL(gn_mod_fold_kernel, dim3(stk_cdiv(C, 32)), dim3(256), 0, s, ws, gamma, beta, mod, mod_stride, dmod, dgamma,
+                       dbeta, N, C);
+    STK_CHECK_LAUNCH();
+  }
+  return STK_OK;
 }
 
 }  // extern "C"

@@ -298,6 +298,57 @@ class GroupNormAct(Op):
     return max(int(lib.gn_ws_bytes(self.N, self.C1 + self.C2, self.HW, self.G)), 4 * 2 * self.N * (self.C1 + self.C2))
 
 
+class GroupNormMod(Op):
+  """y = dropout(act(GroupNorm(x) * (1 + scale) + shift)) with scale = mod[:, col : col + C] and shift = mod[:, col + C :
+  col + 2 C] of the stacked conditioning projection -- the second normalisation of a residual block under
+  config.model.scale_shift_norm (include/stk_adagn.h).  Only the product library has the kernels: on any other the operation
+  is refused here, when the graph is planned.  To the plan passes that look for GroupNormAct this is an ordinary fp32
+  producer and consumer: its output is fp32 (the convolution behind it makes its own planes, measured scale), it leaves no
+  by-products for the convolution in front of it, and it folds its own parameter gradients.  The backward WRITES d(mod) at
+  this layer's 2 C columns of the projection's gradient (one writer per column, as the time-embedding gradient of a
+  convolution), in the input-only backward (Runtime.param_grads) too: `mod` is an activation, and in a stand-alone block it
+  descends from the differentiable input temb, whose gradient has no other source.  That backward skips dgamma and dbeta."""
+
+  def __init__(self, g, x, gamma, beta_t, mod, mod_col, groups, eps, act, drop_p, name):
+    lib = g.lib
+    if not getattr(lib, 'has_adagn', False):
+      raise NotImplementedError(f'backend {getattr(lib, "backend", None)} does not export include/stk_adagn.h: no kernel '
+                                f'evaluates the scale-shift GroupNorm of config.model.scale_shift_norm')
+    self.x, self.gamma, self.beta_t, self.mod, self.mod_col = x, gamma, beta_t, mod, int(mod_col)
+    N, C, H, W = x.shape
+    self.N, self.C, self.HW, self.G = N, C, H * W, groups
+    self.mod_stride = mod.shape[1]
+    if mod.shape[0] != N or self.mod_col < 0 or self.mod_col + 2 * C > self.mod_stride or not int(lib.gn_mod_ok(C, H * W, groups)):
+      raise RuntimeError(f'{name}: columns {mod_col} .. {mod_col + 2 * C} of a projection {tuple(mod.shape)} do not modulate '
+                         f'{C} channels in {groups} groups of a batch of {N}')
+    self.eps, self.act, self.drop_p = eps, int(act), float(drop_p)
+    self.y = g.new((N, C, H, W), name=name)
+    self.mean = g.new((N * groups,), needs_grad=False, name=name + '.mean')
+    self.rstd = g.new((N * groups,), needs_grad=False, name=name + '.rstd')
+    self.inputs = (x,)
+    self.op_id = g.next_id()
+
+  def _tail(self, rt):
+    return (self.N, self.C, self.HW, self.G), (self.act, self.drop_p if rt.training else 0.0,
+                                               (rt.seed + 0x9E3779B1 * self.op_id) & 0xFFFFFFFFFFFFFFFF, rt.seed_dev)
+
+  def forward(self, rt):
+    dims, tail = self._tail(rt)
+    rt.lib.gn_mod_fwd_f32(rt.v(self.x), rt.v(self.gamma), rt.v(self.beta_t), rt.v(self.mod) + 4 * self.mod_col, self.mod_stride,
+                          rt.v(self.y), rt.v(self.mean), rt.v(self.rstd), *dims, self.eps, *tail, rt.ws, rt.stream)
+
+  def backward(self, rt):
+    dims, tail = self._tail(rt)
+    gmod = rt.g(self.mod)
+    rt.lib.gn_mod_bwd_f32(rt.g(self.y), rt.v(self.x), rt.v(self.gamma), rt.v(self.beta_t), rt.v(self.mod) + 4 * self.mod_col,
+                          self.mod_stride, rt.v(self.mean), rt.v(self.rstd), rt.g(self.x), self.b(self.x),
+                          gmod + 4 * self.mod_col if gmod is not None else None, rt.g(self.gamma), rt.g(self.beta_t), rt.ws,
+                          *dims, *tail, rt.stream)
+
+  def ws_bytes(self, lib):
+    return max(int(lib.gn_mod_ws_bytes(self.N, self.C, self.HW, self.G)), 4 * 2 * self.N * self.C)
+
+
 class Conv(Op):
   """y = (conv(cat(x1,x2), w) + bias + temb[:, col:col+Cout] + res) / out_div.
 
@@ -1259,6 +1310,12 @@ class Graph:
 
   def gn_act(self, x1, x2, gn, act=True, drop_p=0.0, name='gn'):
     op = GroupNormAct(self, x1, x2, self.param(gn.weight), self.param(gn.bias), gn.num_groups, gn.eps,
+                      self.act_code if act else 0, drop_p, name)
+    return self.add(op)
+
+  def gn_mod(self, x, gn, mod, mod_col, act=True, drop_p=0.0, name='gn'):
+    """gn_act on one source, modulated by columns mod_col .. mod_col + 2 C of the projection `mod` (GroupNormMod)."""
+    op = GroupNormMod(self, x, self.param(gn.weight), self.param(gn.bias), mod, mod_col, gn.num_groups, gn.eps,
                       self.act_code if act else 0, drop_p, name)
     return self.add(op)
 

@@ -194,6 +194,15 @@ SIGNATURES_COND = {
   'stk_class_embed_bwd_f32': [P, P, P, F, P, I, I, I, S],
   'stk_cfg_combine_f32': [P, P, F, P, L, S],
 }
+# include/stk_adagn.h: GroupNorm modulated per sample by (scale, shift) columns of the conditioning projection
+# (engine.graph.GroupNormMod refuses to plan without it).
+SIGNATURES_ADAGN = {
+  'stk_gn_mod_ok': [I, I, I],
+  'stk_gn_mod_ws_bytes': [I, I, I, I],
+  'stk_gn_mod_fwd_f32': [P, P, P, P, I, P, P, P, I, I, I, I, F, I, F, U64, P, P, S],
+  'stk_gn_mod_bwd_f32': [P, P, P, P, P, I, P, P, P, F, P, P, P, P, I, I, I, I, I, F, U64, P, S],
+}
+_NO_CHECK_ADAGN = {'stk_gn_mod_ws_bytes', 'stk_gn_mod_ok'}                       # its queries
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -216,6 +225,7 @@ OPTIONAL_HEADERS = (
   Header('has_superres', 'include/stk_superres.h', SIGNATURES_SUPERRES, {}, ()),
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
+  Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,

@@ -6,7 +6,8 @@ the engine graph with ``emit``: GroupNorm+SiLU(+dropout) is one fused kernel, th
 the bias / time-embedding / residual / (1/sqrt 2) epilogues, channel concatenation is never
 materialised (GroupNorm and the convs read two sources), and the 46 ``Dense_0`` projections are
 evaluated as one GEMM by the caller (``temb`` below is that shared [B, sum Cout] tensor plus this
-block's column offset).
+block's column offset; with ``scale_shift_norm`` a block owns 2 Cout columns of it, the (scale, shift) that
+modulate its GroupNorm_1 instead of a bias in Conv_0's epilogue).
 
 Called on their own (``forward``), the blocks plan the same ``emit`` as a graph of their own and run it on the same kernels
 (engine/executor.ModuleExecutor); a residual block's ``temb`` then goes through its own Dense_0.
@@ -31,13 +32,34 @@ EagerBlock = layers.EagerBlock
 
 
 def _emit_res_eager(blk, g, x, temb=None):
-  """A residual block on its own: ``temb`` [B, temb_dim] goes through act -> Dense_0 into Conv_0's epilogue (column 0 of
-  its own [B, out_ch] projection) instead of the model's stacked projection of all blocks."""
+  """A residual block on its own: ``temb`` [B, temb_dim] goes through act -> Dense_0 into column 0 of the block's own
+  projection instead of the model's stacked projection of all blocks: [B, out_ch] added by Conv_0's epilogue, or with
+  ``scale_shift_norm`` [B, 2 out_ch], the (scale, shift) of GroupNorm_1 (_emit_conv0_norm1)."""
   g.act_code = layers.act_code_of(blk.act)
   proj = None
   if temb is not None:
     proj = g.linear(g.silu(temb, name='temb.act'), blk.Dense_0.weight, blk.Dense_0.bias, name='temb.dense')
   return blk.emit(g, x, None, proj, 0)
+
+
+def _emit_conv0_norm1(blk, g, h, temb, temb_col, name):
+  """Conv_0 -> GroupNorm_1 + act + Dropout_0 of a residual block, with the block's columns of the conditioning projection:
+  added by Conv_0's epilogue (the reference), or, under ``scale_shift_norm``, as the (scale, shift) that modulate GroupNorm_1
+  -- h = GroupNorm_1(h) * (1 + scale) + shift, scale in the first out_ch columns and shift in the next (absent from the
+  reference; ADM's use_scale_shift_norm)."""
+  if not blk.scale_shift_norm:
+    h = layers.conv_emit(g, blk.Conv_0, h, temb=temb, temb_col=temb_col, name=name + '.conv0')
+    return g.gn_act(h, None, blk.GroupNorm_1, act=True, drop_p=blk.Dropout_0.p, name=name + '.gn1')
+  if temb is None:
+    raise ValueError(f'{name}: scale_shift_norm modulates GroupNorm_1 by the conditioning vector and needs temb')
+  h = layers.conv_emit(g, blk.Conv_0, h, name=name + '.conv0')
+  return g.gn_mod(h, blk.GroupNorm_1, temb, temb_col, act=True, drop_p=blk.Dropout_0.p, name=name + '.gn1')
+
+
+def _check_ssn(scale_shift_norm, temb_dim):
+  if scale_shift_norm and temb_dim is None:
+    raise ValueError('scale_shift_norm modulates GroupNorm_1 by the conditioning vector: the block needs temb_dim')
+  return bool(scale_shift_norm)
 
 
 class FixedFouriereProjection(EagerBlock, nn.Module):
@@ -225,13 +247,14 @@ class ResnetBlockDDPMpp(EagerBlock, nn.Module):
   """DDPM residual block (models/layerspp.py:179-222)."""
 
   def __init__(self, act, in_ch, out_ch=None, temb_dim=None, conv_shortcut=False, dropout=0.1,
-               skip_rescale=False, init_scale=0.):
+               skip_rescale=False, init_scale=0., scale_shift_norm=False):
     super().__init__()
     out_ch = out_ch if out_ch else in_ch
+    self.scale_shift_norm = _check_ssn(scale_shift_norm, temb_dim)
     self.GroupNorm_0 = nn.GroupNorm(num_groups=min(in_ch // 4, 32), num_channels=in_ch, eps=1e-6)
     self.Conv_0 = conv3x3(in_ch, out_ch)
     if temb_dim is not None:
-      self.Dense_0 = nn.Linear(temb_dim, out_ch)
+      self.Dense_0 = nn.Linear(temb_dim, 2 * out_ch if self.scale_shift_norm else out_ch)     # (scale, shift) | the bias
       self.Dense_0.weight.data = default_init()(self.Dense_0.weight.data.shape)
       nn.init.zeros_(self.Dense_0.bias)
     self.GroupNorm_1 = nn.GroupNorm(num_groups=min(out_ch // 4, 32), num_channels=out_ch, eps=1e-6)
@@ -250,8 +273,7 @@ class ResnetBlockDDPMpp(EagerBlock, nn.Module):
 
   def emit(self, g, x1, x2, temb, temb_col, name='res'):
     h = g.gn_act(x1, x2, self.GroupNorm_0, act=True, name=name + '.gn0')
-    h = layers.conv_emit(g, self.Conv_0, h, temb=temb, temb_col=temb_col, name=name + '.conv0')
-    h = g.gn_act(h, None, self.GroupNorm_1, act=True, drop_p=self.Dropout_0.p, name=name + '.gn1')
+    h = _emit_conv0_norm1(self, g, h, temb, temb_col, name)
     if self.in_ch != self.out_ch:
       if self.conv_shortcut:
         xs = layers.conv_emit(g, self.Conv_2, x1, x2, name=name + '.sc')
@@ -274,9 +296,10 @@ class ResnetBlockBigGANpp(EagerBlock, nn.Module):
   (models/layerspp.py:225-287)."""
 
   def __init__(self, act, in_ch, out_ch=None, temb_dim=None, up=False, down=False, dropout=0.1,
-               fir=False, fir_kernel=(1, 3, 3, 1), skip_rescale=True, init_scale=0.):
+               fir=False, fir_kernel=(1, 3, 3, 1), skip_rescale=True, init_scale=0., scale_shift_norm=False):
     super().__init__()
     out_ch = out_ch if out_ch else in_ch
+    self.scale_shift_norm = _check_ssn(scale_shift_norm, temb_dim)
     self.GroupNorm_0 = nn.GroupNorm(num_groups=min(in_ch // 4, 32), num_channels=in_ch, eps=1e-6)
     self.up = up
     self.down = down
@@ -284,7 +307,7 @@ class ResnetBlockBigGANpp(EagerBlock, nn.Module):
     self.fir_kernel = fir_kernel
     self.Conv_0 = conv3x3(in_ch, out_ch)
     if temb_dim is not None:
-      self.Dense_0 = nn.Linear(temb_dim, out_ch)
+      self.Dense_0 = nn.Linear(temb_dim, 2 * out_ch if self.scale_shift_norm else out_ch)     # (scale, shift) | the bias
       self.Dense_0.weight.data = default_init()(self.Dense_0.weight.shape)
       nn.init.zeros_(self.Dense_0.bias)
     self.GroupNorm_1 = nn.GroupNorm(num_groups=min(out_ch // 4, 32), num_channels=out_ch, eps=1e-6)
@@ -309,8 +332,7 @@ class ResnetBlockBigGANpp(EagerBlock, nn.Module):
           else (lambda t, n: uds.emit_naive_downsample_2d(g, t, name=n))
       h = r(h, name + '.rs_h')
       x1 = r(x1, name + '.rs_x')
-    h = layers.conv_emit(g, self.Conv_0, h, temb=temb, temb_col=temb_col, name=name + '.conv0')
-    h = g.gn_act(h, None, self.GroupNorm_1, act=True, drop_p=self.Dropout_0.p, name=name + '.gn1')
+    h = _emit_conv0_norm1(self, g, h, temb, temb_col, name)
     if self.in_ch != self.out_ch or self.up or self.down:
       xs = layers.conv_emit(g, self.Conv_2, x1, x2, name=name + '.sc')
     else:

@@ -73,6 +73,11 @@ class NCSNpp(nn.Module):
     if num_classes < 0 or (num_classes > 0 and not conditional):
       raise ValueError(f'config.model.num_classes = {num_classes} needs config.model.conditional (the class row is added to '
                        f'the time embedding) and must not be negative')
+    # scale-shift GroupNorm conditioning (absent from the reference): False = off, the network of the reference, key for key
+    self.scale_shift_norm = ssn = bool(utils.config_option(config, 'model', 'scale_shift_norm', False))
+    if ssn and not conditional:
+      raise ValueError('config.model.scale_shift_norm needs config.model.conditional (the residual blocks modulate their '
+                       'second GroupNorm by the time embedding)')
     fir = m.fir
     fir_kernel = m.fir_kernel
     self.skip_rescale = skip_rescale = m.skip_rescale
@@ -143,11 +148,11 @@ class NCSNpp(nn.Module):
 
     if resblock_type == 'ddpm':
       ResnetBlock = functools.partial(ResnetBlockDDPM, act=act, dropout=dropout, init_scale=init_scale,
-                                      skip_rescale=skip_rescale, temb_dim=embed_dim_2 * 4)
+                                      skip_rescale=skip_rescale, temb_dim=embed_dim_2 * 4, scale_shift_norm=ssn)
     elif resblock_type == 'biggan':
       ResnetBlock = functools.partial(ResnetBlockBigGAN, act=act, dropout=dropout, fir=fir,
                                       fir_kernel=fir_kernel, init_scale=init_scale,
-                                      skip_rescale=skip_rescale, temb_dim=embed_dim_2 * 4)
+                                      skip_rescale=skip_rescale, temb_dim=embed_dim_2 * 4, scale_shift_norm=ssn)
     else:
       raise ValueError(f'resblock type {resblock_type} unrecognized.')
     # ---- down path ----------------------------------------------------------------------------
