@@ -35,6 +35,36 @@ def within(got, want, mag, k, what, show=False):
   return units
 
 
+GUARD = 8                      # sentinel elements before and after a guarded view
+SENTINEL = {torch.float32: -1.5 * 2.0 ** 79, torch.float64: -1.5 * 2.0 ** 79, torch.float16: -1234.0, torch.uint8: 0xA5}
+ENTERED = {'aligned': 0, 'entered-one-in': 1, 'entered-two-in': 2}
+
+
+class Guarded:
+  """A fresh copy of t (a tensor or a numpy array) on dev with GUARD sentinel elements before and after it (bytes for a
+  uint8 tensor), placed 'aligned' (data_ptr % 16 == 0), 'entered-one-in' (% 16 == 4) or 'entered-two-in' (% 16 == 8; the
+  entered placements are float32's).  .view is the operand; .check() asserts that no sentinel was written."""
+
+  def __init__(self, t, dev, placement='aligned'):
+    if isinstance(t, np.ndarray):
+      t = torch.from_numpy(np.ascontiguousarray(t))
+    entered = ENTERED[placement]
+    assert entered == 0 or t.dtype == torch.float32, (placement, t.dtype)
+    self.lead, self.n = GUARD + entered, t.numel()
+    self.buf = torch.full((self.lead + self.n + GUARD,), SENTINEL[t.dtype], dtype=t.dtype, device=dev)
+    self.view = self.buf[self.lead:self.lead + self.n].view(t.shape)
+    self.view.copy_(t)
+    assert self.view.is_contiguous() and self.buf.data_ptr() % 16 == 0
+    if t.dtype == torch.float32:
+      assert self.view.data_ptr() % 16 == 4 * entered, (placement, self.view.data_ptr() % 16)
+
+  def check(self, what=''):
+    s = SENTINEL[self.buf.dtype]
+    before, after = self.buf[:self.lead].cpu(), self.buf[self.lead + self.n:].cpu()
+    assert bool((before == s).all()), f'{what}: written before the view: {before.tolist()}'
+    assert bool((after == s).all()), f'{what}: written past the view: {after.tolist()}'
+
+
 def case_id(v):
   """Parametrize id of a (shape, shifted) case: '2x3x8x8' for the shape, 'aligned' / 'entered-one-in' for the flag."""
   return 'x'.join(map(str, v)) if isinstance(v, tuple) else ('entered-one-in' if v else 'aligned')
