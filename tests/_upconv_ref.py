@@ -8,6 +8,10 @@ autograd of itself.
   out    (upfirdn2d(u, kf, pad) + bias + res) / out_div
   dx     dx[n,ci,i,j]    = sum_co,kh,kw w[co,ci,kh,kw] du[n,co,2i+(K-1)-kh,2j+(K-1)-kw]
   dw     dw[co,ci,kh,kw] = sum_n,i,j    x[n,ci,i,j]    du[n,co,2i+(K-1)-kh,2j+(K-1)-kw]      du = adjoint of the FIR on dout
+
+forward / grads derive the taps and the pad from a separable k as the model does; forward_taps / grads_taps take any KT x KT tap
+array and any pad0, as the C ABI does (pad1 implied by the 2H x 2W output): tests/_upconv_cases.py runs on those, and
+tests/test_upconv_cases_cpu.py pins them to the header's formulas.
 """
 import torch
 import torch.nn.functional as F
@@ -53,11 +57,15 @@ def fir_adjoint(dout, kf, pad, UH, UW):
   return F.conv2d(d, kf[None, None].repeat(C, 1, 1, 1).to(dout), groups=C)
 
 
-def forward(x, w, k=None, gain=1.0, bias=None, res=None, out_div=1.0):
-  """(out, u) in the dtype of x."""
-  kf, pad = taps_pad(k, w.shape[-1], gain, x.dtype)
+def pad_of(pad0, KT, K):
+  """(pad0, pad1) of the C ABI's single pad0: the output is 2H x 2W, so pad1 = 2H - UH - pad0 + KT - 1 (include/stk_upconv.h)."""
+  return pad0, KT + 1 - K - pad0
+
+
+def forward_taps(x, w, kf, pad0, bias=None, res=None, out_div=1.0):
+  """(out, u) for an arbitrary KT x KT tap array kf and an arbitrary pad0 (either pad may be negative: a crop)."""
   u = contraction(x, w)
-  out = fir(u, kf, pad)
+  out = fir(u, kf, pad_of(pad0, kf.shape[0], w.shape[-1]))
   if bias is not None:
     out = out + bias.reshape(1, -1, 1, 1)
   if res is not None:
@@ -65,12 +73,10 @@ def forward(x, w, k=None, gain=1.0, bias=None, res=None, out_div=1.0):
   return out / out_div, u
 
 
-def grads(x, w, dout, k=None, gain=1.0):
-  """(dx, dw, du) of out = fir(contraction(x, w)) for the output gradient dout, from the two gather formulas."""
+def gather(x, w, du):
+  """(dx, dw) of the two gather formulas from the map gradient du."""
   N, Cin, H, W = x.shape
-  Cout, _, K, _ = w.shape
-  kf, pad = taps_pad(k, K, gain, x.dtype)
-  du = fir_adjoint(dout, kf, pad, 2 * H - 2 + K, 2 * W - 2 + K)
+  K = w.shape[-1]
   dx = torch.zeros_like(x)
   dw = torch.zeros_like(w)
   for kh in range(K):
@@ -78,4 +84,24 @@ def grads(x, w, dout, k=None, gain=1.0):
       g = du[:, :, K - 1 - kh::2, K - 1 - kw::2][:, :, :H, :W]          # du[n, co, 2i+(K-1)-kh, 2j+(K-1)-kw]
       dx += torch.einsum('oc,noij->ncij', w[:, :, kh, kw], g)
       dw[:, :, kh, kw] = torch.einsum('ncij,noij->oc', x, g)
-  return dx, dw, du
+  return dx, dw
+
+
+def grads_taps(x, w, dout, kf, pad0):
+  """(dx, dw, du) for an arbitrary tap array and pad0."""
+  H, W, K = x.shape[2], x.shape[3], w.shape[-1]
+  du = fir_adjoint(dout, kf, pad_of(pad0, kf.shape[0], K), 2 * H - 2 + K, 2 * W - 2 + K)
+  return gather(x, w, du) + (du,)
+
+
+def forward(x, w, k=None, gain=1.0, bias=None, res=None, out_div=1.0):
+  """(out, u) in the dtype of x."""
+  kf, pad = taps_pad(k, w.shape[-1], gain, x.dtype)
+  assert pad == pad_of(pad[0], kf.shape[0], w.shape[-1])
+  return forward_taps(x, w, kf, pad[0], bias, res, out_div)
+
+
+def grads(x, w, dout, k=None, gain=1.0):
+  """(dx, dw, du) of out = fir(contraction(x, w)) for the output gradient dout, from the two gather formulas."""
+  kf, pad = taps_pad(k, w.shape[-1], gain, x.dtype)
+  return grads_taps(x, w, dout, kf, pad[0])

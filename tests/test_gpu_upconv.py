@@ -1,6 +1,8 @@
 """The FIR-upsampling convolution on the GPU (include/stk_upconv.h, csrc/upconv.hip): the three entries through ctypes, then the
 modules that use them, against the float64 restatement of tests/_upconv_ref.py.  Every bound is max|got - ref| / max|ref| <=
-CONV_RTOL (tests/_block_cases.py), the level the project holds its stride-2 f32-MFMA convolutions to.
+CONV_RTOL (tests/_block_cases.py), the level the project holds its stride-2 f32-MFMA convolutions to.  The per-element bounds
+on every launch form are tests/test_gpu_upconv_forms.py's.  (The taps of these cases, (1, 3, 3, 1) and (1, 1) normalised to sum
+4, are dyadic: their float32 and float64 values are the same numbers, so the reference sees the taps the kernel receives.)
 
 Worst measured error per direction over the kernel cases below (MI355X; profiles/upconv_accuracy.txt has every case):
   forward 8.762e-07, FIR adjoint (du) 2.029e-07, data gradient 2.441e-06, weight gradient 1.397e-06;
