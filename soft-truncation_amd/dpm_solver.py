@@ -21,6 +21,20 @@ evaluations follow the engine's conventions as ``get_pc_sampler`` does: ``torch.
 (``models.utils.frozen_weights``), ``precision`` ('fp16' applies to the network only: the update is always fp32).
 Everything runs on the device: host tensors raise the package's device error, there is no CPU path; a library without
 include/stk_solver.h is refused when the sampler is built.  Sample quality (FID) at any step count is unmeasured.
+
+Dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3; opt-in: ``threshold=(p, floor)``,
+``config.sampling.dpm_threshold / dpm_threshold_floor``) replaces the static clamp for guided sampling at large weights: per
+sample, s = max(floor, the p-quantile of |d_i|) and d_i <- clamp(d_i, -s, s) / s.  The quantile is the order statistic of
+rank ``threshold_rank(p, n)`` = min(n - 1, ceil(p (n - 1))) of the n = C H W absolute values -- the "higher" of the two
+order statistics a linearly interpolated percentile (``torch.quantile``, numpy's default) lies between, so it differs from
+that percentile by less than one spacing of order statistics.  A thresholded step is four streaming launches of
+include/stk_guided.h (csrc/guided.hip): ``stk_dpm_predict_f32``, two levels of ``stk_abs_select_f32`` and
+``stk_dpm_threshold_update_f32``, on a scratch, a q[B] and a workspace allocated once per run; the final ``denoise``
+evaluation is thresholded too.  It is defined on centred data (``config.data.centered``), excludes ``clip``, and needs a
+library with include/stk_guided.h (refused when the sampler is built).  Without ``threshold`` the loop is launch for launch
+the one above.  ``dynamic_threshold`` is the same thresholding for a user's own loop.  Not covered: the DPS sampler's
+``stk_tweedie_f32`` (its backward seed treats the clamp's bounds as constants) and the PC, ODE and adaptive samplers, which
+form no data prediction.  Sample quality under thresholding is unmeasured: no class-conditional checkpoint exists.
 """
 import math
 
@@ -154,6 +168,91 @@ def _check_grid(name, times, alpha, sigma):
   return lam
 
 
+def _guided_library():
+  return mutils.require('has_guided', 'stk_guided.h', 'stk_dpm_predict_f32, stk_abs_select_f32 and stk_dpm_threshold_update_f32',
+                        'dynamic thresholding needs')
+
+
+def threshold_rank(p, n):
+  """The 0-based rank min(n - 1, ceil(p (n - 1))) among n sorted absolute values that stands for the p-quantile: in float64,
+  the "higher" order statistic (module docstring)."""
+  return min(int(n) - 1, int(math.ceil(float(p) * (int(n) - 1))))
+
+
+def _threshold_pair(threshold):
+  """None, or (p, floor) as floats: ValueError unless 0 < p <= 1 and floor is positive and finite."""
+  if threshold is None:
+    return None
+  try:
+    p, floor = (float(v) for v in threshold)
+  except (TypeError, ValueError):
+    raise ValueError(f'threshold must be (p, floor), got {threshold!r}') from None
+  if not 0. < p <= 1.:
+    raise ValueError(f'threshold: p must lie in (0, 1], got {p!r}')
+  if not (floor > 0. and math.isfinite(floor)):
+    raise ValueError(f'threshold: floor must be positive and finite, got {floor!r}')
+  return p, floor
+
+
+def _check_threshold(threshold, clip):
+  pair = _threshold_pair(threshold)
+  if pair is not None and clip is not None:
+    raise ValueError(f'threshold={threshold!r} and clip={clip!r} exclude each other: dynamic thresholding replaces the static clamp')
+  return pair
+
+
+class _Thresholder:
+  """What a thresholded run allocates once: the d_raw scratch, q[B] and the workspace of include/stk_guided.h."""
+
+  def __init__(self, lib, x, p, floor):
+    self.lib, self.floor = lib, float(floor)
+    self.B, self.n = x.shape[0], x.numel() // x.shape[0]
+    self.rank = threshold_rank(p, self.n)
+    self.ws_bytes = int(lib.guided_ws_bytes(self.B, self.n))
+    if self.ws_bytes < 0:
+      raise ValueError(f'stk_guided_ws_bytes refuses a state of {self.B} rows of {self.n} (rc={self.ws_bytes})')
+    self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=x.device)
+    self.q = torch.empty(self.B, dtype=torch.float32, device=x.device)
+    self.d_raw = torch.empty_like(x)
+
+  def select(self, v, first_level_done):
+    """q[b] = the rank-th smallest |v[b]|."""
+    self.lib.abs_select_f32(v.data_ptr(), self.B, self.n, self.rank, self.q.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                            1 if first_level_done else 0, stk_lib.stream_ptr(v.device))
+
+  def apply(self, x, d_raw, d_prev, g, A, B, x_out, d_out):
+    ptr = lambda t: None if t is None else t.data_ptr()
+    self.lib.dpm_threshold_update_f32(ptr(x), d_raw.data_ptr(), ptr(d_prev), self.q.data_ptr(), self.floor, float(g), float(A),
+                                      float(B), ptr(x_out), ptr(d_out), self.B, self.n, stk_lib.stream_ptr(d_raw.device))
+
+  def update(self, x, score, d_prev, row, x_out, d_out):
+    """One thresholded step: predict, two select levels, update.  row: (cx, cs, g, A, B)."""
+    cx, cs, g, A, B = (float(v) for v in row)
+    with stk_lib.device_guard(x.device):
+      self.lib.dpm_predict_f32(x.data_ptr(), score.data_ptr(), cx, cs, self.d_raw.data_ptr(), self.B, self.n, self.ws.data_ptr(),
+                               self.ws_bytes, stk_lib.stream_ptr(x.device))
+      self.select(self.d_raw, True)
+      self.apply(x, self.d_raw, d_prev, g, A, B, x_out, d_out)
+    return x_out
+
+
+def dynamic_threshold(x0, p, floor=1.0):
+  """Dynamic thresholding of a data prediction for a user's own loop -> ``(x0_thresholded, s)``: per sample
+  s = max(floor, the order statistic of rank ``threshold_rank(p, n)`` of |x0|) as a [B] tensor (NaN for a sample that holds
+  a NaN at or below that rank) and x0_thresholded = clamp(x0, -s, s) / s, a new tensor.  x0: a contiguous float32 device
+  tensor [B, ...].  One selection (``stk_abs_select_f32``) and one streaming pass, on the device only."""
+  p, floor = _threshold_pair((p, floor))
+  lib = _guided_library()
+  mutils.check_inplace_state(x0, lib, why='the kernels read it in place')
+  th = _Thresholder(lib, x0, p, floor)
+  out = th.d_raw
+  with stk_lib.device_guard(x0.device):
+    th.select(x0, False)
+    th.apply(None, x0, None, 0., 0., 1., None, out)
+  q = th.q
+  return out, torch.where(torch.isnan(q), q, q.clamp_min(floor))
+
+
 def _clip_bounds(clip):
   if clip is None:
     return -_INF, _INF
@@ -173,14 +272,19 @@ def _update(lib, x, score, d_prev, row, bounds, x_out, d_out):
   return x_out
 
 
-def dpm_sample(score_fn, x, schedule, clip=None, denoise=False):
+def dpm_sample(score_fn, x, schedule, clip=None, denoise=False, threshold=None):
   """The loop: `x` (a contiguous fp32 device tensor drawn from the prior at the schedule's T) is advanced IN PLACE to the
   schedule's eps and returned.  Per step one ``score_fn(x, ones(B) * t_i)`` and one launch; the previous data prediction
   lives in one buffer, overwritten in place.  clip = (lo, hi) clamps every data prediction.  denoise: one more evaluation
-  at eps, after which `x` holds the data prediction there."""
+  at eps, after which `x` holds the data prediction there.  threshold = (p, floor): every data prediction, the one of
+  `denoise` included, is thresholded dynamically instead (module docstring): four launches per step."""
   lib = _library()
+  pair = _check_threshold(threshold, clip)
+  if pair is not None:
+    _guided_library()
   mutils.check_inplace_state(x, lib)
   bounds = _clip_bounds(clip)
+  th = _Thresholder(lib, x, *pair) if pair is not None else None
   rows = list(schedule.coeffs) + ([schedule.final] if denoise else [])
   times = list(schedule.times[:-1]) + ([schedule.times[-1]] if denoise else [])
   ones = torch.ones(x.shape[0], dtype=torch.float32, device=x.device)
@@ -190,25 +294,34 @@ def dpm_sample(score_fn, x, schedule, clip=None, denoise=False):
     keep = i + 1 < len(rows) and rows[i + 1][2] != 0.       # the next step extrapolates from this data prediction
     if keep and hist is None:
       hist = torch.empty_like(x)
-    _update(lib, x, score, hist if row[2] != 0. else None, row, bounds, x, hist if keep else None)
+    if th is None:
+      _update(lib, x, score, hist if row[2] != 0. else None, row, bounds, x, hist if keep else None)
+    else:
+      th.update(x, score, hist if row[2] != 0. else None, row, x, hist if keep else None)
   return x
 
 
 def get_dpm_sampler(config, sde, shape, inverse_scaler, steps=20, order=2, skip='logsnr', denoise=True, clip=None, eps=1e-3,
-                    device='cuda', precision='fp32', lower_order_final=True):
+                    device='cuda', precision='fp32', lower_order_final=True, threshold=None):
   """``dpm_sampler(model) -> (samples, nfe)`` with ``nfe = steps + (1 if denoise else 0)``: DPM-Solver++ of `order` over
   `steps` steps from ``sde.T`` down to `eps`.  denoise: return the data prediction at eps (one more evaluation) instead of
-  the state there.  precision='fp16': every network evaluation runs in the engine's fp16 mode (models.utils.precision)."""
+  the state there.  precision='fp16': every network evaluation runs in the engine's fp16 mode (models.utils.precision).
+  threshold = (p, floor): dynamic thresholding of every data prediction (module docstring); ValueError together with `clip`
+  or with ``config.data.centered`` false."""
   lib = _library()
   schedule = dpm_schedule(sde, steps, order=order, skip=skip, eps=eps, lower_order_final=lower_order_final)
   _clip_bounds(clip)
+  if _check_threshold(threshold, clip) is not None:
+    _guided_library()
+    if not config.data.centered:
+      raise ValueError('dynamic thresholding is defined on centred data: config.data.centered is false')
   mutils.check_precision(precision)
   nfe = schedule.steps + (1 if denoise else 0)
 
   def dpm_sampler(model):
     with mutils.sampling_run(model, precision):
       score_fn, x = mutils.score_and_prior(config, sde, model, shape, device, lib)
-      x = dpm_sample(score_fn, x, schedule, clip=clip, denoise=denoise)
+      x = dpm_sample(score_fn, x, schedule, clip=clip, denoise=denoise, threshold=threshold)
       return inverse_scaler(x), nfe
 
   return dpm_sampler
@@ -220,3 +333,12 @@ def sampling_options(config):
   read = lambda key, default: mutils.config_option(config, 'sampling', key, default)
   clip = read('dpm_clip', None)
   return read('dpm_steps', 20), read('dpm_order', 2), read('dpm_skip', 'logsnr'), None if clip is None else tuple(clip)
+
+
+def threshold_options(config):
+  """``threshold`` of ``config.sampling.dpm_threshold`` (p; None where absent: no thresholding) and
+  ``config.sampling.dpm_threshold_floor`` (1.0 where absent): None or (p, floor)."""
+  p = mutils.config_option(config, 'sampling', 'dpm_threshold', None)
+  if p is None:
+    return None
+  return float(p), float(mutils.config_option(config, 'sampling', 'dpm_threshold_floor', 1.0))

@@ -203,6 +203,15 @@ SIGNATURES_ADAGN = {
   'stk_gn_mod_bwd_f32': [P, P, P, P, P, I, P, P, P, F, P, P, P, P, I, I, I, I, I, F, U64, P, S],
 }
 _NO_CHECK_ADAGN = {'stk_gn_mod_ws_bytes', 'stk_gn_mod_ok'}                       # its queries
+# include/stk_guided.h: the per-sample order statistic and the launches of dynamic thresholding and guidance rescale around it.
+SIGNATURES_GUIDED = {
+  'stk_guided_ws_bytes': [I, L],
+  'stk_abs_select_f32': [P, I, L, L, P, P, L, I, S],
+  'stk_dpm_predict_f32': [P, P, F, F, P, I, L, P, L, S],
+  'stk_dpm_threshold_update_f32': [P, P, P, P, F, F, F, F, P, P, I, L, S],
+  'stk_cfg_rescale_f32': [P, P, F, F, P, I, L, P, L, S],
+}
+_RESTYPE_GUIDED = {'stk_guided_ws_bytes': c_long}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -226,6 +235,7 @@ OPTIONAL_HEADERS = (
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
+  Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,
             'stk_conv2d_fwd_ws_bytes': c_long, 'stk_conv2d_dgrad_ws_bytes': c_long, 'stk_gn_ws_bytes': c_long,

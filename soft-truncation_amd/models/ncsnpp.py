@@ -247,6 +247,8 @@ class NCSNpp(nn.Module):
     if num_classes > 0:         # outside all_modules: the all_modules.<i>.* keys keep their indices
       self.class_emb = ClassTable(num_classes, embed_dim_2 * 4)
     self._class_ctx = None      # (classes, guidance, [classes; null]) in force: models.utils.class_condition
+    self._cfg_rescale = 0.0     # ... and its guidance rescale, saved and restored with it
+    self._rescale_ws = {}
     self._null_rows = {}
     self._engine = None
     self._backend = None
@@ -298,7 +300,8 @@ class NCSNpp(nn.Module):
     (config.model.num_classes > 0) takes the classes and the guidance weight in force (models.utils.class_condition): no
     classes, every sample on the null row; a guidance weight w != 0, ONE evaluation of [x; x] with classes [y; null] and
     out = c + w (c - u) of its halves -- by stk_cfg_combine_f32, or by torch operators under grad mode, where autograd
-    has to see it."""
+    has to see it.  A guidance rescale phi != 0 in force: out = (phi std(c) / std(g) + 1 - phi) g per sample instead, by
+    stk_cfg_rescale_f32 (include/stk_guided.h), or by torch operators under grad mode."""
     if not self.num_classes:
       return self._forward(x, time_cond, None)
     B = x.shape[0]
@@ -309,13 +312,38 @@ class NCSNpp(nn.Module):
       return self._forward(x, time_cond, cls)
     out = self._forward(torch.cat([x, x]), torch.cat([time_cond, time_cond]), both)
     c, u = out[:B], out[B:]
+    phi = self._cfg_rescale
     if torch.is_grad_enabled():
-      return c + w * (c - u)
+      g = c + w * (c - u)
+      if phi == 0.0:
+        return g
+      # the kernel's formula: the standard deviations and f in float64, f rounded to fp32 once
+      std = lambda v: v.double().std(dim=(1, 2, 3), keepdim=True, unbiased=False)
+      sd_c, sd_g = std(c), std(g)
+      ok = torch.isfinite(sd_g) & (sd_g > 0)
+      f = torch.where(ok, phi * (sd_c / torch.where(ok, sd_g, torch.ones_like(sd_g))) + (1.0 - phi), torch.ones_like(sd_g))
+      return f.to(g.dtype) * g
     lib = self.engine().lib
     res = torch.empty_like(c)
     with _stk_lib.device_guard(c.device):
-      lib.cfg_combine_f32(c.data_ptr(), u.data_ptr(), w, res.data_ptr(), c.numel(), _stk_lib.stream_ptr(c.device))
+      if phi == 0.0:
+        lib.cfg_combine_f32(c.data_ptr(), u.data_ptr(), w, res.data_ptr(), c.numel(), _stk_lib.stream_ptr(c.device))
+      else:
+        n = c.numel() // B
+        ws = self._rescale_workspace(lib, B, n, c.device)
+        lib.cfg_rescale_f32(c.data_ptr(), u.data_ptr(), w, phi, res.data_ptr(), B, n, ws.data_ptr(), ws.numel(),
+                            _stk_lib.stream_ptr(c.device))
     return res
+
+  def _rescale_workspace(self, lib, B, n, device):
+    """The workspace of stk_cfg_rescale_f32 for B rows of n, allocated once per (B, n, device)."""
+    ws = self._rescale_ws.get((B, n, device))
+    if ws is None:
+      if not getattr(lib, 'has_guided', False):
+        raise NotImplementedError(f'{lib.path} ({lib.backend}) does not implement include/stk_guided.h: guidance rescale '
+                                  f'needs stk_cfg_rescale_f32 (there is no other path)')
+      ws = self._rescale_ws[(B, n, device)] = torch.empty(int(lib.guided_ws_bytes(B, n)), dtype=torch.uint8, device=device)
+    return ws
 
   def _forward(self, x, time_cond, cls):
     sigma = None

@@ -190,14 +190,15 @@ def classes_in_force(model, cls):
   `cls` is a [B] float32 tensor of class indices on the model's device."""
   inner = getattr(model, 'module', model)
   saved, inner._class_ctx = inner._class_ctx, (cls, 0.0, None)
+  saved_rescale, inner._cfg_rescale = getattr(inner, '_cfg_rescale', 0.0), 0.0
   try:
     yield
   finally:
-    inner._class_ctx = saved
+    inner._class_ctx, inner._cfg_rescale = saved, saved_rescale
 
 
 @contextlib.contextmanager
-def class_condition(model, classes, guidance=0.0):
+def class_condition(model, classes, guidance=0.0, rescale=0.0):
   """Context manager: every network evaluation of the class-conditional `model` inside it is conditioned on `classes` -- a
   [B] integer tensor or sequence, the value C (= config.model.num_classes) or None for the null class -- with
   classifier-free guidance of weight `guidance`: out = c + guidance (c - u), c the evaluation with the classes, u the one
@@ -205,10 +206,18 @@ def class_condition(model, classes, guidance=0.0):
   weight costs ONE pass at batch 2 B ([x; x] with classes [y; null]) and one launch of stk_cfg_combine_f32 (torch
   operators under grad mode, where autograd has to see the combination), and the engine's arena of a batch of 2 B.
 
+  rescale = phi in [0, 1] (Lin et al. 2024, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4)
+  pulls each sample's guided output g back towards the standard deviation of its conditional output c:
+  out = (phi std(c) / std(g) + 1 - phi) g, the standard deviations per sample over C H W in population form.  0 is the
+  path above, bit for bit; any other value replaces the combination by the two launches of stk_cfg_rescale_f32
+  (include/stk_guided.h; the same formula by torch operators under grad mode, so the DPS sampler and the likelihood
+  differentiate through it); with guidance = 0 it is accepted and does nothing (c is its own target).  Sample quality under
+  it is unmeasured.  A model whose library lacks include/stk_guided.h raises NotImplementedError at its first guided evaluation.
+
   Every sampler takes classes through it unchanged: ``with class_condition(model, y, 1.5): sampling_fn(model)``.
   Checked once, on entry, with one host read: ValueError for a model that is not class-conditional, a wrong shape or
-  dtype, a value outside [0, C], a guidance weight that is not finite; an evaluation of a batch of another size inside it
-  raises ValueError too.  Contexts nest and restore; `model` may be the DataParallel wrapper."""
+  dtype, a value outside [0, C], a guidance weight that is not finite, a rescale outside [0, 1]; an evaluation of a batch of
+  another size inside it raises ValueError too.  Contexts nest and restore; `model` may be the DataParallel wrapper."""
   inner = getattr(model, 'module', model)
   C = num_classes(model)
   if C <= 0:
@@ -219,14 +228,21 @@ def class_condition(model, classes, guidance=0.0):
     raise ValueError(f'guidance must be a finite number, got {guidance!r}') from None
   if not math.isfinite(w):
     raise ValueError(f'guidance must be a finite number, got {guidance!r}')
+  try:
+    phi = float(rescale)
+  except (TypeError, ValueError):
+    raise ValueError(f'rescale must be a number in [0, 1], got {rescale!r}') from None
+  if not 0.0 <= phi <= 1.0:
+    raise ValueError(f'rescale must be a number in [0, 1], got {rescale!r}')
   device = next(inner.parameters()).device
   cls = as_class_tensor(classes, C).to(device=device, dtype=torch.float32)
   both = torch.cat([cls, inner.null_classes(cls.shape[0], device)]) if w != 0.0 else None
   saved, inner._class_ctx = inner._class_ctx, (cls, w, both)
+  saved_rescale, inner._cfg_rescale = getattr(inner, '_cfg_rescale', 0.0), phi
   try:
     yield
   finally:
-    inner._class_ctx = saved
+    inner._class_ctx, inner._cfg_rescale = saved, saved_rescale
 
 
 # ---- what the samplers share (sampling.py, controllable_generation.py, dpm_solver.py, adaptive_sde.py) --------------------
@@ -258,11 +274,12 @@ def score_and_prior(config, sde, model, shape, device, lib):
   return score_fn, x
 
 
-def check_inplace_state(x, lib):
-  """The state a loop advances in place: on the library's device, contiguous, float32."""
+def check_inplace_state(x, lib, why='it is updated in place'):
+  """The state a loop advances in place (or an operand the kernels take as it lies): on the library's device, contiguous,
+  float32."""
   _backend.check(x, lib)
   if x.dtype != torch.float32 or not x.is_contiguous():
-    raise ValueError(f'x must be a contiguous float32 tensor (it is updated in place), got {x.dtype}, strides {x.stride()}')
+    raise ValueError(f'x must be a contiguous float32 tensor ({why}), got {x.dtype}, strides {x.stride()}')
 
 
 def checked_score(score_fn, x, t, lib):

@@ -314,7 +314,8 @@ def _denoiser(config, sde, probability_flow):
 
 def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   """``sampling_fn(model) -> (samples, nfe)`` for ``config.sampling.method`` (sampling.py:80-125): 'pc', 'ode', or
-  'dpm_solver' (dpm_solver.py; its options are ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip``) or 'adaptive'
+  'dpm_solver' (dpm_solver.py; its options are ``config.sampling.dpm_steps / dpm_order / dpm_skip / dpm_clip / dpm_threshold /
+  dpm_threshold_floor``) or 'adaptive'
   (adaptive_sde.py; ``config.sampling.adaptive_rtol / adaptive_atol / adaptive_h_init / adaptive_safety / adaptive_exponent``)."""
   s = config.sampling
   kind = s.method.lower()
@@ -336,7 +337,8 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
     steps, order, skip, clip = dpm_solver.sampling_options(config)
     return dpm_solver.get_dpm_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=steps,
                                       order=order, skip=skip, denoise=s.noise_removal, clip=clip, eps=eps,
-                                      device=config.device, precision=precision)
+                                      device=config.device, precision=precision,
+                                      threshold=dpm_solver.threshold_options(config))
   if kind == 'adaptive':
     rtol, atol, h_init, safety, exponent = adaptive_sde.sampling_options(config)
     return adaptive_sde.get_adaptive_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, rtol=rtol,
