@@ -16,6 +16,14 @@
  *
  * Shapes: 32 <= C <= 256, C % 32 == 0, 4 <= T <= 16384, T % 4 == 0, fewer than 2^31 elements per [B, C, T] tensor.
  *
+ * Range: a tensor's power-of-two scale is at most 2^127, and so is the scale of a score-gradient column ds; the
+ * epilogues undo them one after the other, so dq and dk are right wherever (scale / s_k) / sig (dq) and
+ * (scale / s_q) / sig (dk) are fp32 numbers: with |q|, |k|, |v| around 1, down to gradients d_o of 2^-100 and below.  Once
+ * that factor is subnormal (s_x sig above scale 2^126) it keeps 2^-149 absolute, and the result degrades gradually.
+ * What remains outside: max |q| or max |k| below scale 2^-113 (scale / s_x is then itself subnormal), products
+ * s_q s_k or s_v s_do above 2^127 (the scores or dp are then below fp32 range themselves), and entries of ds under
+ * 2^-126, which do not contribute.
+ *
  * Arguments (both directions):
  *   q, k, v      [B, C, T] fp32, 16-byte aligned; image b of each at b * qkv_bstride floats from its pointer
  *   qkv_bstride  floats between consecutive images of q, k, v: C*T for separate tensors, 3*C*T for the channel slices of

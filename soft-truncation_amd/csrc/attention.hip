@@ -513,7 +513,7 @@ __global__ __launch_bounds__(TK * 2, TK / 128) void attn_kernel(Args a) {   // N
     // rows of channels >= C were computed from zeros and are not stored
     __amdgpu_buffer_rsrc_t ors = make_rsrc(a.out[which], bytes_of(a.os[which]));
     const float beta = a.beta[which];
-    const float inv = 1.f / (s_a * s_b);
+    const float inv = (1.f / s_a) / s_b;        // powers of two, one after the other: s_a s_b may pass 2^127 (a tiny ds tile)
     const unsigned obase = (unsigned)(b * a.os[which]) * 4u + hoff;
     if (MH && !wlive) return;
 #pragma unroll

@@ -21,7 +21,9 @@
 // ds is scaled per owned column (query for DQ, key for DKV): the scale of a column is the power of two of the largest
 // |ds| seen so far in it; when a chunk raises that maximum the scale drops and the column's accumulator is multiplied by
 // the exact power-of-two ratio of the two scales.  Chunks with smaller |ds| keep the current scale (their terms land
-// below 2^13 in the planes, exact to the fp16 subnormal step: 2^-37 of the column's largest term).
+// below 2^13 in the planes, exact to the fp16 subnormal step: 2^-37 of the column's largest term).  A chunk whose |ds|
+// are all subnormal sets no scale; the epilogue undoes the tensor's and the column's scale one after the other, because
+// their product may pass 2^127 where neither does (include/stk_attention_long.h, "Range").
 //
 // Fragment layouts of v_mfma_f32_16x16x32_f16 (lane l, r = l % 16, g = l / 16): A[i = r][k = 8 g + j], B[k = 8 g + j][n = r],
 // D[i = 4 g + e][n = r].  A score tile of 32 streamed positions is two 16-row D tiles; lane (r, g) holds rows
@@ -218,8 +220,8 @@ template <int NCB>
 __device__ __forceinline__ void ds_rescale(float dmax, float& sig, floatx4 (&acc)[NCB]) {
   dmax = fmaxf(dmax, __shfl_xor(dmax, 16, 64));
   dmax = fmaxf(dmax, __shfl_xor(dmax, 32, 64));
-  if (dmax > 0.f) {
-    const float sc = pow2_scale_of(dmax);
+  if (dmax >= 1.17549435e-38f) {                                   // a subnormal maximum sets no scale: pow2_scale_of gives 1,
+    const float sc = pow2_scale_of(dmax);                          // which would pin the column's scale (it only drops)
     if (sig == 0.f || sc < sig) {
       if (sig != 0.f) {
         const float f = sc / sig;                                 // a power of two <= 1/2: exact
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(NW * 64) void dq_kernel(KArgs a) {
     for (int cb = 0; cb < NCB; ++cb) mma3(acc[cb], frag_pf<C>(kp, 0, cb, r, g), frag_pf<C>(kp, 1, cb, r, g), bh, bl);
   }
   if (live) {
-    const float f = sig == 0.f ? 0.f : a.scale / (sk * sig), beta = a.beta[0];
+    const float f = sig == 0.f ? 0.f : (a.scale / sk) / sig, beta = a.beta[0];   // not scale / (sk sig): sk sig may pass 2^127
     float* ob = a.out[0] + (long)(b / a.H) * a.os + (long)(b % a.H) * C * T + t;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
@@ -454,7 +456,7 @@ __global__ __launch_bounds__(NW * 64) void dkv_kernel(KArgs a) {
     for (int cb = 0; cb < NCB; ++cb) mma3(dk[cb], frag_pf<C>(qp, 0, cb, r, g), frag_pf<C>(qp, 1, cb, r, g), bh, bl);
   }
   if (live) {
-    const float fk = sig == 0.f ? 0.f : a.scale / (sq * sig), fv = 1.f / (sd * P_SCALE);
+    const float fk = sig == 0.f ? 0.f : (a.scale / sq) / sig, fv = 1.f / (sd * P_SCALE);   // as in dq_kernel
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
       float* base = a.out[which];

@@ -30,6 +30,8 @@ Input families (inputs()):
   offset      k = +a u + noise: row maxima around +60.
   coherent    q, k = (1 + 0.9 2^-11) 2^j, j in {-1, 0, 1}: every lo part is positive and as large as it gets, so a lost
               hi lo term is a coherent 4.4e-4 of every score instead of a random walk.
+  tiny do     randn with do = 2^-100 randn: the ds tiles' scales reach 2^120, and their product with k's or q's scale passes
+              2^127, which the epilogue's 1 / (sa sds) turned into a factor 0; it divides by one after the other now.
   floor cases (FLOOR_CASES; the floor may dominate the bound there, and the model has to show an error of a quarter of it):
     floor peaked      one key takes all but ~4e-11 of every row (the others' exp(s - max) ~ 0.4 2^-38, below half a step of
                       the 2^13 split; at 1e-9 of the mass they would round either way and cancel) and carries v = 0; v >= 0.
@@ -112,6 +114,7 @@ CASES = [
   _c('mh', 1, 64, 2, 128, 'separate', fam='floor unattended'),
   _c('sh', 2, 32, 1, 28, 'separate', fam='floor ds row'),
   _c('mh', 2, 64, 2, 64, 'separate', fam='coherent'),
+  _c('sh', 2, 64, 1, 128, 'separate', fam='tiny do'),                           # last: a case's seed is its position
 ]
 IDS = [c.name for c in CASES]
 BY_NAME = {c.name: c for c in CASES}
@@ -193,7 +196,7 @@ def _required():
   R |= {f'mh full d {d}' for d in (32, 64, 128, 256)} | {'split-n', 'dead waves d 32', 'dead waves d 96', 'C 512'}
   R |= {'one head through mh, MH kernels', 'one head through mh, single-head kernels'}
   R |= {f'negative T {T}' for T in T_VALUES if T % 32}
-  R |= {f'fam {f}' for f in ('randn', 'decades', 'apart', 'negative', 'offset', 'coherent') + tuple(FLOOR_CASES)}
+  R |= {f'fam {f}' for f in ('randn', 'decades', 'apart', 'negative', 'offset', 'coherent', 'tiny do') + tuple(FLOOR_CASES)}
   return R
 
 
@@ -201,17 +204,18 @@ REQUIRED = _required()
 
 
 # ---- operands ----------------------------------------------------------------------------------------------------------------
-def _inputs(c):
+def _inputs(c, seed=None):
+  """seed: for a case of another table (tests/_attn_long_cases.py); this table's cases take theirs from their position."""
   B, C, T, H = c.B, c.C, c.T, c.heads
   d = C // H
   scale = scale_of(c)
-  rng = np.random.default_rng(4100 + IDS.index(c.name))
+  rng = np.random.default_rng(4100 + IDS.index(c.name) if seed is None else seed)
   rn = lambda *s: rng.standard_normal(s)
   per_head = lambda u: np.tile(u, H)[None, :, None]                             # a [d] vector on every head: [1, C, 1]
   u0 = per_head(rng.choice([-1.0, 1.0], d))
   q, k, v, do = rn(B, C, T), rn(B, C, T), rn(B, C, T), rn(B, C, T)
   fam = c.fam
-  if fam in ('randn', 'decades', 'apart', 'floor ds row'):
+  if fam in ('randn', 'decades', 'apart', 'floor ds row', 'tiny do'):
     a = (3.0 / (scale * d ** 0.5)) ** 0.5
     q, k = q * a, k * a
     if fam == 'decades':
@@ -223,6 +227,8 @@ def _inputs(c):
       q, k, v, do = q / a * 3e3, k / a * 2e-3, v * 5e-4, do * 1e-6
     elif fam == 'floor ds row':
       do[:, :, DS_ROW] *= 2.0 ** -20
+    elif fam == 'tiny do':
+      do = do * 2.0 ** -100
   elif fam in ('negative', 'offset'):
     a = ((34.0 if fam == 'negative' else 55.0) / (scale * d)) ** 0.5
     sg = 2.0 / (scale * a * (2 * d) ** 0.5)
