@@ -271,3 +271,25 @@ def tiny(config, nf=16, ch_mult=(1, 2), num_res_blocks=1, image_size=16, attn_re
   config.model.dropout = dropout
   config.data.image_size = image_size
   return config
+
+
+def edm(config, sigma_min=0.002, sigma_max=80., sigma_data=0.5, p_mean=-1.2, p_std=1.2, steps=18, rho=7.):
+  """The EDM variant of any config above (Karras et al. 2022, Table 1 "Ours"): the same network under ``training.sde =
+  'edm'`` with its noise range and data scale, the log-normal training levels, and the 18-step Heun sampler.  Centred data and
+  ``scale_by_sigma = False`` are what the family needs (models.utils.check_edm_config); the switches of the Soft-Truncation
+  objective it refuses are set off."""
+  config = copy.deepcopy(config)
+  t = config.training
+  t.sde = 'edm'
+  t.continuous = True
+  t.edm_p_mean, t.edm_p_std = p_mean, p_std
+  t.mixed = t.importance_sampling = t.likelihood_weighting = t.reconstruction_loss = False
+  m = config.model
+  m.sigma_min, m.sigma_max, m.sigma_data = sigma_min, sigma_max, sigma_data
+  m.scale_by_sigma = False
+  config.data.centered = True
+  s = config.sampling
+  s.method = 'edm'
+  s.edm_steps, s.edm_rho = steps, rho
+  s.edm_s_churn, s.edm_s_tmin, s.edm_s_tmax, s.edm_s_noise = 0., 0., float('inf'), 1.
+  return config

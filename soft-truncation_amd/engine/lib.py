@@ -203,6 +203,16 @@ SIGNATURES_ADAGN = {
   'stk_gn_mod_bwd_f32': [P, P, P, P, P, I, P, P, P, F, P, P, P, P, I, I, I, I, I, F, U64, P, S],
 }
 _NO_CHECK_ADAGN = {'stk_gn_mod_ws_bytes', 'stk_gn_mod_ok'}                       # its queries
+# include/stk_edm.h: the coefficients, the loss pair and the sampler launches of the EDM formulation.
+SIGNATURES_EDM = {
+  'stk_edm_coeffs_f32': [P, F, P, I, S],
+  'stk_edm_ws_bytes': [I, L],
+  'stk_edm_loss_f32': [P, P, P, P, P, P, L, P, P, I, L, I, S],
+  'stk_edm_loss_grad_f32': [P, P, P, P, I, L, I, S],
+  'stk_edm_churn_f32': [P, P, F, F, P, P, L, S],
+  'stk_edm_step_f32': [P, P, P, P, F, F, F, F, F, P, P, P, L, S],
+}
+_RESTYPE_EDM = {'stk_edm_ws_bytes': c_long}
 # include/stk_guided.h: the per-sample order statistic and the launches of dynamic thresholding and guidance rescale around it.
 SIGNATURES_GUIDED = {
   'stk_guided_ws_bytes': [I, L],
@@ -235,6 +245,7 @@ OPTIONAL_HEADERS = (
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
+  Header('has_edm', 'include/stk_edm.h', SIGNATURES_EDM, _RESTYPE_EDM, ()),
   Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),
 )
 _RESTYPE = {'stk_strerror': c_char_p, 'stk_backend': c_char_p, 'stk_conv2d_wgrad_ws_bytes': c_long,

@@ -26,7 +26,7 @@ from .engine import ddp
 from .engine.flat import flat_of
 from .engine.optim import FusedAdam
 from .models import utils as mutils
-from .sde_lib import VESDE, VPSDE, reciprocal_VESDE
+from .sde_lib import EDM, VESDE, VPSDE, reciprocal_VESDE
 
 
 def _wide(v):
@@ -271,7 +271,113 @@ def get_ddpm_loss_fn(config, vpsde, train):
   return loss_fn
 
 
+class _EdmLoss(torch.autograd.Function):
+  """losses[b] = lambda_b * reduce(r^2), r = c_skip (y + sigma n) + c_out F - y: the tail of the EDM loss on the raw network
+  output F as stk_edm_loss_f32 (include/stk_edm.h), whose residual r is kept; the backward is stk_edm_loss_grad_f32 IN PLACE
+  on that r (24 B per element for the pair), so a second backward through the same evaluation is refused."""
+
+  @staticmethod
+  def forward(ctx, F, y, n, sigma, coef, lib, reduce_mean):
+    from .engine import lib as stk_lib
+    F, y, n = F.contiguous(), y.contiguous(), n.contiguous()
+    B, inner = F.shape[0], F[0].numel()
+    key = ('edm_ws', B, inner, F.device)
+    ws = _fused_bufs.get(key)
+    if ws is None:       # per batch shape: the partial sums, consumed by the finishing pass of the same call
+      ws_bytes = int(lib.edm_ws_bytes(B, inner))
+      if ws_bytes < 0:
+        raise ValueError(f'stk_edm_ws_bytes refuses a batch of {B} rows of {inner} (rc={ws_bytes})')
+      ws = _fused_bufs[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=F.device)
+    keep = ctx.needs_input_grad[0]
+    r = torch.empty_like(F) if keep else None
+    losses = torch.empty(B, dtype=torch.float32, device=F.device)
+    with stk_lib.device_guard(F.device):
+      lib.edm_loss_f32(F.data_ptr(), y.data_ptr(), n.data_ptr(), sigma.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel(),
+                       r.data_ptr() if keep else None, losses.data_ptr(), B, inner, int(reduce_mean), stk_lib.stream_ptr(F.device))
+    ctx.args = (lib, B, inner, int(reduce_mean), r, coef)
+    return losses
+
+  @staticmethod
+  def backward(ctx, dloss):
+    from .engine import lib as stk_lib
+    lib, B, inner, reduce_mean, r, coef = ctx.args
+    if r is None:
+      raise RuntimeError('the EDM loss kept its residual once: a second backward through the same evaluation is not possible')
+    ctx.args = (lib, B, inner, reduce_mean, None, coef)
+    dloss = dloss.contiguous()
+    with stk_lib.device_guard(r.device):
+      lib.edm_loss_grad_f32(r.data_ptr(), coef.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, reduce_mean,
+                            stk_lib.stream_ptr(r.device))
+    return r, None, None, None, None, None, None
+
+
+def get_edm_loss_fn(config, sde, train):
+  """The EDM training loss (Karras et al. 2022, Table 1 "Ours"): ``loss_fn(model, batch, importance_sampling=None, t_min=None)
+  -> [B]``, both keywords accepted and unused.  Per evaluation, in this order: ``torch.randn(B)`` for ln sigma = P_mean +
+  P_std randn (``training.edm_p_mean`` = -1.2, ``training.edm_p_std`` = 1.2 where absent), then ``torch.randn_like(batch)``
+  for n.  With the coefficients of include/stk_edm.h,
+
+    x_in = c_in y + (c_in sigma) n;  F = network(x_in, c_noise);  r = c_skip (y + sigma n) + c_out F - y;
+    loss[b] = lambda_b sum r^2   (the mean over C H W under ``training.reduce_mean``)
+
+  every element in fp32 in that order, the squares summed in float64.  On an engine model with a device fp32 batch, a library
+  with the header and STK_FUSED_LOSS != 0 this is stk_edm_coeffs_f32, stk_perturb_f32, the network and stk_edm_loss_f32 /
+  stk_edm_loss_grad_f32; otherwise the same expressions by torch operators."""
+  mutils.check_edm_config(config, training=True)
+  if not isinstance(sde, EDM):
+    raise ValueError(f'get_edm_loss_fn needs sde_lib.EDM, got {type(sde).__name__}')
+  tr = config.training
+  p_mean = float(mutils.config_option(config, 'training', 'edm_p_mean', -1.2))
+  p_std = float(mutils.config_option(config, 'training', 'edm_p_std', 1.2))
+  if not p_std > 0:
+    raise ValueError(f'config.training.edm_p_std must be positive, got {p_std!r}')
+  s_data = float(sde.sigma_data)
+  reduce_mean = bool(tr.reduce_mean)
+
+  def fused_losses(lib, F_fn, batch, sigma, n):
+    from .engine import lib as stk_lib
+    B = batch.shape[0]
+    y = batch.contiguous()
+    inner = y[0].numel()
+    sigma = sigma.contiguous()
+    coef = torch.empty((6, B), dtype=torch.float32, device=y.device)
+    x_in = torch.empty_like(y)
+    with stk_lib.device_guard(y.device):
+      stream = stk_lib.stream_ptr(y.device)
+      lib.edm_coeffs_f32(sigma.data_ptr(), s_data, coef.data_ptr(), B, stream)
+      lib.perturb_f32(y.data_ptr(), n.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), x_in.data_ptr(), B, inner, stream)
+    F = F_fn(x_in, coef[5])
+    return _EdmLoss.apply(F, y, n, sigma, coef, lib, reduce_mean)
+
+  def torch_losses(F_fn, batch, sigma, n):
+    c_in, c_in_sigma, c_skip, c_out, lam, c_noise = (v.to(torch.float32) for v in mutils.edm_coefficients(sigma, s_data))
+    x_in = _wide(c_in) * batch + _wide(c_in_sigma) * n
+    F = F_fn(x_in, c_noise)
+    x = batch + _wide(sigma) * n
+    D = _wide(c_skip) * x + _wide(c_out) * F
+    r = D - batch
+    total = (r * r).double().reshape(r.shape[0], -1).sum(dim=-1)
+    total = lam.double() * total
+    if reduce_mean:
+      total = total / float(np.prod(batch.shape[1:]))
+    return total.to(torch.float32)
+
+  def loss_fn(model, batch, importance_sampling=None, t_min=None):
+    B = batch.shape[0]
+    sigma = torch.exp(p_mean + p_std * torch.randn(B, device=batch.device)).to(torch.float32)
+    n = torch.randn_like(batch)
+    F_fn = mutils.get_edm_model_fn(config, model, train=train)
+    lib = _engine_lib(model, batch) if FUSED_LOSS else None
+    if lib is not None and lib.has_edm:
+      return fused_losses(lib, F_fn, batch, sigma, n.contiguous())
+    return torch_losses(F_fn, batch, sigma, n)
+
+  return loss_fn
+
+
 def _pick_loss_fn(config, sde, train):
+  if isinstance(sde, EDM):
+    return get_edm_loss_fn(config, sde, train)
   if config.training.continuous:
     return get_sde_loss_fn(config, sde, train)
   assert not config.training.likelihood_weighting, \

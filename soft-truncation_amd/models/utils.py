@@ -342,12 +342,75 @@ def _ve_score_fn(sde, model_fn, continuous):
   return score_fn
 
 
+# ---- the EDM formulation (sde_lib.EDM, include/stk_edm.h) ---------------------------------------------------------------------
+EDM_TRAINING_REFUSED = ('mixed', 'importance_sampling', 'likelihood_weighting', 'reconstruction_loss')
+
+
+def check_edm_config(config, training=False):
+  """What sde_lib.EDM asks of a config, checked when a score function, a loss, a step function or a sampler is built on it;
+  ValueError naming the key.  ``data.centered`` must be true (the network recentres uncentred data itself, which it would
+  apply to c_in x), ``model.scale_by_sigma`` false (the denoiser's c_out is the output scale) and ``training.continuous``
+  true; training: ``training.mixed / importance_sampling / likelihood_weighting / reconstruction_loss`` must all be off
+  (they belong to the Soft-Truncation objective)."""
+  if not config_option(config, 'data', 'centered', False):
+    raise ValueError('the EDM formulation needs config.data.centered = True: the network would recentre c_in x itself')
+  if config_option(config, 'model', 'scale_by_sigma', False):
+    raise ValueError('the EDM formulation needs config.model.scale_by_sigma = False: c_out is the output scale of the denoiser')
+  if not config_option(config, 'training', 'continuous', True):
+    raise ValueError('the EDM formulation needs config.training.continuous = True: the noise level is a continuous time')
+  if training:
+    for key in EDM_TRAINING_REFUSED:
+      if config_option(config, 'training', key, False):
+        raise ValueError(f'the EDM loss does not take config.training.{key}: it belongs to the Soft-Truncation objective')
+
+
+def edm_coefficients(sigma, sigma_data):
+  """The six rows of include/stk_edm.h -- c_in, c_in sigma, c_skip, c_out, lambda = 1 / c_out^2, c_noise = ln(sigma) / 4 -- of
+  the [B] tensor `sigma`, in float64 in the header's operation order; the caller rounds them."""
+  S, d = sigma.double(), float(sigma_data)
+  v = S * S + d * d
+  q = torch.sqrt(v)
+  p = S * d
+  return 1. / q, S / q, (d * d) / v, p / q, v / (p * p), torch.log(S) / 4.
+
+
+def get_edm_model_fn(config, model, train=False):
+  """``F(x_in, c_noise)``: the raw network under the EDM conditioning c_noise = ln(sigma) / 4 ([B] fp32) -- handed over as it
+  is for ``embedding_type = 'positional'``, as exp(c_noise) for 'fourier', whose forward takes the log itself."""
+  model_fn = get_model_fn(model, train=train)
+  if config.model.embedding_type.lower() == 'fourier':
+    return lambda x_in, c_noise: model_fn(x_in, torch.exp(c_noise))
+  return model_fn
+
+
+def _edm_score_fn(config, sde, model, train):
+  """score(x, sigma) = (D(x; sigma) - x) / sigma^2 = -c_in^2 x + (s c_in / sigma) F(c_in x; c_noise), by torch operators
+  (autograd sees it: the likelihood, DPS and class_condition work as for the other families).  Classifier-free guidance acts
+  on F inside the model; D is affine in it."""
+  check_edm_config(config)
+  F = get_edm_model_fn(config, model, train)
+  s = float(sde.sigma_data)
+
+  def score_fn(x, t):
+    sigma = t.to(x.dtype)
+    c_in = 1. / torch.sqrt(sigma * sigma + s * s)
+    out = F(c_in[:, None, None, None] * x, (torch.log(sigma) / 4.).to(torch.float32))
+    return -(c_in * c_in)[:, None, None, None] * x + (s * c_in / sigma)[:, None, None, None] * out
+
+  return score_fn
+
+
 def get_raw_fn(config, sde, model, train=False, continuous=False):
   """The pieces of :func:`get_score_fn` for callers that fuse what follows the network (losses.py's fused loss path):
   ``raw_fn(x, t) -> network output`` with exactly the conditioning labels `get_score_fn` computes, and ``neg_over_std``:
   whether the score is ``-output / std(t)`` (VP family with ``training.ddpm_score``) or the output itself.  Returns
-  ``(None, None)`` for the combinations it does not cover (discrete ladders)."""
+  ``(None, None)`` for the combinations it does not cover (discrete ladders).  sde_lib.EDM: ``raw_fn(x_in, sigma) = F``, the
+  network on an input the caller has scaled by c_in already (the score is :func:`get_score_fn`'s, not the output)."""
   model_fn = get_model_fn(model, train=train)
+  if isinstance(sde, sde_lib.EDM):
+    check_edm_config(config)
+    F = get_edm_model_fn(config, model, train)
+    return (lambda x_in, t: F(x_in, (torch.log(t) / 4.).to(torch.float32))), False
   if isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE)):
     if not (continuous or isinstance(sde, sde_lib.subVPSDE)):
       return None, None
@@ -362,7 +425,10 @@ def get_score_fn(config, sde, model, train=False, continuous=False):
   """Turn the raw network into a score function s(x, t) (models/utils.py:128-190).
 
   VP / subVP: labels = 999 t (continuous), score = -net/std when ``training.ddpm_score``;
-  VE / RVE:   labels = sigma(t) (continuous), the network output is already the score."""
+  VE / RVE:   labels = sigma(t) (continuous), the network output is already the score;
+  EDM:        t = sigma, score = (D(x; sigma) - x) / sigma^2 of the preconditioned denoiser D."""
+  if isinstance(sde, sde_lib.EDM):
+    return _edm_score_fn(config, sde, model, train)
   model_fn = get_model_fn(model, train=train)
   if isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE)):
     return _vp_score_fn(config, sde, model_fn, continuous)

@@ -2,7 +2,8 @@
 
 Interface parity with the reference ``sde_lib.py`` (file:line = /root/reference/sde_lib.py): abstract ``SDE``
 (:8-119) with ``T, sde, marginal_prob, prior_sampling, prior_logp, discretize, reverse``; ``VPSDE`` (:121-207),
-``subVPSDE`` (:209-246), ``VESDE`` (:248-332), ``reciprocal_VESDE`` (:334-430); factory ``get_sde`` (:433-445); the
+``subVPSDE`` (:209-246), ``VESDE`` (:248-332), ``reciprocal_VESDE`` (:334-430); factory ``get_sde`` (:433-445), which
+also knows ``EDM`` (this package's own: the sigma-parametrised family of Karras et al. 2022); the
 Soft-Truncation additions ``integral_beta / antiderivative / normalizing_constant / get_diffusion_time / get_t_min``.
 
 How this file is organised (it is not laid out like the reference): the pieces several SDEs share live once, in
@@ -361,6 +362,39 @@ class reciprocal_VESDE(_UnitHorizon, _GaussianPrior, SDE):
     return 1. / (np.random.rand() * (1. / self.eps - 1. / self.T) + 1. / self.T)
 
 
+# ---- EDM ------------------------------------------------------------------------------------------------------------
+class EDM(_GaussianPrior, SDE):
+  """The noise family of EDM (Karras et al. 2022, "Elucidating the Design Space of Diffusion-Based Generative Models"): the
+  time IS the noise level, x_t = x_0 + t z on [sigma_min, sigma_max], so T = sigma_max and eps = sigma_min.  Not in the
+  reference.  ``marginal_prob`` hands the time back as the std in the dtype it came in (float64 carried through, which
+  ``dpm_solver.alpha_sigma`` relies on).  The network is wrapped into the denoiser D(x; sigma) with ``sigma_data``
+  (models.utils.get_score_fn); the loss is losses.get_edm_loss_fn and the sampler edm.get_edm_sampler.  There is no
+  Soft-Truncation time sampling for this family: ``get_t_min`` is ``eps``."""
+
+  def __init__(self, sigma_min=0.002, sigma_max=80, sigma_data=0.5, N=1000):
+    super().__init__(N)
+    if not 0 < sigma_min < sigma_max:
+      raise ValueError(f'EDM needs 0 < model.sigma_min < model.sigma_max, got {sigma_min!r}, {sigma_max!r}')
+    if not sigma_data > 0:
+      raise ValueError(f'EDM needs model.sigma_data > 0, got {sigma_data!r}')
+    self.sigma_min, self.sigma_max, self.sigma_data = sigma_min, sigma_max, sigma_data
+    self._prior_scale = sigma_max
+    self.eps = sigma_min
+
+  @property
+  def T(self):
+    return self.sigma_max
+
+  def sde(self, x, t):
+    return torch.zeros_like(x), torch.sqrt(2. * t)
+
+  def marginal_prob(self, x, t):
+    return x, t
+
+  def get_t_min(self, config):
+    return self.eps
+
+
 # ---- factory --------------------------------------------------------------------------------------------------------
 def get_sde(config, state):
   """Factory keyed on ``config.training.sde`` (sde_lib.py:433-445)."""
@@ -372,4 +406,8 @@ def get_sde(config, state):
     return VESDE(sigma_min=m.sigma_min, sigma_max=m.sigma_max, N=m.num_scales)
   if kind == 'reciprocal_vesde':
     return reciprocal_VESDE(sigma_min=m.sigma_min, sigma_max=m.sigma_max, N=m.num_scales, eta=tr.eta)
+  if kind == 'edm':
+    from .models.utils import config_option
+    return EDM(sigma_min=config_option(config, 'model', 'sigma_min', 0.002), sigma_max=config_option(config, 'model', 'sigma_max', 80),
+               sigma_data=config_option(config, 'model', 'sigma_data', 0.5), N=config_option(config, 'model', 'num_scales', 1000))
   raise NotImplementedError(f"SDE {config.training.sde} unknown.")
