@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256, WPS) void gemm_kernel(ConvP p, Src q, int M, i
   const int lane = tid & 63, wid = tid >> 6;
   const float sx = pow2_scale_of(block_amax(xpart, nxpart, reinterpret_cast<float*>(lds)));
   const float sw = weight_scale(q.wp);
-  const float unscale = 1.f / (sw * sx);                                   // a power of two: exact
+  const float unscale = (1.f / sw) / sx;      // powers of two, one after the other (exact): sw sx may pass 2^127 (tiny operands)
   const int ntiles = tiles_m * tiles_n;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int tile = id % ntiles, zs = id / ntiles;
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void wgrad3_kernel(ConvP p, int tiles_m, int t
   const int lane = tid & 63, wid = tid >> 6;
   const float sa = pow2_scale_of(block_amax(dypart, NPART, reinterpret_cast<float*>(lds)));
   const float sb = pow2_scale_of(block_amax(xpart, nxpart, reinterpret_cast<float*>(lds)));
-  const float unscale = 1.f / (sa * sb);
+  const float unscale = (1.f / sa) / sb;      // in turn: sa sb may pass 2^127
   const int ntiles = tiles_m * tiles_n;
   const int id = xcd_remap(blockIdx.x, gridDim.x);       // kernel row fastest: the three blocks share dy / x panels
   const int kh = id % 3;
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(256) void wgemm_kernel(ConvP p, int M, int Nn, int 
   const int lane = tid & 63, wid = tid >> 6;
   const float sa = pow2_scale_of(block_amax(dypart, NPART, reinterpret_cast<float*>(lds)));
   const float sb = pow2_scale_of(block_amax(xpart, nxpart, reinterpret_cast<float*>(lds)));
-  const float unscale = 1.f / (sa * sb);
+  const float unscale = (1.f / sa) / sb;      // in turn: sa sb may pass 2^127
   const int ntiles = tiles_m * tiles_n;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int zb = id % taps_z;

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(ConvP p, x2::Src q, int M,
 #undef STK_D_FRAGS
 #undef STK_D_FRAGS_AT
 
-  const float unscale = 1.f / (sw * x2::pow2_scale_of(xmax.reduce(red_amax, tid)));
+  const float unscale = (1.f / sw) / x2::pow2_scale_of(xmax.reduce(red_amax, tid));      // in turn: the product of the scales may pass 2^127
   ep.stage(lds, tid);
   ep.init(p, 0, zs);
 #pragma unroll
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(ConvP p, x2::Src q, i
 #undef STK_H_MFMAS
 #undef STK_H_FRAGS
 
-  const float unscale = 1.f / (sw * x2::pow2_scale_of(xmax.reduce(red_amax, tid)));
+  const float unscale = (1.f / sw) / x2::pow2_scale_of(xmax.reduce(red_amax, tid));      // in turn: the product of the scales may pass 2^127
   ep.stage(lds, tid);
   ep.init(p, 0, 0);
 #pragma unroll

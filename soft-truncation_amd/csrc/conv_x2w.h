@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256 * (FORM & 15), 2) void wgrad_kernel(Args a) {
   const int tid_late = wid * 64 + lane_late;
   const float sa = x2::pow2_scale_of(amax_dy.reduce(red_amax[0][grp], tid_late));
   const float sb = x2::pow2_scale_of(amax_x.reduce(red_amax[1][grp], tid_late));
-  const float unscale = 1.f / (sa * sb);
+  const float unscale = (1.f / sa) / sb;      // in turn: sa sb may pass 2^127 (tiny operands)
   if (GROUPS == 2) {
     // group 1 -> group 0, three taps (48 floats per thread, 48 KB) per round through group 0's stages; element (t, e) of
     // thread tid at float (16 t + e) 256 + tid: conflict-free for writer and reader

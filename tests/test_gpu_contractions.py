@@ -413,8 +413,17 @@ WGRAD_CASES = [
 def test_weight_gradient_from_planes(hip_lib, case):
   """dw += alpha sum dy x with both operands as planes, through the default launch (256 workgroups) and with 512, each
   twice; dy spread over 4 decades per image.  The error is relative to max|alpha sum dy x|, not to the accumulated dw."""
+  _weight_gradient_from_planes(hip_lib, case, tiny=False)
+
+
+def test_weight_gradient_from_planes_tiny_operands(hip_lib):
+  """The same with max|x| = 2^-60 and max|dy| = 2^-50 into a zero dw: the two scales multiply to 2^136, past fp32, and the
+  gradient (about 2^-105) is a normal fp32 number.  `unscale` formed as 1 / (sa sb) is 0 there and dw stays 0."""
+  _weight_gradient_from_planes(hip_lib, ('w8', 128, 256, 256, 8, 16), tiny=True)
+
+
+def _weight_gradient_from_planes(lib, case, tiny):
   form, N, Cin, Cout, H, slabs = case
-  lib = hip_lib
   _size_gate(lib, 2.0 * N * H * H * Cin * Cout * 9)
   assert int(lib.conv2d_wgrad_pl_ok(N, H, H, Cin, Cout)) == 1
   nb = int(lib.conv2d_wgrad_pl_ws_bytes(N, H, H, Cin, Cout))
@@ -424,6 +433,9 @@ def test_weight_gradient_from_planes(hip_lib, case):
   x = rnd(N, Cin, H, H, seed=41)
   dy = rnd(N, Cout, H, H, seed=42) * _spread(N, 3)
   dw0 = rnd(Cout, Cin, 3, 3, seed=43)
+  if tiny:
+    x, dy = x / x.abs().max() * 2.0 ** -60, dy / dy.abs().max() * 2.0 ** -50
+    dw0 = torch.zeros_like(dw0)
   alpha = 0.5
   xd, dyd = x.to(d), dy.to(d)
   rx, ry = _record(lib, xd), _record(lib, dyd)
