@@ -17,10 +17,10 @@ from . import op
 from .models import utils as _mutils  # noqa: F401
 from .models import ema, layers, layerspp, ncsnpp, up_or_down_sampling  # noqa: F401
 from . import models
-from . import adaptive_sde, controllable_generation, dpm_solver, edm, likelihood, losses, posterior_sampling, sampling, sampling_lib, utils
+from . import adaptive_sde, consistency, controllable_generation, dpm_solver, edm, likelihood, losses, posterior_sampling, sampling, sampling_lib, utils
 
 __all__ = ['configs', 'datasets', 'sde_lib', 'op', 'models', 'likelihood', 'losses', 'sampling', 'sampling_lib', 'utils',
-           'controllable_generation', 'dpm_solver', 'adaptive_sde', 'posterior_sampling', 'edm', 'install']
+           'controllable_generation', 'dpm_solver', 'adaptive_sde', 'posterior_sampling', 'edm', 'consistency', 'install']
 
 # name the reference's modules import under -> our module
 _REFERENCE_NAMES = {
@@ -33,6 +33,7 @@ _REFERENCE_NAMES = {
   'adaptive_sde': adaptive_sde, # the adaptive-step SDE sampler; neither the reference nor score_sde has such a module
   'posterior_sampling': posterior_sampling,   # the DPS sampler; neither the reference nor score_sde has such a module
   'edm': edm,                   # the EDM schedule and Heun sampler; neither the reference nor score_sde has such a module
+  'consistency': consistency,   # consistency training's definitions and sampler; neither the reference nor score_sde has one
   'utils': utils,
   'op': op,
   'models': models,

@@ -293,3 +293,22 @@ def edm(config, sigma_min=0.002, sigma_max=80., sigma_data=0.5, p_mean=-1.2, p_s
   s.edm_steps, s.edm_rho = steps, rho
   s.edm_s_churn, s.edm_s_tmin, s.edm_s_tmax, s.edm_s_noise = 0., 0., float('inf'), 1.
   return config
+
+
+def consistency(config, s0=10, s1=1280, p_mean=-1.1, p_std=2.0, huber_c=0.00054, levels=None, clip=True, **edm_options):
+  """The consistency-training variant of any config above (Song & Dhariwal 2023, iCT): :func:`edm` of it (``edm_options`` are
+  its keywords) with ``training.consistency`` on -- the discretised log-normal over neighbouring levels, the curriculum from
+  ``s0 + 1`` to ``s1 + 1`` levels over ``training.n_iters`` steps, the pseudo-Huber constant ``huber_c`` sqrt(C H W) -- and the
+  consistency sampler at `levels` (``(sigma_max,)`` where None: one network evaluation per sample; the paper's two-step
+  CIFAR-10 setting is ``(80, 0.821)``), clamped to the data range under `clip`."""
+  config = edm(config, **edm_options)
+  t = config.training
+  t.consistency = True
+  t.ct_p_mean, t.ct_p_std = p_mean, p_std
+  t.ct_s0, t.ct_s1 = s0, s1
+  t.ct_huber_c = huber_c
+  s = config.sampling
+  s.method = 'consistency'
+  s.ct_levels = (config.model.sigma_max,) if levels is None else tuple(levels)
+  s.ct_clip = clip
+  return config

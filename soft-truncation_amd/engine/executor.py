@@ -468,6 +468,21 @@ class Executor:
     self._awaiting = weakref.WeakSet()
     self.mode = 'fp32'       # precision of forward-only evaluations (Executor.precision)
     self.train_mode = 'fp32'  # precision of evaluations a backward may follow (Executor.training_precision)
+    self._pinned_seed = None  # the dropout seed of every evaluation inside Executor.dropout_seed, else None
+
+  @contextlib.contextmanager
+  def dropout_seed(self, seed):
+    """Every training-mode evaluation inside the block uses the dropout seed `seed` (an integer in [0, 2^62)) instead of
+    drawing one: evaluations of one program under one seed see the same masks (consistency training: the student and its
+    stop-gradient target).  Nothing is drawn inside the block; outside it the per-evaluation draw is what it was."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 62:
+      raise ValueError(f'a dropout seed lies in [0, 2^62), got {seed!r}')
+    saved, self._pinned_seed = self._pinned_seed, seed
+    try:
+      yield self
+    finally:
+      self._pinned_seed = saved
 
   @contextlib.contextmanager
   def precision(self, precision):
@@ -703,7 +718,7 @@ class Executor:
       prog.build_gn_folds(flat.grad.data_ptr())          # allocation + upload: never inside a hipGraph capture
     seed = 0
     if training and self._uses_dropout():
-      seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+      seed = self._pinned_seed if self._pinned_seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
     c.uses += 1
     done = False
     if self._graphs_on() and c.uses > 1:          # first use of a context runs eagerly (warm-up)

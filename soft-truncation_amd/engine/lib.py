@@ -213,6 +213,16 @@ SIGNATURES_EDM = {
   'stk_edm_step_f32': [P, P, P, P, F, F, F, F, F, P, P, P, L, S],
 }
 _RESTYPE_EDM = {'stk_edm_ws_bytes': c_long}
+# include/stk_consistency.h: the coefficients, the input pair, the loss pair and the sampler step of consistency training.
+SIGNATURES_CONSISTENCY = {
+  'stk_ct_coeffs_f32': [P, P, F, F, P, I, S],
+  'stk_ct_pair_f32': [P, P, P, P, P, I, L, S],
+  'stk_ct_ws_bytes': [I, L],
+  'stk_ct_loss_f32': [P, P, P, P, P, P, P, F, P, L, P, P, P, I, L, I, S],
+  'stk_ct_loss_grad_f32': [P, P, P, P, I, L, S],
+  'stk_ct_step_f32': [P, P, P, F, F, F, F, F, F, P, P, P, L, S],
+}
+_RESTYPE_CONSISTENCY = {'stk_ct_ws_bytes': c_long}
 # include/stk_guided.h: the per-sample order statistic and the launches of dynamic thresholding and guidance rescale around it.
 SIGNATURES_GUIDED = {
   'stk_guided_ws_bytes': [I, L],
@@ -245,6 +255,7 @@ OPTIONAL_HEADERS = (
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
+  Header('has_consistency', 'include/stk_consistency.h', SIGNATURES_CONSISTENCY, _RESTYPE_CONSISTENCY, ()),
   Header('has_edm', 'include/stk_edm.h', SIGNATURES_EDM, _RESTYPE_EDM, ()),
   Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),
 )

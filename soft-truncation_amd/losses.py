@@ -15,6 +15,7 @@ The soft-truncation loss itself (time sampling, perturbation, weighting) is per-
 math plus a few element-wise passes over the [B,3,H,W] batch; it is written with the same torch
 expression order as the reference so results are bit-identical on identical inputs.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -375,8 +376,184 @@ def get_edm_loss_fn(config, sde, train):
   return loss_fn
 
 
+class _CtLoss(torch.autograd.Function):
+  """losses[b] = lambda_b (sqrt(S + c^2) - c) (/ inner), S = sum r^2, r = f(y + sigma_hi n; sigma_hi) - f(y + sigma_lo n;
+  sigma_lo): the tail of the consistency loss on the two raw network outputs as stk_ct_loss_f32 (include/stk_consistency.h),
+  which keeps r and the per-sample factor of the gradient; the backward is stk_ct_loss_grad_f32 IN PLACE on that r (28 B per
+  element for the pair), so a second backward through the same evaluation is refused.  F_lo is the stop-gradient target: it
+  receives no gradient."""
+
+  @staticmethod
+  def forward(ctx, F_hi, F_lo, y, n, sigma_hi, sigma_lo, coef, huber_c, lib, reduce_mean):
+    from .engine import lib as stk_lib
+    F_hi, F_lo = F_hi.contiguous(), F_lo.contiguous()
+    B, inner = F_hi.shape[0], F_hi[0].numel()
+    key = ('ct_ws', B, inner, F_hi.device)
+    ws = _fused_bufs.get(key)
+    if ws is None:       # per batch shape: the partial sums, consumed by the finishing pass of the same call
+      ws_bytes = int(lib.ct_ws_bytes(B, inner))
+      if ws_bytes < 0:
+        raise ValueError(f'stk_ct_ws_bytes refuses a batch of {B} rows of {inner} (rc={ws_bytes})')
+      ws = _fused_bufs[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=F_hi.device)
+    keep = ctx.needs_input_grad[0]
+    r = torch.empty_like(F_hi) if keep else None
+    gfac = torch.empty(B, dtype=torch.float32, device=F_hi.device) if keep else None
+    losses = torch.empty(B, dtype=torch.float32, device=F_hi.device)
+    with stk_lib.device_guard(F_hi.device):
+      lib.ct_loss_f32(F_hi.data_ptr(), F_lo.data_ptr(), y.data_ptr(), n.data_ptr(), sigma_hi.data_ptr(), sigma_lo.data_ptr(),
+                      coef.data_ptr(), huber_c, ws.data_ptr(), ws.numel(), r.data_ptr() if keep else None,
+                      gfac.data_ptr() if keep else None, losses.data_ptr(), B, inner, int(reduce_mean),
+                      stk_lib.stream_ptr(F_hi.device))
+    ctx.args = (lib, B, inner, r, gfac)
+    return losses
+
+  @staticmethod
+  def backward(ctx, dloss):
+    from .engine import lib as stk_lib
+    lib, B, inner, r, gfac = ctx.args
+    if r is None:
+      raise RuntimeError('the consistency loss kept its residual once: a second backward through the same evaluation is not '
+                         'possible')
+    ctx.args = (lib, B, inner, None, None)
+    dloss = dloss.contiguous()
+    with stk_lib.device_guard(r.device):
+      lib.ct_loss_grad_f32(r.data_ptr(), gfac.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, stk_lib.stream_ptr(r.device))
+    return (r,) + (None,) * 9
+
+
+class ConsistencyLoss:
+  """What :func:`get_consistency_loss_fn` returns: ``loss_fn(model, batch, importance_sampling=None, t_min=None, levels=None)
+  -> [B]`` with the curriculum's state.  ``N``: the number of levels in force;  ``set_step(k)``: N of training step k
+  (get_step_fn calls it with ``state['step']`` before the micro-batches), the level grid and the index distribution cached
+  per N."""
+
+  def __init__(self, config, sde, train):
+    from . import consistency
+    mutils.check_edm_config(config, training=True)
+    if not isinstance(sde, EDM):
+      raise ValueError(f'get_consistency_loss_fn needs sde_lib.EDM, got {type(sde).__name__}')
+    self._ct = consistency
+    self.config, self.sde, self.train = config, sde, train
+    self.p_mean, self.p_std, self.s0, self.s1, huber_c = consistency.training_options(config)
+    self.huber_c = huber_c
+    self.K = int(mutils.config_option(config, 'training', 'n_iters', 1))
+    self.s_data, self.s_min = float(sde.sigma_data), mutils.ct_sigma_min(sde)
+    self.reduce_mean = bool(config.training.reduce_mean)
+    self._tables = {}       # N -> (levels, pmf), float64 numpy
+    self._device = {}       # (N, device) -> (levels fp32, pmf fp32) on the device
+    self.step = None
+    self.N = None
+    self.set_step(0)
+
+  def set_step(self, k):
+    self.step = int(k)
+    self.N = self._ct.ct_num_levels(self.step, self.K, self.s0, self.s1)
+    return self.N
+
+  def tables(self, N=None):
+    """(levels [N], pmf [N - 1]) of N levels (the N in force where None), float64 numpy."""
+    N = self.N if N is None else N
+    hit = self._tables.get(N)
+    if hit is None:
+      levels = self._ct.ct_levels(self.sde, N)
+      hit = self._tables[N] = (levels, self._ct.ct_index_pmf(levels, self.p_mean, self.p_std))
+    return hit
+
+  def _on_device(self, device):
+    key = (self.N, device)
+    hit = self._device.get(key)
+    if hit is None:
+      levels, pmf = self.tables()
+      hit = self._device[key] = (torch.tensor(levels, dtype=torch.float32).to(device), torch.tensor(pmf, dtype=torch.float32).to(device))
+    return hit
+
+  def _fused(self, lib, F_fn, batch, sigma_hi, sigma_lo, n, pinned):
+    from .engine import lib as stk_lib
+    B = batch.shape[0]
+    y = batch.contiguous()
+    inner = y[0].numel()
+    coef = torch.empty((11, B), dtype=torch.float32, device=y.device)
+    xin_hi, xin_lo = torch.empty_like(y), torch.empty_like(y)
+    with stk_lib.device_guard(y.device):
+      stream = stk_lib.stream_ptr(y.device)
+      lib.ct_coeffs_f32(sigma_hi.data_ptr(), sigma_lo.data_ptr(), self.s_data, self.s_min, coef.data_ptr(), B, stream)
+      lib.ct_pair_f32(y.data_ptr(), n.data_ptr(), coef.data_ptr(), xin_hi.data_ptr(), xin_lo.data_ptr(), B, inner, stream)
+    with pinned():
+      with torch.no_grad():
+        F_lo = F_fn(xin_lo, coef[9])
+      F_hi = F_fn(xin_hi, coef[4])
+    c = self.huber_c * float(np.sqrt(inner))
+    return _CtLoss.apply(F_hi, F_lo, y, n, sigma_hi, sigma_lo, coef, c, lib, self.reduce_mean)
+
+  def _torch(self, F_fn, batch, sigma_hi, sigma_lo, n, pinned):
+    f32 = lambda rows: tuple(v.to(torch.float32) for v in rows)
+    cin_h, cis_h, csk_h, cou_h, cn_h = f32(mutils.ct_coefficients(sigma_hi, self.s_data, self.s_min))
+    cin_l, cis_l, csk_l, cou_l, cn_l = f32(mutils.ct_coefficients(sigma_lo, self.s_data, self.s_min))
+    lam = 1. / (sigma_hi.double() - sigma_lo.double())
+    with pinned():
+      with torch.no_grad():
+        F_lo = F_fn(_wide(cin_l) * batch + _wide(cis_l) * n, cn_l)
+      F_hi = F_fn(_wide(cin_h) * batch + _wide(cis_h) * n, cn_h)
+    f_hi = _wide(csk_h) * (batch + _wide(sigma_hi) * n) + _wide(cou_h) * F_hi
+    f_lo = _wide(csk_l) * (batch + _wide(sigma_lo) * n) + _wide(cou_l) * F_lo.detach()
+    r = f_hi - f_lo
+    inner = float(np.prod(batch.shape[1:]))
+    c = float(np.float32(self.huber_c * float(np.sqrt(inner))))
+    S = (r * r).double().reshape(r.shape[0], -1).sum(dim=-1)
+    total = (lam * S) / (torch.sqrt(S + c * c) + c)
+    if self.reduce_mean:
+      total = total / inner
+    return total.to(torch.float32)
+
+  def __call__(self, model, batch, importance_sampling=None, t_min=None, levels=None):
+    B = batch.shape[0]
+    if levels is None:
+      lv, pmf = self._on_device(batch.device)
+      idx = torch.multinomial(pmf, B, replacement=True)
+      sigma_hi, sigma_lo = lv[idx + 1], lv[idx]
+    else:
+      sigma_hi, sigma_lo = (v.to(device=batch.device, dtype=torch.float32).contiguous() for v in levels)
+    n = torch.randn_like(batch)
+    net = getattr(model, 'module', model)
+    uses_dropout = getattr(net, '_uses_dropout', None)
+    engine = getattr(net, 'engine', None)
+    pinned = contextlib.nullcontext
+    if self.train and callable(uses_dropout) and uses_dropout():
+      # ONE seed for both evaluations: the student and its stop-gradient target see the same dropout masks
+      seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+      if callable(engine):
+        pinned = lambda: engine().dropout_seed(seed)
+    F_fn = mutils.get_edm_model_fn(self.config, model, train=self.train)
+    lib = _engine_lib(model, batch) if FUSED_LOSS else None
+    if lib is not None and lib.has_consistency:
+      return self._fused(lib, F_fn, batch, sigma_hi.contiguous(), sigma_lo.contiguous(), n.contiguous(), pinned)
+    return self._torch(F_fn, batch, sigma_hi, sigma_lo, n, pinned)
+
+
+def get_consistency_loss_fn(config, sde, train):
+  """The consistency-training loss of iCT (Song & Dhariwal 2023) on sde_lib.EDM, chosen by ``training.consistency``: a
+  :class:`ConsistencyLoss`, ``loss_fn(model, batch, importance_sampling=None, t_min=None, levels=None) -> [B]``, the first two
+  keywords accepted and unused.  Per evaluation, in this order: ``torch.multinomial(pmf, B, replacement=True)`` on the batch's
+  device for the pair index i (``levels = (sigma_hi, sigma_lo)``, two [B] tensors, replaces this draw), ``torch.randn_like(
+  batch)`` for the ONE noise n of both levels, and -- only for a model in training mode that uses dropout -- one
+  ``torch.randint(0, 2**62, (1,))``, the dropout seed both evaluations share (``Executor.dropout_seed``).  With the rows of
+  include/stk_consistency.h at (sigma_hi, sigma_lo) = (sigma_{i+1}, sigma_i) of the N levels in force,
+
+    F_lo = network(c_in y + (c_in sigma) n, c_noise) at sigma_lo under ``torch.no_grad()``: the stop-gradient target, first;
+    F_hi = the same at sigma_hi with gradient: the student (one backward per step);
+    r = f(y + sigma_hi n; sigma_hi) - f(y + sigma_lo n; sigma_lo);  S = sum r^2;  lambda = 1 / (sigma_hi - sigma_lo);
+    loss[b] = lambda S / (sqrt(S + c^2) + c),  c = ``training.ct_huber_c`` sqrt(C H W)   (/ C H W under ``reduce_mean``)
+
+  every element in fp32 in that order, the squares summed in float64.  On an engine model with a device fp32 batch, a library
+  with the header and STK_FUSED_LOSS != 0 this is stk_ct_coeffs_f32, stk_ct_pair_f32, the network twice and stk_ct_loss_f32 /
+  stk_ct_loss_grad_f32; otherwise the same expressions by torch operators around any callable network."""
+  return ConsistencyLoss(config, sde, train)
+
+
 def _pick_loss_fn(config, sde, train):
   if isinstance(sde, EDM):
+    if mutils.config_option(config, 'training', 'consistency', False):
+      return get_consistency_loss_fn(config, sde, train)
     return get_edm_loss_fn(config, sde, train)
   if config.training.continuous:
     return get_sde_loss_fn(config, sde, train)
@@ -510,6 +687,8 @@ def get_step_fn(config, sde, train, optimize_fn=None):
     out_per = per // 2 if mixed else per
     losses_ = torch.zeros(n // 2 if mixed else n)
     t_min = sde.get_t_min(config)
+    if hasattr(loss_fn, 'set_step'):     # a loss with a curriculum (the consistency loss): the levels of this step
+      loss_fn.set_step(state['step'])
     pinned, copied = None, None
     ddp.begin_step(model)
     try:

@@ -383,6 +383,41 @@ def get_edm_model_fn(config, model, train=False):
   return model_fn
 
 
+def ct_coefficients(sigma, sigma_data, sigma_min):
+  """The five rows of one level of include/stk_consistency.h -- c_in, c_in sigma, c_skip, c_out, c_noise = ln(sigma) / 4 of the
+  consistency function, whose c_skip = 1 and c_out = 0 at sigma = sigma_min -- of the [B] tensor `sigma`, in float64 in the
+  header's operation order; the caller rounds them."""
+  S, d, e = sigma.double(), float(sigma_data), float(sigma_min)
+  v = S * S + d * d
+  q = torch.sqrt(v)
+  g = S - e
+  w = g * g + d * d
+  return 1. / q, S / q, (d * d) / w, (d * g) / q, torch.log(S) / 4.
+
+
+def ct_sigma_min(sde):
+  """sigma_min as the kernels and the levels carry it: rounded to fp32, so that the lowest level meets it exactly."""
+  return float(np.float32(sde.sigma_min))
+
+
+def get_consistency_fn(config, sde, model, train=False):
+  """``f(x, sigma) = c_skip x + c_out F(c_in x; c_noise)``: the consistency function around the raw network (consistency.py,
+  include/stk_consistency.h) at the [B] levels `sigma`, by torch operators -- autograd sees it -- for users' own loops.  The
+  network is conditioned exactly as :func:`get_edm_model_fn` does; f(x, sigma_min) = x."""
+  if not isinstance(sde, sde_lib.EDM):
+    raise ValueError(f'the consistency function needs sde_lib.EDM (config.training.sde = \'edm\'), got {type(sde).__name__}')
+  check_edm_config(config)
+  F = get_edm_model_fn(config, model, train)
+  s, e = float(sde.sigma_data), ct_sigma_min(sde)
+
+  def consistency_fn(x, sigma):
+    c_in, _, c_skip, c_out, c_noise = (v.to(torch.float32) for v in ct_coefficients(sigma, s, e))
+    out = F(c_in[:, None, None, None] * x, c_noise)
+    return c_skip[:, None, None, None] * x + c_out[:, None, None, None] * out
+
+  return consistency_fn
+
+
 def _edm_score_fn(config, sde, model, train):
   """score(x, sigma) = (D(x; sigma) - x) / sigma^2 = -c_in^2 x + (s c_in / sigma) F(c_in x; c_noise), by torch operators
   (autograd sees it: the likelihood, DPS and class_condition work as for the other families).  Classifier-free guidance acts

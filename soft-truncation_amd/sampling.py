@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import adaptive_sde, dpm_solver, edm, sde_lib
+from . import adaptive_sde, consistency, dpm_solver, edm, sde_lib
 from .engine import rk45
 from .models import utils as mutils
 from .models.utils import from_flattened_numpy, get_score_fn, to_flattened_numpy
@@ -318,7 +318,8 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   dpm_threshold_floor``) or 'adaptive'
   (adaptive_sde.py; ``config.sampling.adaptive_rtol / adaptive_atol / adaptive_h_init / adaptive_safety / adaptive_exponent``)
   or 'edm' (edm.py, on sde_lib.EDM alone; ``config.sampling.edm_steps / edm_rho / edm_s_churn / edm_s_tmin / edm_s_tmax /
-  edm_s_noise``; it runs down to noise level 0, so `eps` and ``noise_removal`` do not apply)."""
+  edm_s_noise``; it runs down to noise level 0, so `eps` and ``noise_removal`` do not apply) or 'consistency'
+  (consistency.py, on sde_lib.EDM alone; ``config.sampling.ct_levels / ct_clip``; one network evaluation per level)."""
   s = config.sampling
   kind = s.method.lower()
   precision = mutils.sampling_precision(config)
@@ -351,6 +352,10 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
     return edm.get_edm_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=steps, rho=rho,
                                s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, device=config.device,
                                precision=precision)
+  if kind == 'consistency':
+    levels, clip = consistency.sampling_options(config)
+    return consistency.get_consistency_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler,
+                                               levels=levels, clip=clip, device=config.device, precision=precision)
   raise ValueError(f"Sampler name {s.method} unknown.")
 
 
