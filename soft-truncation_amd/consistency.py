@@ -40,8 +40,7 @@ def _library():
   return mutils.require('has_consistency', 'stk_consistency.h', 'stk_ct_step_f32', 'the consistency sampler needs')
 
 
-def _fp32(v):
-  return np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+_fp32, _ptr = mutils.fp32_levels, mutils.optional_ptr
 
 
 def _need_edm(sde, who):
@@ -142,19 +141,9 @@ def consistency_schedule(sde, levels=None, clip=True):
 def _step(lib, x, F, z, row, lo, hi, x0_out, x_out, xin_out):
   """One launch of stk_ct_step_f32 on contiguous fp32 device tensors.  row: (cs, co, c_z, c_in_next, ...)."""
   cs, co, c_z, c_next = (float(v) for v in row[:4])
-  ptr = lambda t: None if t is None else t.data_ptr()
   with stk_lib.device_guard(x.device):
-    lib.ct_step_f32(x.data_ptr(), F.data_ptr(), ptr(z), cs, co, float(lo), float(hi), c_z, c_next, ptr(x0_out), ptr(x_out),
-                    ptr(xin_out), x.numel(), stk_lib.stream_ptr(x.device))
-
-
-def _evaluate(model_fn, xin, c_noise, lib):
-  """``model_fn(xin, c_noise)``, which must be a float32 tensor of xin's shape on the library's device, made contiguous."""
-  F = model_fn(xin, c_noise)
-  _backend.check(F, lib)
-  if F.shape != xin.shape or F.dtype != torch.float32:
-    raise ValueError(f'the network returned {F.dtype} {tuple(F.shape)} for a float32 input {tuple(xin.shape)}')
-  return F.contiguous()
+    lib.ct_step_f32(x.data_ptr(), F.data_ptr(), _ptr(z), cs, co, float(lo), float(hi), c_z, c_next, _ptr(x0_out), _ptr(x_out),
+                    _ptr(xin_out), x.numel(), stk_lib.stream_ptr(x.device))
 
 
 def consistency_sample(model_fn, schedule, x, noise_fn=None):
@@ -170,10 +159,9 @@ def consistency_sample(model_fn, schedule, x, noise_fn=None):
   mutils.check_inplace_state(z, lib, why='the kernels read it in place')
   torch.mul(z, float(schedule.levels[0]), out=x)
   xin = x * float(schedule.c_in_first)
-  # the conditioning vectors of all evaluations, one host-to-device copy per run
-  cond = torch.tensor(schedule.rows[:, 4], dtype=torch.float32).to(x.device)[:, None].expand(-1, B).contiguous()
+  cond = mutils.level_conditioning(schedule.rows[:, 4], B, x.device)       # the conditioning vectors of all evaluations
   for j in range(n):
-    F = _evaluate(model_fn, xin, cond[j], lib)
+    F = mutils.checked_score(model_fn, xin, cond[j], lib)
     if j == n - 1:
       _step(lib, x, F, None, schedule.rows[j], schedule.lo, schedule.hi, x, None, None)
       break

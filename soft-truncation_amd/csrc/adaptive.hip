@@ -27,17 +27,15 @@ struct StageArgs {
 // row: items of V elements per sample.
 template <int V>
 __global__ __launch_bounds__(256) void sde_stage_kernel(unsigned row, int B, StageArgs a) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     const float ca = a.coef[4 * b], cs = a.coef[4 * b + 2], cn = a.coef[4 * b + 3];
     const float cp = a.xp ? a.coef[4 * b + 1] : 0.f;
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto xv = Vec<V>::load(a.x, base + i);
-      const auto sv = Vec<V>::load(a.score, base + i);
-      const auto zv = Vec<V>::load(a.z, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto xv = Vec<V>::load(a.x, i);
+      const auto sv = Vec<V>::load(a.score, i);
+      const auto zv = Vec<V>::load(a.z, i);
       Vec<V> pv, o;
-      if (a.xp) pv = Vec<V>::load(a.xp, base + i);
+      if (a.xp) pv = Vec<V>::load(a.xp, i);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         float r = ca * xv.v[j];
@@ -45,9 +43,9 @@ __global__ __launch_bounds__(256) void sde_stage_kernel(unsigned row, int B, Sta
         r = r + cs * sv.v[j];
         o.v[j] = r + cn * zv.v[j];
       }
-      o.store(a.out, base + i);
-    }
-  }
+      o.store(a.out, i);
+    });
+  });
 }
 
 struct HeunArgs {
@@ -59,17 +57,15 @@ struct HeunArgs {
 template <int V>
 __global__ __launch_bounds__(256) void sde_heun_error_kernel(unsigned row, int B, HeunArgs a) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     const float ca = a.coef[4 * b], cp = a.coef[4 * b + 1], cs = a.coef[4 * b + 2], cn = a.coef[4 * b + 3];
-    const unsigned base = (unsigned)b * row;
     double acc = 0.;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto xv = Vec<V>::load(a.x, base + i);
-      const auto x1v = Vec<V>::load(a.x1, base + i);
-      const auto pv = Vec<V>::load(a.x1_prev, base + i);
-      const auto sv = Vec<V>::load(a.score2, base + i);
-      const auto zv = Vec<V>::load(a.z, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto xv = Vec<V>::load(a.x, i);
+      const auto x1v = Vec<V>::load(a.x1, i);
+      const auto pv = Vec<V>::load(a.x1_prev, i);
+      const auto sv = Vec<V>::load(a.score2, i);
+      const auto zv = Vec<V>::load(a.z, i);
       Vec<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
@@ -82,11 +78,10 @@ __global__ __launch_bounds__(256) void sde_heun_error_kernel(unsigned row, int B
         acc += (double)qq;
         o.v[j] = x2;
       }
-      o.store(a.x2, base + i);
-    }
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) a.ws[(size_t)b * gridDim.x + blockIdx.x] = acc;
-  }
+      o.store(a.x2, i);
+    });
+    row_store_partial(acc, red, a.ws, b);
+  });
 }
 
 struct CommitArgs {
@@ -101,11 +96,8 @@ struct CommitArgs {
 template <int V>
 __global__ __launch_bounds__(256) void sde_commit_kernel(unsigned row, int B, CommitArgs a) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    double acc = 0.;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += 256) acc += a.ws[(size_t)b * gridDim.x + j];
-    acc = block_sum_f64(acc, red);
+  row_samples(B, [&](int b) {
+    const double acc = row_sum_partial(a.ws, b, gridDim.x, red);
     const float E = sqrtf((float)(acc / a.n));
     const float t = a.t[b], h = a.h[b];
     const bool active = t > a.eps;
@@ -125,46 +117,33 @@ __global__ __launch_bounds__(256) void sde_commit_kernel(unsigned row, int B, Co
       a.E_out[b] = E;
       a.accept_out[b] = accept ? 1 : 0;
     }
-    if (!accept) continue;                               // uniform over the block
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto v2 = Vec<V>::load(a.x2, base + i);
-      const auto v1 = Vec<V>::load(a.x1, base + i);
-      v2.store(a.x, base + i);
-      v1.store(a.x1_prev, base + i);
+    if (accept) {                                        // uniform over the block
+      row_items(row, b, [&](unsigned i) {
+        const auto v2 = Vec<V>::load(a.x2, i);
+        const auto v1 = Vec<V>::load(a.x1, i);
+        v2.store(a.x, i);
+        v1.store(a.x1_prev, i);
+      });
     }
-  }
-}
-
-// 0, or the code every entry returns for these sizes.
-int check_sizes(int B, long n) {
-  if (B <= 0 || n <= 0) return STK_EINVAL;
-  if (n >= (1L << 31) || (long)B * n >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
-}
-
-bool ws_ok(const void* ws, long ws_bytes, int B, long n) {
-  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)B * stk_row_parts(B, n) * (long)sizeof(double);
+  });
 }
 
 }  // namespace
 
 extern "C" long stk_sde_ws_bytes(int B, long n_per_sample) {
-  const int rc = check_sizes(B, n_per_sample);
+  const int rc = stk_row_check(B, n_per_sample);
   if (rc != STK_OK) return rc;
-  return (long)B * stk_row_parts(B, n_per_sample) * (long)sizeof(double);
+  return stk_row_ws_bytes(B, n_per_sample);
 }
 
 extern "C" int stk_sde_stage_f32(const float* x, const float* xp, const float* score, const float* z, const float* coef,
                                  float* out, int B, long n, void* stream) {
   if (!x || !score || !z || !coef || !out) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, z, out, xp);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
+  const StkRowPlan p = stk_row_plan(B, n, x, score, z, out, xp);
   StageArgs a{x, xp, score, z, coef, out};
-  return stk_launch_vec(vec, sde_stage_kernel<4>, sde_stage_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return stk_launch_vec(p.vec, sde_stage_kernel<4>, sde_stage_kernel<1>, p.grid, (hipStream_t)stream, p.row, B, a);
 }
 
 extern "C" int stk_sde_heun_error_f32(const float* x, const float* x1, const float* x1_prev, const float* score2,
@@ -172,14 +151,12 @@ extern "C" int stk_sde_heun_error_f32(const float* x, const float* x1, const flo
                                       long ws_bytes, int B, long n, void* stream) {
   if (!x || !x1 || !x1_prev || !score2 || !z || !coef || !x2 || !ws) return STK_EINVAL;
   if (!(atol >= 0.f) || !(rtol >= 0.f) || !(atol + rtol > 0.f)) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1, x1_prev, score2, z, x2);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
+  if (!stk_row_ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
+  const StkRowPlan p = stk_row_plan(B, n, x, x1, x1_prev, score2, z, x2);
   HeunArgs a{x, x1, x1_prev, score2, z, coef, x2, (double*)ws, atol, rtol};
-  return stk_launch_vec(vec, sde_heun_error_kernel<4>, sde_heun_error_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return stk_launch_vec(p.vec, sde_heun_error_kernel<4>, sde_heun_error_kernel<1>, p.grid, (hipStream_t)stream, p.row, B, a);
 }
 
 extern "C" int stk_sde_commit_f32(float* x, float* x1_prev, const float* x2, const float* x1, const float* t, const float* h,
@@ -188,12 +165,10 @@ extern "C" int stk_sde_commit_f32(float* x, float* x1_prev, const float* x2, con
   if (!x || !x1_prev || !x2 || !x1 || !t || !h || !ws || !t_out || !h_out || !E_out || !accept_out) return STK_EINVAL;
   if (t_out == t || t_out == h || h_out == t || h_out == h || t_out == h_out) return STK_EINVAL;
   if (!(eps >= 0.f) || !(safety > 0.f) || !(exponent >= 0.f)) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, x1_prev, x2, x1);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(B, n), stk_row_rows(B, n));
+  if (!stk_row_ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
+  const StkRowPlan p = stk_row_plan(B, n, x, x1_prev, x2, x1);
   CommitArgs a{x, x1_prev, x2, x1, t, h, (const double*)ws, t_out, h_out, E_out, accept_out, eps, safety, exponent, (double)n};
-  return stk_launch_vec(vec, sde_commit_kernel<4>, sde_commit_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return stk_launch_vec(p.vec, sde_commit_kernel<4>, sde_commit_kernel<1>, p.grid, (hipStream_t)stream, p.row, B, a);
 }

@@ -11,13 +11,14 @@
 // entries), so the index arithmetic is 32-bit.
 //
 // No fused multiply-add in this file (header, "Arithmetic"): the pragma below holds for every function that follows.
-// stream.h, included before it, holds loads, stores and host code only.
+// stream.h, included before it, holds loads, stores and host code only; sqloss.h (the loss, finish and gradient kernels shared
+// with edm.hip, on the scaffold of rowsum.h) holds arithmetic and follows the pragma.
 #include "stream.h"
 #include "stk_consistency.h"
 
 #pragma clang fp contract(off)
 
-#include "rowsum.h"
+#include "sqloss.h"
 
 namespace {
 
@@ -53,107 +54,63 @@ struct PairArgs {
 // row: items of V elements per sample.
 template <int V>
 __global__ __launch_bounds__(256) void ct_pair_kernel(unsigned row, int B, PairArgs a) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     const float ah = a.coef[b], sh = a.coef[(size_t)B + b], al = a.coef[5 * (size_t)B + b], sl = a.coef[6 * (size_t)B + b];
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto yv = Vec<V>::load(a.y, base + i);
-      const auto nv = Vec<V>::load(a.n, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto yv = Vec<V>::load(a.y, i);
+      const auto nv = Vec<V>::load(a.n, i);
       Vec<V> oh, ol;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         oh.v[j] = ah * yv.v[j] + sh * nv.v[j];
         ol.v[j] = al * yv.v[j] + sl * nv.v[j];
       }
-      oh.store(a.xin_hi, base + i);
-      ol.store(a.xin_lo, base + i);
-    }
-  }
+      oh.store(a.xin_hi, i);
+      ol.store(a.xin_lo, i);
+    });
+  });
 }
 
-struct LossArgs {
-  const float* F_hi; const float* F_lo; const float* y; const float* n; const float* sigma_hi; const float* sigma_lo;
-  const float* coef;
-  float* r; double* ws;
+// r = f(y + sigma_hi n; sigma_hi) - f(y + sigma_lo n; sigma_lo), every operation rounded to fp32 in that order.
+struct CtRes {
+  static constexpr int N = 4;
+  const float* in[N];                                      // F_hi, F_lo, y, n
+  const float* sigma_hi; const float* sigma_lo; const float* coef;
+  struct Row { float sh, sl, ckh, coh, ckl, col; };
+  __device__ Row row(int b, int B) const {
+    return {sigma_hi[b], sigma_lo[b], coef[2 * (size_t)B + b], coef[3 * (size_t)B + b], coef[7 * (size_t)B + b],
+            coef[8 * (size_t)B + b]};
+  }
+  __device__ static float r(const Row& c, const float* v) {
+    const float xh = v[2] + c.sh * v[3];
+    const float fh = c.ckh * xh + c.coh * v[0];
+    const float xl = v[2] + c.sl * v[3];
+    const float fl = c.ckl * xl + c.col * v[1];
+    return fh - fl;
+  }
 };
 
-template <int V>
-__global__ __launch_bounds__(256) void ct_loss_kernel(unsigned row, int B, LossArgs a) {
-  __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const float sh = a.sigma_hi[b], sl = a.sigma_lo[b];
-    const float ckh = a.coef[2 * (size_t)B + b], coh = a.coef[3 * (size_t)B + b];
-    const float ckl = a.coef[7 * (size_t)B + b], col = a.coef[8 * (size_t)B + b];
-    const unsigned base = (unsigned)b * row;
-    double acc = 0.;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto Fh = Vec<V>::load(a.F_hi, base + i);
-      const auto Fl = Vec<V>::load(a.F_lo, base + i);
-      const auto yv = Vec<V>::load(a.y, base + i);
-      const auto nv = Vec<V>::load(a.n, base + i);
-      Vec<V> o;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float xh = yv.v[j] + sh * nv.v[j];
-        const float fh = ckh * xh + coh * Fh.v[j];
-        const float xl = yv.v[j] + sl * nv.v[j];
-        const float fl = ckl * xl + col * Fl.v[j];
-        const float r = fh - fl;
-        const float q = r * r;
-        acc += (double)q;
-        o.v[j] = r;
-      }
-      if (a.r) o.store(a.r, base + i);
-    }
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) a.ws[(size_t)b * gridDim.x + blockIdx.x] = acc;
-  }
-}
-
-// One block per sample (striding): the row's partials in index order within the fixed tree, then the pseudo-Huber value in its
-// cancellation-free form and the factor of the gradient, float64, each rounded once.
-__global__ __launch_bounds__(256) void ct_loss_finish_kernel(const double* ws, const float* coef, double C, float* loss,
-                                                             float* gfac, int B, int parts, double inner, int reduce_mean) {
-  __shared__ double red[4];
-  for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    double acc = 0.;
-    for (int j = threadIdx.x; j < parts; j += 256) acc += ws[(size_t)b * parts + j];
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) {
-      const double L = (double)coef[10 * (size_t)B + b];
-      const double h = sqrt(acc + C * C);
-      const double v = (L * acc) / (h + C);
-      loss[b] = (float)(reduce_mean ? v / inner : v);
-      if (gfac) {
-        const double g = (L * (double)coef[3 * (size_t)B + b]) / h;
-        gfac[b] = (float)(reduce_mean ? g / inner : g);
-      }
+// The pseudo-Huber value of the row's sum in its cancellation-free form and the factor of the gradient, each rounded once.
+struct CtFinish {
+  const float* coef; float* loss; float* gfac;
+  double C, inner;
+  int reduce_mean;
+  __device__ void operator()(double acc, int b, int B) const {
+    const double L = (double)coef[10 * (size_t)B + b];
+    const double h = sqrt(acc + C * C);
+    const double v = (L * acc) / (h + C);
+    loss[b] = (float)(reduce_mean ? v / inner : v);
+    if (gfac) {
+      const double g = (L * (double)coef[3 * (size_t)B + b]) / h;
+      gfac[b] = (float)(reduce_mean ? g / inner : g);
     }
   }
-}
-
-struct GradArgs {
-  const float* r; const float* gfac; const float* dloss;
-  float* dF;
 };
 
-template <int V>
-__global__ __launch_bounds__(256) void ct_loss_grad_kernel(unsigned row, int B, GradArgs a) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const float k = a.gfac[b] * a.dloss[b];
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto rv = Vec<V>::load(a.r, base + i);
-      Vec<V> o;
-#pragma unroll
-      for (int j = 0; j < V; ++j) o.v[j] = k * rv.v[j];
-      o.store(a.dF, base + i);
-    }
-  }
-}
+struct CtGradFactor {
+  const float* gfac; const float* dloss;
+  __device__ float operator()(int b, int B) const { return gfac[b] * dloss[b]; }
+};
 
 struct StepArgs {
   const float* x; const float* F; const float* z;
@@ -189,31 +146,11 @@ __global__ __launch_bounds__(256) void ct_step_kernel(unsigned total, StepArgs a
   }
 }
 
-// 0, or the code every per-sample entry returns for B rows of `len` floats.
-int check_sizes(int B, long len) {
-  if (B <= 0 || len <= 0) return STK_EINVAL;
-  if (len >= (1L << 31) || (long)B * len >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
-}
-
-// ... and the sampler's entry for n elements.
-int check_length(long n) {
-  if (n <= 0) return STK_EINVAL;
-  if (n >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
-}
-
-bool ws_ok(const void* ws, long ws_bytes, int B, long inner) {
-  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)B * stk_row_parts(B, inner) * (long)sizeof(double);
-}
-
-bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }      // false for NaN and +inf
-
 }  // namespace
 
 extern "C" int stk_ct_coeffs_f32(const float* sigma_hi, const float* sigma_lo, float sigma_data, float sigma_min, float* coef,
                                  int B, void* stream) {
-  if (!sigma_hi || !sigma_lo || !coef || B <= 0 || !positive_finite(sigma_data)) return STK_EINVAL;
+  if (!sigma_hi || !sigma_lo || !coef || B <= 0 || !stk_positive_finite(sigma_data)) return STK_EINVAL;
   if (!(sigma_min >= 0.f && sigma_min <= 3.402823466e38f)) return STK_EINVAL;
   hipLaunchKernelGGL(ct_coeffs_kernel, dim3(stk_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, sigma_hi, sigma_lo,
                      (double)sigma_data, (double)sigma_min, coef, B);
@@ -224,59 +161,44 @@ extern "C" int stk_ct_coeffs_f32(const float* sigma_hi, const float* sigma_lo, f
 extern "C" int stk_ct_pair_f32(const float* y, const float* n, const float* coef, float* xin_hi, float* xin_lo, int B,
                                long inner, void* stream) {
   if (!y || !n || !coef || !xin_hi || !xin_lo) return STK_EINVAL;
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  const bool vec = (inner & 3) == 0 && stk_all_aligned16(y, n, xin_hi, xin_lo);
-  const unsigned row = (unsigned)(vec ? inner >> 2 : inner);
-  const dim3 grid(stk_row_parts(B, inner), stk_row_rows(B, inner));
+  const StkRowPlan p = stk_row_plan(B, inner, y, n, xin_hi, xin_lo);
   PairArgs a{y, n, coef, xin_hi, xin_lo};
-  return stk_launch_vec(vec, ct_pair_kernel<4>, ct_pair_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return stk_launch_vec(p.vec, ct_pair_kernel<4>, ct_pair_kernel<1>, p.grid, (hipStream_t)stream, p.row, B, a);
 }
 
 extern "C" long stk_ct_ws_bytes(int B, long inner) {
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  return (long)B * stk_row_parts(B, inner) * (long)sizeof(double);
+  return stk_row_ws_bytes(B, inner);
 }
 
 extern "C" int stk_ct_loss_f32(const float* F_hi, const float* F_lo, const float* y, const float* n, const float* sigma_hi,
                                const float* sigma_lo, const float* coef, float c, void* ws, long ws_bytes, float* r_out,
                                float* gfac_out, float* loss_out, int B, long inner, int reduce_mean, void* stream) {
   if (!F_hi || !F_lo || !y || !n || !sigma_hi || !sigma_lo || !coef || !ws || !loss_out) return STK_EINVAL;
-  if (!r_out != !gfac_out || !positive_finite(c)) return STK_EINVAL;
-  const int rc = check_sizes(B, inner);
+  if (!r_out != !gfac_out || !stk_positive_finite(c)) return STK_EINVAL;
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, inner)) return STK_EINVAL;
-  const bool vec = (inner & 3) == 0 && stk_all_aligned16(F_hi, F_lo, y, n, r_out);
-  const unsigned row = (unsigned)(vec ? inner >> 2 : inner);
-  const int parts = stk_row_parts(B, inner);
-  const dim3 grid(parts, stk_row_rows(B, inner));                 // grid.x is the workspace's row length on either path
-  LossArgs a{F_hi, F_lo, y, n, sigma_hi, sigma_lo, coef, r_out, (double*)ws};
-  const int launched = stk_launch_vec(vec, ct_loss_kernel<4>, ct_loss_kernel<1>, grid, (hipStream_t)stream, row, B, a);
-  if (launched != STK_OK) return launched;
-  hipLaunchKernelGGL(ct_loss_finish_kernel, dim3(B < STK_MAX_GRID ? B : STK_MAX_GRID), dim3(256), 0, (hipStream_t)stream,
-                     (const double*)ws, coef, (double)c, loss_out, gfac_out, B, parts, (double)inner, reduce_mean);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  if (!stk_row_ws_ok(ws, ws_bytes, B, inner)) return STK_EINVAL;
+  return sq_loss_launch(stk_row_plan(B, inner, F_hi, F_lo, y, n, r_out), B, CtRes{{F_hi, F_lo, y, n}, sigma_hi, sigma_lo, coef},
+                        CtFinish{coef, loss_out, gfac_out, (double)c, (double)inner, reduce_mean}, r_out, ws, (hipStream_t)stream);
 }
 
 extern "C" int stk_ct_loss_grad_f32(const float* r, const float* gfac, const float* dloss, float* dF, int B, long inner,
                                     void* stream) {
   if (!r || !gfac || !dloss || !dF) return STK_EINVAL;
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  const bool vec = (inner & 3) == 0 && stk_all_aligned16(r, dF);
-  const unsigned row = (unsigned)(vec ? inner >> 2 : inner);
-  const dim3 grid(stk_row_parts(B, inner), stk_row_rows(B, inner));
-  GradArgs a{r, gfac, dloss, dF};
-  return stk_launch_vec(vec, ct_loss_grad_kernel<4>, ct_loss_grad_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return sq_loss_grad_launch(B, inner, CtGradFactor{gfac, dloss}, r, dF, (hipStream_t)stream);
 }
 
 extern "C" int stk_ct_step_f32(const float* x, const float* F, const float* z, float cs, float co, float lo, float hi, float c_z,
                                float c_in_next, float* x0_out, float* x_out, float* xin_out, long n, void* stream) {
   if (!x || !F || !(lo <= hi)) return STK_EINVAL;
   if (z ? (!x_out || !xin_out) : !x0_out) return STK_EINVAL;
-  const int rc = check_length(n);
+  const int rc = stk_length_check(n);
   if (rc != STK_OK) return rc;
   if (!z) x_out = xin_out = nullptr;                               // not touched: they neither count for the alignment
   const bool vec = (n & 3) == 0 && stk_all_aligned16(x, F, z, x0_out, x_out, xin_out);

@@ -9,13 +9,14 @@
 // seeing a pointer.  B inner < 2^31 and n < 2^31 (checked by the entries), so the index arithmetic is 32-bit.
 //
 // No fused multiply-add in this file (header, "Arithmetic"): the pragma below holds for every function that follows.
-// stream.h, included before it, holds loads, stores and host code only.
+// stream.h, included before it, holds loads, stores and host code only; sqloss.h (the loss, finish and gradient kernels shared
+// with consistency.hip, on the scaffold of rowsum.h) holds arithmetic and follows the pragma.
 #include "stream.h"
 #include "stk_edm.h"
 
 #pragma clang fp contract(off)
 
-#include "rowsum.h"
+#include "sqloss.h"
 
 namespace {
 
@@ -35,79 +36,41 @@ __global__ __launch_bounds__(256) void edm_coeffs_kernel(const float* sigma, dou
   coef[5 * (size_t)B + b] = (float)(log(S) / 4.);
 }
 
-struct LossArgs {
-  const float* F; const float* y; const float* n; const float* sigma; const float* coef;
-  float* r; double* ws;
+// r = c_skip (y + sigma n) + c_out F - y, every operation rounded to fp32 in that order.
+struct EdmRes {
+  static constexpr int N = 3;
+  const float* in[N];                                      // F, y, n
+  const float* sigma; const float* coef;
+  struct Row { float sg, csk, cou; };
+  __device__ Row row(int b, int B) const { return {sigma[b], coef[2 * (size_t)B + b], coef[3 * (size_t)B + b]}; }
+  __device__ static float r(const Row& c, const float* v) {
+    const float x = v[1] + c.sg * v[2];
+    const float D = c.csk * x + c.cou * v[0];
+    return D - v[1];
+  }
 };
 
-// row: items of V elements per sample.
-template <int V>
-__global__ __launch_bounds__(256) void edm_loss_kernel(unsigned row, int B, LossArgs a) {
-  __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const float sg = a.sigma[b], csk = a.coef[2 * (size_t)B + b], cou = a.coef[3 * (size_t)B + b];
-    const unsigned base = (unsigned)b * row;
-    double acc = 0.;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto Fv = Vec<V>::load(a.F, base + i);
-      const auto yv = Vec<V>::load(a.y, base + i);
-      const auto nv = Vec<V>::load(a.n, base + i);
-      Vec<V> o;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float x = yv.v[j] + sg * nv.v[j];
-        const float D = csk * x + cou * Fv.v[j];
-        const float r = D - yv.v[j];
-        const float q = r * r;
-        acc += (double)q;
-        o.v[j] = r;
-      }
-      if (a.r) o.store(a.r, base + i);
-    }
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) a.ws[(size_t)b * gridDim.x + blockIdx.x] = acc;
+// The row's sum times lambda, rounded once.
+struct EdmFinish {
+  const float* coef; float* loss;
+  double inner;
+  int reduce_mean;
+  __device__ void operator()(double acc, int b, int B) const {
+    const double v = (double)coef[4 * (size_t)B + b] * acc;
+    loss[b] = (float)(reduce_mean ? v / inner : v);
   }
-}
+};
 
-// One block per sample (striding): the row's partials in index order within the fixed tree, times lambda, rounded once.
-__global__ __launch_bounds__(256) void edm_loss_finish_kernel(const double* ws, const float* coef, float* loss, int B, int parts,
-                                                              double inner, int reduce_mean) {
-  __shared__ double red[4];
-  for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    double acc = 0.;
-    for (int j = threadIdx.x; j < parts; j += 256) acc += ws[(size_t)b * parts + j];
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) {
-      const double v = (double)coef[4 * (size_t)B + b] * acc;
-      loss[b] = (float)(reduce_mean ? v / inner : v);
-    }
-  }
-}
-
-struct GradArgs {
-  const float* r; const float* coef; const float* dloss;
-  float* dF;
+struct EdmGradFactor {
+  const float* coef; const float* dloss;
   float inner;
   int reduce_mean;
-};
-
-template <int V>
-__global__ __launch_bounds__(256) void edm_loss_grad_kernel(unsigned row, int B, GradArgs a) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    float k = ((2.f * a.coef[4 * (size_t)B + b]) * a.coef[3 * (size_t)B + b]) * a.dloss[b];
-    if (a.reduce_mean) k = k / a.inner;
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto rv = Vec<V>::load(a.r, base + i);
-      Vec<V> o;
-#pragma unroll
-      for (int j = 0; j < V; ++j) o.v[j] = k * rv.v[j];
-      o.store(a.dF, base + i);
-    }
+  __device__ float operator()(int b, int B) const {
+    float k = ((2.f * coef[4 * (size_t)B + b]) * coef[3 * (size_t)B + b]) * dloss[b];
+    if (reduce_mean) k = k / inner;
+    return k;
   }
-}
+};
 
 struct ChurnArgs {
   const float* x; const float* eps;
@@ -165,30 +128,10 @@ __global__ __launch_bounds__(256) void edm_step_kernel(unsigned total, StepArgs 
   }
 }
 
-// 0, or the code every per-sample entry returns for B rows of `len` floats.
-int check_sizes(int B, long len) {
-  if (B <= 0 || len <= 0) return STK_EINVAL;
-  if (len >= (1L << 31) || (long)B * len >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
-}
-
-// ... and every entry of the sampler for n elements.
-int check_length(long n) {
-  if (n <= 0) return STK_EINVAL;
-  if (n >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
-}
-
-bool ws_ok(const void* ws, long ws_bytes, int B, long inner) {
-  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)B * stk_row_parts(B, inner) * (long)sizeof(double);
-}
-
-bool positive_finite(float v) { return v > 0.f && v <= 3.402823466e38f; }      // false for NaN and +inf
-
 }  // namespace
 
 extern "C" int stk_edm_coeffs_f32(const float* sigma, float sigma_data, float* coef, int B, void* stream) {
-  if (!sigma || !coef || B <= 0 || !positive_finite(sigma_data)) return STK_EINVAL;
+  if (!sigma || !coef || B <= 0 || !stk_positive_finite(sigma_data)) return STK_EINVAL;
   hipLaunchKernelGGL(edm_coeffs_kernel, dim3(stk_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, sigma, (double)sigma_data,
                      coef, B);
   STK_CHECK_LAUNCH();
@@ -196,47 +139,34 @@ extern "C" int stk_edm_coeffs_f32(const float* sigma, float sigma_data, float* c
 }
 
 extern "C" long stk_edm_ws_bytes(int B, long inner) {
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  return (long)B * stk_row_parts(B, inner) * (long)sizeof(double);
+  return stk_row_ws_bytes(B, inner);
 }
 
 extern "C" int stk_edm_loss_f32(const float* F, const float* y, const float* n, const float* sigma, const float* coef, void* ws,
                                 long ws_bytes, float* r_out, float* loss_out, int B, long inner, int reduce_mean, void* stream) {
   if (!F || !y || !n || !sigma || !coef || !ws || !loss_out) return STK_EINVAL;
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, inner)) return STK_EINVAL;
-  const bool vec = (inner & 3) == 0 && stk_all_aligned16(F, y, n, r_out);
-  const unsigned row = (unsigned)(vec ? inner >> 2 : inner);
-  const int parts = stk_row_parts(B, inner);
-  const dim3 grid(parts, stk_row_rows(B, inner));                 // grid.x is the workspace's row length on either path
-  LossArgs a{F, y, n, sigma, coef, r_out, (double*)ws};
-  const int launched = stk_launch_vec(vec, edm_loss_kernel<4>, edm_loss_kernel<1>, grid, (hipStream_t)stream, row, B, a);
-  if (launched != STK_OK) return launched;
-  hipLaunchKernelGGL(edm_loss_finish_kernel, dim3(B < STK_MAX_GRID ? B : STK_MAX_GRID), dim3(256), 0, (hipStream_t)stream,
-                     (const double*)ws, coef, loss_out, B, parts, (double)inner, reduce_mean);
-  STK_CHECK_LAUNCH();
-  return STK_OK;
+  if (!stk_row_ws_ok(ws, ws_bytes, B, inner)) return STK_EINVAL;
+  return sq_loss_launch(stk_row_plan(B, inner, F, y, n, r_out), B, EdmRes{{F, y, n}, sigma, coef},
+                        EdmFinish{coef, loss_out, (double)inner, reduce_mean}, r_out, ws, (hipStream_t)stream);
 }
 
 extern "C" int stk_edm_loss_grad_f32(const float* r, const float* coef, const float* dloss, float* dF, int B, long inner,
                                      int reduce_mean, void* stream) {
   if (!r || !coef || !dloss || !dF) return STK_EINVAL;
-  const int rc = check_sizes(B, inner);
+  const int rc = stk_row_check(B, inner);
   if (rc != STK_OK) return rc;
-  const bool vec = (inner & 3) == 0 && stk_all_aligned16(r, dF);
-  const unsigned row = (unsigned)(vec ? inner >> 2 : inner);
-  const dim3 grid(stk_row_parts(B, inner), stk_row_rows(B, inner));
-  GradArgs a{r, coef, dloss, dF, (float)inner, reduce_mean};
-  return stk_launch_vec(vec, edm_loss_grad_kernel<4>, edm_loss_grad_kernel<1>, grid, (hipStream_t)stream, row, B, a);
+  return sq_loss_grad_launch(B, inner, EdmGradFactor{coef, dloss, (float)inner, reduce_mean}, r, dF, (hipStream_t)stream);
 }
 
 extern "C" int stk_edm_churn_f32(const float* x, const float* eps, float c_eps, float c_in_hat, float* x_hat_out, float* xin_out,
                                  long n, void* stream) {
   if (!x || !xin_out || !(c_eps >= 0.f)) return STK_EINVAL;
   if (eps ? !x_hat_out : c_eps != 0.f) return STK_EINVAL;
-  const int rc = check_length(n);
+  const int rc = stk_length_check(n);
   if (rc != STK_OK) return rc;
   const bool vec = (n & 3) == 0 && stk_all_aligned16(x, eps, x_hat_out, xin_out);
   const unsigned total = (unsigned)(vec ? n >> 2 : n);
@@ -246,8 +176,8 @@ extern "C" int stk_edm_churn_f32(const float* x, const float* eps, float c_eps, 
 
 extern "C" int stk_edm_step_f32(const float* xb, const float* xe, const float* F, const float* d_prev, float cs, float co, float t,
                                 float h, float c_next, float* x_out, float* d_out, float* xin_out, long n, void* stream) {
-  if (!xb || !xe || !F || !x_out || !positive_finite(t)) return STK_EINVAL;
-  const int rc = check_length(n);
+  if (!xb || !xe || !F || !x_out || !stk_positive_finite(t)) return STK_EINVAL;
+  const int rc = stk_length_check(n);
   if (rc != STK_OK) return rc;
   const bool vec = (n & 3) == 0 && stk_all_aligned16(xb, xe, F, d_prev, x_out, d_out, xin_out);
   const unsigned total = (unsigned)(vec ? n >> 2 : n);

@@ -105,15 +105,13 @@ __global__ __launch_bounds__(256) void select_pass_kernel(unsigned row, int B, c
   __shared__ unsigned hist[BINS1];
   __shared__ unsigned sh[6];
   constexpr unsigned NB = LEVEL == 1 ? BINS1 : (LEVEL == 2 ? BINS2 : BINS3);
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     unsigned prefix = 0, r = rank, bin;
     if (LEVEL >= 2) { find_bin<BINS1>(hist1_of(ws, B, b), r, sh, bin, r); prefix = bin; }
     if (LEVEL == 3) { find_bin<BINS2>(hist2_of(ws, B, b), r, sh, bin, r); prefix = (prefix << 10) | bin; }
     zero_hist(hist, NB);
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto vv = Vec<V>::load(v, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto vv = Vec<V>::load(v, i);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const unsigned k = key_of(vv.v[j]);
@@ -121,9 +119,9 @@ __global__ __launch_bounds__(256) void select_pass_kernel(unsigned row, int B, c
         if (LEVEL == 2) { if ((k >> 20) == prefix) atomicAdd(&hist[(k >> 10) & 1023u], 1u); }
         if (LEVEL == 3) { if ((k >> 10) == prefix) atomicAdd(&hist[k & 1023u], 1u); }
       }
-    }
+    });
     flush_hist(hist, NB, LEVEL == 1 ? hist1_of(ws, B, b) : (LEVEL == 2 ? hist2_of(ws, B, b) : hist3_of(ws, B, b)));
-  }
+  });
 }
 
 // One block per row (striding): the three scans, and q; then the row's planes two and three are zeroed for the next
@@ -148,13 +146,11 @@ template <int V>
 __global__ __launch_bounds__(256) void predict_kernel(unsigned row, int B, const float* x, const float* score, float cx, float cs,
                                                       float* d_raw, unsigned* ws) {
   __shared__ unsigned hist[BINS1];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     zero_hist(hist, BINS1);
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto xv = Vec<V>::load(x, base + i);
-      const auto sv = Vec<V>::load(score, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto xv = Vec<V>::load(x, i);
+      const auto sv = Vec<V>::load(score, i);
       Vec<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
@@ -163,10 +159,10 @@ __global__ __launch_bounds__(256) void predict_kernel(unsigned row, int B, const
         o.v[j] = px + ps;
         atomicAdd(&hist[key_of(o.v[j]) >> 20], 1u);
       }
-      o.store(d_raw, base + i);
-    }
+      o.store(d_raw, i);
+    });
     flush_hist(hist, BINS1, hist1_of(ws, B, b));
-  }
+  });
 }
 
 struct UpdateArgs {
@@ -180,17 +176,15 @@ __device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { r
 
 template <int V>
 __global__ __launch_bounds__(256) void threshold_update_kernel(unsigned row, int B, UpdateArgs p) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+  row_samples(B, [&](int b) {
     const float qb = p.q[b];
     const float s = qb != qb ? qb : (qb > p.floor ? qb : p.floor);
     const float ms = -s;
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto rv = Vec<V>::load(p.d_raw, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto rv = Vec<V>::load(p.d_raw, i);
       Vec<V> xv, pv, xo, dv;
-      if (p.x) xv = Vec<V>::load(p.x, base + i);
-      if (p.d_prev) pv = Vec<V>::load(p.d_prev, base + i);
+      if (p.x) xv = Vec<V>::load(p.x, i);
+      if (p.d_prev) pv = Vec<V>::load(p.d_prev, i);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const float d = clamp_keep_nan(rv.v[j], ms, s) / s;
@@ -207,10 +201,10 @@ __global__ __launch_bounds__(256) void threshold_update_kernel(unsigned row, int
           xo.v[j] = ax + bd;
         }
       }
-      if (p.x) xo.store(p.x_out, base + i);
-      if (p.d_out) dv.store(p.d_out, base + i);
-    }
-  }
+      if (p.x) xo.store(p.x_out, i);
+      if (p.d_out) dv.store(p.d_out, i);
+    });
+  });
 }
 
 // Pass 1 of the rescale: g, and the row's partial sums [B, parts, SUMS].
@@ -218,13 +212,11 @@ template <int V>
 __global__ __launch_bounds__(256) void rescale_combine_kernel(unsigned row, int B, const float* cond, const float* uncond, float w,
                                                               float* out, double* ws) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const unsigned base = (unsigned)b * row;
+  row_samples(B, [&](int b) {
     double acc[SUMS] = {0., 0., 0., 0.};                               // sum c, sum c c, sum g, sum g g
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto cv = Vec<V>::load(cond, base + i);
-      const auto uv = Vec<V>::load(uncond, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto cv = Vec<V>::load(cond, i);
+      const auto uv = Vec<V>::load(uncond, i);
       Vec<V> ov;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
@@ -236,33 +228,19 @@ __global__ __launch_bounds__(256) void rescale_combine_kernel(unsigned row, int 
         acc[0] += c64; acc[1] += cc; acc[2] += g64; acc[3] += gg;
         ov.v[j] = g;
       }
-      ov.store(out, base + i);
-    }
-#pragma unroll
-    for (int k = 0; k < SUMS; ++k) acc[k] = block_sum_f64(acc[k], red);
-    if (threadIdx.x == 0) {
-      double* slot = ws + ((size_t)b * gridDim.x + blockIdx.x) * SUMS;
-#pragma unroll
-      for (int k = 0; k < SUMS; ++k) slot[k] = acc[k];
-    }
-  }
+      ov.store(out, i);
+    });
+    row_store_partials(acc, red, ws, b);
+  });
 }
 
 // Pass 2: every block of a row sums the row's partials itself, in the same order, and scales its stretch of g in place.
 template <int V>
 __global__ __launch_bounds__(256) void rescale_scale_kernel(unsigned row, int B, double n, float phi, float* out, const double* ws) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  const int parts = gridDim.x;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    double s[SUMS] = {0., 0., 0., 0.};
-    for (int j = threadIdx.x; j < parts; j += 256) {
-      const double* slot = ws + ((size_t)b * parts + j) * SUMS;
-#pragma unroll
-      for (int k = 0; k < SUMS; ++k) s[k] += slot[k];
-    }
-#pragma unroll
-    for (int k = 0; k < SUMS; ++k) s[k] = block_sum_f64(s[k], red);
+  row_samples(B, [&](int b) {
+    double s[SUMS];
+    row_sum_partials(ws, b, gridDim.x, red, s);
     const double mc = s[0] / n, mg = s[2] / n;
     double vc = s[1] / n - mc * mc, vg = s[3] / n - mg * mg;
     vc = vc < 0. ? 0. : vc;
@@ -274,41 +252,30 @@ __global__ __launch_bounds__(256) void rescale_scale_kernel(unsigned row, int B,
       const double scaled = (double)phi * ratio;
       f = (float)(scaled + (1. - (double)phi));
     }
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      auto gv = Vec<V>::load(out, base + i);
+    row_items(row, b, [&](unsigned i) {
+      auto gv = Vec<V>::load(out, i);
 #pragma unroll
       for (int j = 0; j < V; ++j) gv.v[j] = f * gv.v[j];
-      gv.store(out, base + i);
-    }
-  }
-}
-
-// 0, or the code every entry returns for B rows of n floats.
-int check_sizes(int B, long n) {
-  if (B <= 0 || n <= 0) return STK_EINVAL;
-  if (n >= (1L << 31) || (long)B * n >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
+      gv.store(out, i);
+    });
+  });
 }
 
 long select_bytes(int B) { return (long)B * ROW_WORDS * (long)sizeof(unsigned); }
-long rescale_bytes(int B, long n) { return (long)B * stk_row_parts(B, n) * SUMS * (long)sizeof(double); }
 
 long ws_bytes_of(int B, long n) {
-  const long a = select_bytes(B), b = rescale_bytes(B, n);
+  const long a = select_bytes(B), b = stk_row_ws_bytes(B, n, SUMS);
   return a > b ? a : b;
 }
 
-bool ws_ok(const void* ws, long ws_bytes, int B, long n) {
+bool guided_ws_ok(const void* ws, long ws_bytes, int B, long n) {
   return ws && stk_aligned16(ws) && ws_bytes >= ws_bytes_of(B, n);
 }
-
-dim3 row_grid(int B, long n) { return dim3(stk_row_parts(B, n), stk_row_rows(B, n)); }
 
 }  // namespace
 
 extern "C" long stk_guided_ws_bytes(int B, long n) {
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
   return ws_bytes_of(B, n);
 }
@@ -316,22 +283,21 @@ extern "C" long stk_guided_ws_bytes(int B, long n) {
 extern "C" int stk_abs_select_f32(const float* v, int B, long n, long rank, float* q, void* ws, long ws_bytes,
                                   int first_level_done, void* stream) {
   if (!v || !q || !ws) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  if (rank < 0 || rank >= n || (first_level_done != 0 && first_level_done != 1) || !ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
+  if (rank < 0 || rank >= n || (first_level_done != 0 && first_level_done != 1) || !guided_ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
   const hipStream_t st = (hipStream_t)stream;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(v);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n), r = (unsigned)rank;
-  const dim3 grid = row_grid(B, n);
+  const StkRowPlan p = stk_row_plan(B, n, v);
+  const unsigned r = (unsigned)rank;
   unsigned* w = (unsigned*)ws;
   if (!first_level_done) {
     if (hipMemsetAsync(ws, 0, (size_t)select_bytes(B), st) != hipSuccess) return STK_ELAUNCH;
-    const int rc1 = stk_launch_vec(vec, select_pass_kernel<4, 1>, select_pass_kernel<1, 1>, grid, st, row, B, v, r, w);
+    const int rc1 = stk_launch_vec(p.vec, select_pass_kernel<4, 1>, select_pass_kernel<1, 1>, p.grid, st, p.row, B, v, r, w);
     if (rc1 != STK_OK) return rc1;
   }
-  const int rc2 = stk_launch_vec(vec, select_pass_kernel<4, 2>, select_pass_kernel<1, 2>, grid, st, row, B, v, r, w);
+  const int rc2 = stk_launch_vec(p.vec, select_pass_kernel<4, 2>, select_pass_kernel<1, 2>, p.grid, st, p.row, B, v, r, w);
   if (rc2 != STK_OK) return rc2;
-  const int rc3 = stk_launch_vec(vec, select_pass_kernel<4, 3>, select_pass_kernel<1, 3>, grid, st, row, B, v, r, w);
+  const int rc3 = stk_launch_vec(p.vec, select_pass_kernel<4, 3>, select_pass_kernel<1, 3>, p.grid, st, p.row, B, v, r, w);
   if (rc3 != STK_OK) return rc3;
   hipLaunchKernelGGL(select_finish_kernel, dim3(B < STK_MAX_GRID ? B : STK_MAX_GRID), dim3(256), 0, st, B, r, w, q);
   STK_CHECK_LAUNCH();
@@ -341,43 +307,37 @@ extern "C" int stk_abs_select_f32(const float* v, int B, long n, long rank, floa
 extern "C" int stk_dpm_predict_f32(const float* x, const float* score, float cx, float cs, float* d_raw, int B, long n, void* ws,
                                    long ws_bytes, void* stream) {
   if (!x || !score || !d_raw || !ws) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
+  if (!guided_ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
   const hipStream_t st = (hipStream_t)stream;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, d_raw);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
+  const StkRowPlan p = stk_row_plan(B, n, x, score, d_raw);
   if (hipMemsetAsync(ws, 0, (size_t)select_bytes(B), st) != hipSuccess) return STK_ELAUNCH;
-  return stk_launch_vec(vec, predict_kernel<4>, predict_kernel<1>, row_grid(B, n), st, row, B, x, score, cx, cs, d_raw,
-                        (unsigned*)ws);
+  return stk_launch_vec(p.vec, predict_kernel<4>, predict_kernel<1>, p.grid, st, p.row, B, x, score, cx, cs, d_raw, (unsigned*)ws);
 }
 
 extern "C" int stk_dpm_threshold_update_f32(const float* x, const float* d_raw, const float* d_prev, const float* q, float floor,
                                             float g, float A, float Bc, float* x_out, float* d_out, int B, long n, void* stream) {
   if (!d_raw || !q || (x == nullptr) != (x_out == nullptr) || (!x && !d_out)) return STK_EINVAL;
   if ((g != 0.f && !d_prev) || !(floor > 0.f && floor <= 3.402823466e38f)) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, d_raw, d_prev, x_out, d_out);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
+  const StkRowPlan pl = stk_row_plan(B, n, x, d_raw, d_prev, x_out, d_out);
   UpdateArgs p{x, d_raw, d_prev, q, x_out, d_out, floor, g, A, Bc};
-  return stk_launch_vec(vec, threshold_update_kernel<4>, threshold_update_kernel<1>, row_grid(B, n), (hipStream_t)stream, row, B,
-                        p);
+  return stk_launch_vec(pl.vec, threshold_update_kernel<4>, threshold_update_kernel<1>, pl.grid, (hipStream_t)stream, pl.row, B, p);
 }
 
 extern "C" int stk_cfg_rescale_f32(const float* cond, const float* uncond, float w, float phi, float* out, int B, long n, void* ws,
                                    long ws_bytes, void* stream) {
   if (!cond || !uncond || !out || !ws || !(w - w == 0.f) || !(phi >= 0.f && phi <= 1.f)) return STK_EINVAL;
-  const int rc = check_sizes(B, n);
+  const int rc = stk_row_check(B, n);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
+  if (!guided_ws_ok(ws, ws_bytes, B, n)) return STK_EINVAL;
   const hipStream_t st = (hipStream_t)stream;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(cond, uncond, out);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid = row_grid(B, n);
-  const int rc1 = stk_launch_vec(vec, rescale_combine_kernel<4>, rescale_combine_kernel<1>, grid, st, row, B, cond, uncond, w, out,
-                                 (double*)ws);
+  const StkRowPlan p = stk_row_plan(B, n, cond, uncond, out);
+  const int rc1 = stk_launch_vec(p.vec, rescale_combine_kernel<4>, rescale_combine_kernel<1>, p.grid, st, p.row, B, cond, uncond, w,
+                                 out, (double*)ws);
   if (rc1 != STK_OK) return rc1;
-  return stk_launch_vec(vec, rescale_scale_kernel<4>, rescale_scale_kernel<1>, grid, st, row, B, (double)n, phi, out,
+  return stk_launch_vec(p.vec, rescale_scale_kernel<4>, rescale_scale_kernel<1>, p.grid, st, p.row, B, (double)n, phi, out,
                         (const double*)ws);
 }

@@ -31,20 +31,18 @@ struct TweedieArgs {
 // row: items of V elements per sample.
 template <int V>
 __global__ __launch_bounds__(256) void tweedie_kernel(unsigned row, int N, TweedieArgs p) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < N; b += gridDim.y) {
+  row_samples(N, [&](int b) {
     const float a = p.a[b], s = p.s[b];
     const float s2 = s * s;
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto xv = Vec<V>::load(p.x, base + i);
-      const auto sv = Vec<V>::load(p.score, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto xv = Vec<V>::load(p.x, i);
+      const auto sv = Vec<V>::load(p.score, i);
       Vec<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) o.v[j] = clamp_keep_nan((xv.v[j] + s2 * sv.v[j]) / a, p.lo, p.hi);
-      o.store(p.x0, base + i);
-    }
-  }
+      o.store(p.x0, i);
+    });
+  });
 }
 
 struct ResidualArgs {
@@ -55,13 +53,11 @@ struct ResidualArgs {
 template <int V>
 __global__ __launch_bounds__(256) void residual_kernel(unsigned row, int N, ResidualArgs p) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < N; b += gridDim.y) {
-    const unsigned base = (unsigned)b * row;
+  row_samples(N, [&](int b) {
     double acc = 0.;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto yv = Vec<V>::load(p.y, base + i);
-      const auto mv = Vec<V>::load(p.m, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto yv = Vec<V>::load(p.y, i);
+      const auto mv = Vec<V>::load(p.m, i);
       Vec<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) {
@@ -70,11 +66,10 @@ __global__ __launch_bounds__(256) void residual_kernel(unsigned row, int N, Resi
         acc += (double)rr;
         o.v[j] = r;
       }
-      o.store(p.r, base + i);
-    }
-    acc = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) p.ws[(size_t)b * gridDim.x + blockIdx.x] = acc;
-  }
+      o.store(p.r, i);
+    });
+    row_store_partial(acc, red, p.ws, b);
+  });
 }
 
 struct SeedArgs {
@@ -89,26 +84,22 @@ struct SeedArgs {
 template <int V>
 __global__ __launch_bounds__(256) void guide_seed_kernel(unsigned row, int N, SeedArgs p) {
   __shared__ double red[4];
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < N; b += gridDim.y) {
+  row_samples(N, [&](int b) {
     if (blockIdx.x == 0) {                                 // uniform over the block
-      double acc = 0.;
-      for (int j = threadIdx.x; j < p.parts; j += 256) acc += p.ws[(size_t)b * p.parts + j];
-      acc = block_sum_f64(acc, red);
+      const double acc = row_sum_partial(p.ws, b, p.parts, red);
       if (threadIdx.x == 0) p.rnorm[b] = (float)sqrt(acc);
     }
     const float a = p.a[b], s = p.s[b];
     const float c = (s * s) / a;
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto vv = Vec<V>::load(p.v, base + i);
-      const auto x0 = Vec<V>::load(p.x0, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto vv = Vec<V>::load(p.v, i);
+      const auto x0 = Vec<V>::load(p.x0, i);
       Vec<V> o;
 #pragma unroll
       for (int j = 0; j < V; ++j) o.v[j] = inside(x0.v[j], p.lo, p.hi) ? c * vv.v[j] : 0.f;
-      o.store(p.seed, base + i);
-    }
-  }
+      o.store(p.seed, i);
+    });
+  });
 }
 
 struct UpdateArgs {
@@ -119,18 +110,16 @@ struct UpdateArgs {
 
 template <int V>
 __global__ __launch_bounds__(256) void guide_update_kernel(unsigned row, int N, UpdateArgs p) {
-  const unsigned stride = gridDim.x * 256;
-  for (int b = blockIdx.y; b < N; b += gridDim.y) {
+  row_samples(N, [&](int b) {
     const float a = p.a[b], rn = p.rnorm[b];
     const float c = (rn > 0.f && rn <= 3.402823466e38f) ? p.zeta / rn : 0.f;      // false for NaN and +inf
-    const unsigned base = (unsigned)b * row;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < row; i += stride) {
-      const auto xp = Vec<V>::load(p.xp, base + i);
-      const auto vv = Vec<V>::load(p.v, base + i);
-      const auto gn = Vec<V>::load(p.gnet, base + i);
-      const auto x0 = Vec<V>::load(p.x0, base + i);
+    row_items(row, b, [&](unsigned i) {
+      const auto xp = Vec<V>::load(p.xp, i);
+      const auto vv = Vec<V>::load(p.v, i);
+      const auto gn = Vec<V>::load(p.gnet, i);
+      const auto x0 = Vec<V>::load(p.x0, i);
       Vec<V> xm, o, om;
-      if (p.xpm) xm = Vec<V>::load(p.xpm, base + i);
+      if (p.xpm) xm = Vec<V>::load(p.xpm, i);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const float g = inside(x0.v[j], p.lo, p.hi) ? vv.v[j] / a + gn.v[j] : gn.v[j];
@@ -138,57 +127,42 @@ __global__ __launch_bounds__(256) void guide_update_kernel(unsigned row, int N, 
         o.v[j] = xp.v[j] + step;
         if (p.xpm) om.v[j] = xm.v[j] + step;
       }
-      o.store(p.x_out, base + i);
-      if (p.xpm) om.store(p.xmean_out, base + i);
-    }
-  }
-}
-
-// 0, or the code every entry returns for N rows of `len` floats.
-int check_sizes(int N, long len) {
-  if (N <= 0 || len <= 0) return STK_EINVAL;
-  if (len >= (1L << 31) || (long)N * len >= (1L << 31)) return STK_EUNSUPPORTED;
-  return STK_OK;
+      o.store(p.x_out, i);
+      if (p.xpm) om.store(p.xmean_out, i);
+    });
+  });
 }
 
 bool bounds_ok(float lo, float hi) { return lo <= hi; }      // false when either is NaN
 
-bool ws_ok(const void* ws, long ws_bytes, int N, long k) {
-  return ws && (((uintptr_t)ws) & 7) == 0 && ws_bytes >= (long)N * stk_row_parts(N, k) * (long)sizeof(double);
-}
-
 }  // namespace
 
 extern "C" long stk_posterior_ws_bytes(int N, long k) {
-  const int rc = check_sizes(N, k);
+  const int rc = stk_row_check(N, k);
   if (rc != STK_OK) return rc;
-  return (long)N * stk_row_parts(N, k) * (long)sizeof(double);
+  return stk_row_ws_bytes(N, k);
 }
 
 extern "C" int stk_tweedie_f32(const float* x, const float* score, const float* a, const float* s, float lo, float hi,
                                float* x0_out, int N, long n, void* stream) {
   if (!x || !score || !a || !s || !x0_out) return STK_EINVAL;
   if (!bounds_ok(lo, hi)) return STK_EINVAL;
-  const int rc = check_sizes(N, n);
+  const int rc = stk_row_check(N, n);
   if (rc != STK_OK) return rc;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(x, score, x0_out);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(N, n), stk_row_rows(N, n));
+  const StkRowPlan pl = stk_row_plan(N, n, x, score, x0_out);
   TweedieArgs p{x, score, a, s, x0_out, lo, hi};
-  return stk_launch_vec(vec, tweedie_kernel<4>, tweedie_kernel<1>, grid, (hipStream_t)stream, row, N, p);
+  return stk_launch_vec(pl.vec, tweedie_kernel<4>, tweedie_kernel<1>, pl.grid, (hipStream_t)stream, pl.row, N, p);
 }
 
 extern "C" int stk_residual_f32(const float* y, const float* m, float* r_out, void* ws, long ws_bytes, int N, long k,
                                 void* stream) {
   if (!y || !m || !r_out || !ws) return STK_EINVAL;
-  const int rc = check_sizes(N, k);
+  const int rc = stk_row_check(N, k);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, N, k)) return STK_EINVAL;
-  const bool vec = (k & 3) == 0 && stk_all_aligned16(y, m, r_out);
-  const unsigned row = (unsigned)(vec ? k >> 2 : k);
-  const dim3 grid(stk_row_parts(N, k), stk_row_rows(N, k));       // grid.x is the workspace's row length on either path
+  if (!stk_row_ws_ok(ws, ws_bytes, N, k)) return STK_EINVAL;
+  const StkRowPlan pl = stk_row_plan(N, k, y, m, r_out);
   ResidualArgs p{y, m, r_out, (double*)ws};
-  return stk_launch_vec(vec, residual_kernel<4>, residual_kernel<1>, grid, (hipStream_t)stream, row, N, p);
+  return stk_launch_vec(pl.vec, residual_kernel<4>, residual_kernel<1>, pl.grid, (hipStream_t)stream, pl.row, N, p);
 }
 
 extern "C" int stk_guide_seed_f32(const float* v, const float* x0, const float* a, const float* s, float lo, float hi,
@@ -196,16 +170,14 @@ extern "C" int stk_guide_seed_f32(const float* v, const float* x0, const float* 
                                   void* stream) {
   if (!v || !x0 || !a || !s || !ws || !seed_out || !rnorm_out) return STK_EINVAL;
   if (!bounds_ok(lo, hi)) return STK_EINVAL;
-  int rc = check_sizes(N, n);
+  int rc = stk_row_check(N, n);
   if (rc != STK_OK) return rc;
-  rc = check_sizes(N, k);
+  rc = stk_row_check(N, k);
   if (rc != STK_OK) return rc;
-  if (!ws_ok(ws, ws_bytes, N, k)) return STK_EINVAL;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(v, x0, seed_out);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(N, n), stk_row_rows(N, n));
+  if (!stk_row_ws_ok(ws, ws_bytes, N, k)) return STK_EINVAL;
+  const StkRowPlan pl = stk_row_plan(N, n, v, x0, seed_out);
   SeedArgs p{v, x0, a, s, (const double*)ws, seed_out, rnorm_out, lo, hi, stk_row_parts(N, k)};
-  return stk_launch_vec(vec, guide_seed_kernel<4>, guide_seed_kernel<1>, grid, (hipStream_t)stream, row, N, p);
+  return stk_launch_vec(pl.vec, guide_seed_kernel<4>, guide_seed_kernel<1>, pl.grid, (hipStream_t)stream, pl.row, N, p);
 }
 
 extern "C" int stk_guide_update_f32(const float* xp, const float* xpm, const float* v, const float* gnet, const float* x0,
@@ -214,11 +186,9 @@ extern "C" int stk_guide_update_f32(const float* xp, const float* xpm, const flo
   if (!xp || !v || !gnet || !x0 || !a || !rnorm || !x_out) return STK_EINVAL;
   if ((xpm == nullptr) != (xmean_out == nullptr)) return STK_EINVAL;
   if (!(zeta >= 0.f) || !bounds_ok(lo, hi)) return STK_EINVAL;
-  const int rc = check_sizes(N, n);
+  const int rc = stk_row_check(N, n);
   if (rc != STK_OK) return rc;
-  const bool vec = (n & 3) == 0 && stk_all_aligned16(xp, xpm, v, gnet, x0, x_out, xmean_out);
-  const unsigned row = (unsigned)(vec ? n >> 2 : n);
-  const dim3 grid(stk_row_parts(N, n), stk_row_rows(N, n));
+  const StkRowPlan pl = stk_row_plan(N, n, xp, xpm, v, gnet, x0, x_out, xmean_out);
   UpdateArgs p{xp, xpm, v, gnet, x0, a, rnorm, x_out, xmean_out, zeta, lo, hi};
-  return stk_launch_vec(vec, guide_update_kernel<4>, guide_update_kernel<1>, grid, (hipStream_t)stream, row, N, p);
+  return stk_launch_vec(pl.vec, guide_update_kernel<4>, guide_update_kernel<1>, pl.grid, (hipStream_t)stream, pl.row, N, p);
 }

@@ -1,4 +1,5 @@
-// stream.h -- what the HBM-bound streaming kernels share (elementwise.hip, impute.hip, solver.hip, adaptive.hip).
+// stream.h -- what the HBM-bound streaming kernels share (elementwise.hip, impute.hip, solver.hip, superres.hip, cond.hip and,
+// through rowsum.h, the per-sample files adaptive.hip, posterior.hip, guided.hip, edm.hip, consistency.hip).
 //
 // The layout they all follow: lanes walk consecutive addresses, 16 B per lane (one float4) whenever the length -- or the
 // plane or row a thread stays inside -- is a multiple of 4 and every pointer given is 16-byte aligned, a scalar path
@@ -6,9 +7,10 @@
 // template over V = 4 or 1 elements per item and moves its data through Vec<V>; its entry decides `vec` from its own length
 // condition and stk_all_aligned16 of its pointers, and launches the pair through stk_launch_vec.
 //
-// Loads, stores and host code only: NO floating-point arithmetic belongs in this file.  adaptive.hip switches contraction
-// off with a pragma that holds "for every function that follows" it, so arithmetic written here, before that pragma,
-// would be compiled under another rule than the file that includes it states.
+// Loads, stores and host code only: NO floating-point arithmetic belongs in this file.  The files that include it switch
+// contraction off with a pragma that holds "for every function that follows" it, so arithmetic written here, before that
+// pragma, would be compiled under another rule than the file that includes it states.  Headers that hold arithmetic
+// (rowsum.h, sqloss.h) are included after the pragma.
 #pragma once
 #include "common.h"
 

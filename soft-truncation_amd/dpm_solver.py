@@ -75,8 +75,7 @@ def _lam(sde, t):
     return np.log(alpha) - np.log(sigma)
 
 
-def _fp32(v):
-  return np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+_fp32 = mutils.fp32_levels
 
 
 def _invert_lambda(sde, targets, lo, hi):

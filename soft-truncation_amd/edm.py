@@ -42,8 +42,7 @@ def _library():
   return mutils.require('has_edm', 'stk_edm.h', 'stk_edm_churn_f32 and stk_edm_step_f32', 'the EDM sampler needs')
 
 
-def _fp32(v):
-  return np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+_fp32, _ptr = mutils.fp32_levels, mutils.optional_ptr
 
 
 def denoiser_coefficients(sigma, sigma_data):
@@ -120,28 +119,17 @@ def edm_schedule(sde, steps, rho=7, s_churn=0, s_tmin=0, s_tmax=_INF, s_noise=1)
 
 def _churn(lib, x, eps, c_eps, c_in_hat, x_hat_out, xin_out):
   """One launch of stk_edm_churn_f32 on contiguous fp32 device tensors; eps None: no noise."""
-  ptr = lambda t: None if t is None else t.data_ptr()
   with stk_lib.device_guard(x.device):
-    lib.edm_churn_f32(x.data_ptr(), ptr(eps), float(c_eps), float(c_in_hat), ptr(x_hat_out), xin_out.data_ptr(), x.numel(),
+    lib.edm_churn_f32(x.data_ptr(), _ptr(eps), float(c_eps), float(c_in_hat), _ptr(x_hat_out), xin_out.data_ptr(), x.numel(),
                       stk_lib.stream_ptr(x.device))
 
 
 def _step(lib, xb, xe, F, d_prev, row, x_out, d_out, xin_out):
   """One launch of stk_edm_step_f32 on contiguous fp32 device tensors.  row: (cs, co, t, h, c_next, ...)."""
   cs, co, t, h, c_next = (float(v) for v in row[:5])
-  ptr = lambda t_: None if t_ is None else t_.data_ptr()
   with stk_lib.device_guard(xb.device):
-    lib.edm_step_f32(xb.data_ptr(), xe.data_ptr(), F.data_ptr(), ptr(d_prev), cs, co, t, h, c_next, x_out.data_ptr(), ptr(d_out),
-                     ptr(xin_out), xb.numel(), stk_lib.stream_ptr(xb.device))
-
-
-def _evaluate(model_fn, xin, c_noise, lib):
-  """``model_fn(xin, c_noise)``, which must be a float32 tensor of xin's shape on the library's device, made contiguous."""
-  F = model_fn(xin, c_noise)
-  _backend.check(F, lib)
-  if F.shape != xin.shape or F.dtype != torch.float32:
-    raise ValueError(f'the network returned {F.dtype} {tuple(F.shape)} for a float32 input {tuple(xin.shape)}')
-  return F.contiguous()
+    lib.edm_step_f32(xb.data_ptr(), xe.data_ptr(), F.data_ptr(), _ptr(d_prev), cs, co, t, h, c_next, x_out.data_ptr(), _ptr(d_out),
+                     _ptr(xin_out), xb.numel(), stk_lib.stream_ptr(xb.device))
 
 
 def edm_sample(model_fn, schedule, x, noise_fn=None):
@@ -154,9 +142,9 @@ def edm_sample(model_fn, schedule, x, noise_fn=None):
   draw = torch.randn_like if noise_fn is None else noise_fn
   steps, B = schedule.steps, x.shape[0]
   x1, d, xin = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-  # the conditioning vectors of all evaluations, one host-to-device copy per run: row 2 i for t^_i, row 2 i + 1 for t_{i+1}
+  # the conditioning vectors of all evaluations: row 2 i for t^_i, row 2 i + 1 for t_{i+1}
   levels = np.stack([schedule.euler[:, 5], np.concatenate([schedule.correct[:, 5], [0.]])], axis=1).reshape(-1)[:schedule.nfe]
-  cond = torch.tensor(levels, dtype=torch.float32).to(x.device)[:, None].expand(-1, B).contiguous()
+  cond = mutils.level_conditioning(levels, B, x.device)
   for i in range(steps):
     if schedule.gamma[i] > 0.:
       eps = draw(x)
@@ -164,12 +152,12 @@ def edm_sample(model_fn, schedule, x, noise_fn=None):
       _churn(lib, x, eps, schedule.c_eps[i], schedule.c_in_hat[i], x, xin)
     elif i == 0:
       _churn(lib, x, None, 0., schedule.c_in_hat[0], None, xin)
-    F = _evaluate(model_fn, xin, cond[2 * i], lib)
+    F = mutils.checked_score(model_fn, xin, cond[2 * i], lib)
     if i == steps - 1:                                    # t_{i+1} = 0: the Euler point is the result
       _step(lib, x, x, F, None, schedule.euler[i], x, None, None)
       break
     _step(lib, x, x, F, None, schedule.euler[i], x1, d, xin)
-    F = _evaluate(model_fn, xin, cond[2 * i + 1], lib)
+    F = mutils.checked_score(model_fn, xin, cond[2 * i + 1], lib)
     feeds_next = not schedule.gamma[i + 1] > 0.           # a churned step writes its own network input
     _step(lib, x, x1, F, d, schedule.correct[i], x, None, xin if feeds_next else None)
   return x

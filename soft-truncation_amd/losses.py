@@ -272,44 +272,68 @@ def get_ddpm_loss_fn(config, vpsde, train):
   return loss_fn
 
 
-class _EdmLoss(torch.autograd.Function):
+class _KeptResidual(torch.autograd.Function):
+  """What the squared-residual losses share (csrc/sqloss.h): the loss launch keeps its residual r when the raw network output F
+  needs a gradient, and the backward is the gradient launch IN PLACE on that r, so a second backward through the same
+  evaluation is refused.  A subclass names itself (NAME, WS_QUERY) and gives the two launches."""
+
+  @classmethod
+  def keep(cls, ctx, lib, F, launch):
+    """The forward: ``launch(ws, r, losses, B, inner, stream)`` -> what the gradient launch needs beside r."""
+    from .engine import lib as stk_lib
+    B, inner = F.shape[0], F[0].numel()
+    key = (cls.WS_QUERY, B, inner, F.device)
+    ws = _fused_bufs.get(key)
+    if ws is None:       # per batch shape: the partial sums, consumed by the finishing pass of the same call
+      ws_bytes = int(getattr(lib, cls.WS_QUERY)(B, inner))
+      if ws_bytes < 0:
+        raise ValueError(f'stk_{cls.WS_QUERY} refuses a batch of {B} rows of {inner} (rc={ws_bytes})')
+      ws = _fused_bufs[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=F.device)
+    r = torch.empty_like(F) if ctx.needs_input_grad[0] else None
+    losses = torch.empty(B, dtype=torch.float32, device=F.device)
+    with stk_lib.device_guard(F.device):
+      extras = launch(ws, r, losses, B, inner, stk_lib.stream_ptr(F.device))
+    ctx.args = (lib, B, inner, r, extras)
+    return losses
+
+  @classmethod
+  def spend(cls, ctx, dloss, launch_grad):
+    """The backward: ``launch_grad(lib, r, extras, dloss, B, inner, stream)`` writes dF over r, which is returned."""
+    from .engine import lib as stk_lib
+    lib, B, inner, r, extras = ctx.args
+    if r is None:
+      raise RuntimeError(f'the {cls.NAME} loss kept its residual once: a second backward through the same evaluation is not '
+                         f'possible')
+    ctx.args = (lib, B, inner, None, None)
+    with stk_lib.device_guard(r.device):
+      launch_grad(lib, r, extras, dloss.contiguous(), B, inner, stk_lib.stream_ptr(r.device))
+    return r
+
+
+class _EdmLoss(_KeptResidual):
   """losses[b] = lambda_b * reduce(r^2), r = c_skip (y + sigma n) + c_out F - y: the tail of the EDM loss on the raw network
-  output F as stk_edm_loss_f32 (include/stk_edm.h), whose residual r is kept; the backward is stk_edm_loss_grad_f32 IN PLACE
-  on that r (24 B per element for the pair), so a second backward through the same evaluation is refused."""
+  output F as stk_edm_loss_f32 (include/stk_edm.h), whose residual r is kept; the backward is stk_edm_loss_grad_f32 on that r
+  (24 B per element for the pair)."""
+  NAME, WS_QUERY = 'EDM', 'edm_ws_bytes'
 
   @staticmethod
   def forward(ctx, F, y, n, sigma, coef, lib, reduce_mean):
-    from .engine import lib as stk_lib
     F, y, n = F.contiguous(), y.contiguous(), n.contiguous()
-    B, inner = F.shape[0], F[0].numel()
-    key = ('edm_ws', B, inner, F.device)
-    ws = _fused_bufs.get(key)
-    if ws is None:       # per batch shape: the partial sums, consumed by the finishing pass of the same call
-      ws_bytes = int(lib.edm_ws_bytes(B, inner))
-      if ws_bytes < 0:
-        raise ValueError(f'stk_edm_ws_bytes refuses a batch of {B} rows of {inner} (rc={ws_bytes})')
-      ws = _fused_bufs[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=F.device)
-    keep = ctx.needs_input_grad[0]
-    r = torch.empty_like(F) if keep else None
-    losses = torch.empty(B, dtype=torch.float32, device=F.device)
-    with stk_lib.device_guard(F.device):
+
+    def launch(ws, r, losses, B, inner, stream):
       lib.edm_loss_f32(F.data_ptr(), y.data_ptr(), n.data_ptr(), sigma.data_ptr(), coef.data_ptr(), ws.data_ptr(), ws.numel(),
-                       r.data_ptr() if keep else None, losses.data_ptr(), B, inner, int(reduce_mean), stk_lib.stream_ptr(F.device))
-    ctx.args = (lib, B, inner, int(reduce_mean), r, coef)
-    return losses
+                       mutils.optional_ptr(r), losses.data_ptr(), B, inner, int(reduce_mean), stream)
+      return coef, int(reduce_mean)
+
+    return _EdmLoss.keep(ctx, lib, F, launch)
 
   @staticmethod
   def backward(ctx, dloss):
-    from .engine import lib as stk_lib
-    lib, B, inner, reduce_mean, r, coef = ctx.args
-    if r is None:
-      raise RuntimeError('the EDM loss kept its residual once: a second backward through the same evaluation is not possible')
-    ctx.args = (lib, B, inner, reduce_mean, None, coef)
-    dloss = dloss.contiguous()
-    with stk_lib.device_guard(r.device):
-      lib.edm_loss_grad_f32(r.data_ptr(), coef.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, reduce_mean,
-                            stk_lib.stream_ptr(r.device))
-    return r, None, None, None, None, None, None
+    def launch_grad(lib, r, extras, dloss, B, inner, stream):
+      coef, reduce_mean = extras
+      lib.edm_loss_grad_f32(r.data_ptr(), coef.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, reduce_mean, stream)
+
+    return (_EdmLoss.spend(ctx, dloss, launch_grad),) + (None,) * 6
 
 
 def get_edm_loss_fn(config, sde, train):
@@ -376,49 +400,32 @@ def get_edm_loss_fn(config, sde, train):
   return loss_fn
 
 
-class _CtLoss(torch.autograd.Function):
+class _CtLoss(_KeptResidual):
   """losses[b] = lambda_b (sqrt(S + c^2) - c) (/ inner), S = sum r^2, r = f(y + sigma_hi n; sigma_hi) - f(y + sigma_lo n;
   sigma_lo): the tail of the consistency loss on the two raw network outputs as stk_ct_loss_f32 (include/stk_consistency.h),
-  which keeps r and the per-sample factor of the gradient; the backward is stk_ct_loss_grad_f32 IN PLACE on that r (28 B per
-  element for the pair), so a second backward through the same evaluation is refused.  F_lo is the stop-gradient target: it
-  receives no gradient."""
+  which keeps r and the per-sample factor of the gradient; the backward is stk_ct_loss_grad_f32 on that r (28 B per element for
+  the pair).  F_lo is the stop-gradient target: it receives no gradient."""
+  NAME, WS_QUERY = 'consistency', 'ct_ws_bytes'
 
   @staticmethod
   def forward(ctx, F_hi, F_lo, y, n, sigma_hi, sigma_lo, coef, huber_c, lib, reduce_mean):
-    from .engine import lib as stk_lib
     F_hi, F_lo = F_hi.contiguous(), F_lo.contiguous()
-    B, inner = F_hi.shape[0], F_hi[0].numel()
-    key = ('ct_ws', B, inner, F_hi.device)
-    ws = _fused_bufs.get(key)
-    if ws is None:       # per batch shape: the partial sums, consumed by the finishing pass of the same call
-      ws_bytes = int(lib.ct_ws_bytes(B, inner))
-      if ws_bytes < 0:
-        raise ValueError(f'stk_ct_ws_bytes refuses a batch of {B} rows of {inner} (rc={ws_bytes})')
-      ws = _fused_bufs[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=F_hi.device)
-    keep = ctx.needs_input_grad[0]
-    r = torch.empty_like(F_hi) if keep else None
-    gfac = torch.empty(B, dtype=torch.float32, device=F_hi.device) if keep else None
-    losses = torch.empty(B, dtype=torch.float32, device=F_hi.device)
-    with stk_lib.device_guard(F_hi.device):
+
+    def launch(ws, r, losses, B, inner, stream):
+      gfac = None if r is None else torch.empty(B, dtype=torch.float32, device=F_hi.device)
       lib.ct_loss_f32(F_hi.data_ptr(), F_lo.data_ptr(), y.data_ptr(), n.data_ptr(), sigma_hi.data_ptr(), sigma_lo.data_ptr(),
-                      coef.data_ptr(), huber_c, ws.data_ptr(), ws.numel(), r.data_ptr() if keep else None,
-                      gfac.data_ptr() if keep else None, losses.data_ptr(), B, inner, int(reduce_mean),
-                      stk_lib.stream_ptr(F_hi.device))
-    ctx.args = (lib, B, inner, r, gfac)
-    return losses
+                      coef.data_ptr(), huber_c, ws.data_ptr(), ws.numel(), mutils.optional_ptr(r), mutils.optional_ptr(gfac),
+                      losses.data_ptr(), B, inner, int(reduce_mean), stream)
+      return gfac
+
+    return _CtLoss.keep(ctx, lib, F_hi, launch)
 
   @staticmethod
   def backward(ctx, dloss):
-    from .engine import lib as stk_lib
-    lib, B, inner, r, gfac = ctx.args
-    if r is None:
-      raise RuntimeError('the consistency loss kept its residual once: a second backward through the same evaluation is not '
-                         'possible')
-    ctx.args = (lib, B, inner, None, None)
-    dloss = dloss.contiguous()
-    with stk_lib.device_guard(r.device):
-      lib.ct_loss_grad_f32(r.data_ptr(), gfac.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, stk_lib.stream_ptr(r.device))
-    return (r,) + (None,) * 9
+    def launch_grad(lib, r, gfac, dloss, B, inner, stream):
+      lib.ct_loss_grad_f32(r.data_ptr(), gfac.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, stream)
+
+    return (_CtLoss.spend(ctx, dloss, launch_grad),) + (None,) * 9
 
 
 class ConsistencyLoss:

@@ -291,6 +291,21 @@ def checked_score(score_fn, x, t, lib):
   return score.contiguous()
 
 
+def fp32_levels(v):
+  """`v` rounded to fp32 and held as float64 numpy: the levels a schedule computes its float64 coefficients at."""
+  return np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def optional_ptr(t):
+  """The device pointer of an optional operand: None (null) where it is absent."""
+  return None if t is None else t.data_ptr()
+
+
+def level_conditioning(levels, B, device):
+  """[len(levels), B] fp32 on `device`: row j conditions evaluation j of a run on a batch of B, one host-to-device copy."""
+  return torch.tensor(levels, dtype=torch.float32).to(device)[:, None].expand(-1, B).contiguous()
+
+
 def get_model_fn(model, train=False):
   """Callable running the model in train or eval mode, re-asserted on every call (models/utils.py:97-126)."""
 

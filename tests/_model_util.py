@@ -135,3 +135,23 @@ def grads_close(model, ref, tol):
       worst, wk = e, k
   assert worst <= tol, f'parameter gradient mismatch {worst:.3e} at {wk}'
   return worst
+
+
+class Tap(torch.nn.Module):
+  """Records what a loss hands to the network -- (x, cond, out, whether gradients were enabled) per call -- and keeps the
+  gradient of what it returns; the engine and the dropout predicate show through, so the loss takes the path it would take on
+  the model itself."""
+
+  def __init__(self, model):
+    super().__init__()
+    self.inner = model
+    self.engine = model.module.engine
+    self._uses_dropout = getattr(model.module, '_uses_dropout', None)
+    self.seen = []
+
+  def forward(self, x, cond):
+    out = self.inner(x, cond)
+    if out.requires_grad:
+      out.retain_grad()
+    self.seen.append((x.detach().clone(), cond.detach().clone(), out, torch.is_grad_enabled()))
+    return out

@@ -1,4 +1,5 @@
-"""Helpers of the GPU tests of the streaming kernels (test_gpu_impute.py, test_gpu_dpm_solver.py, test_gpu_adaptive_sde.py):
+"""Helpers of the GPU tests of the streaming kernels (test_gpu_impute.py, test_gpu_dpm_solver.py, test_gpu_adaptive_sde.py
+and the files since):
 operands on the 16-byte and on the scalar path, and the per-element rounding bound k u B."""
 import numpy as np
 import torch
@@ -68,3 +69,35 @@ class Guarded:
 def case_id(v):
   """Parametrize id of a (shape, shifted) case: '2x3x8x8' for the shape, 'aligned' / 'entered-one-in' for the flag."""
   return 'x'.join(map(str, v)) if isinstance(v, tuple) else ('entered-one-in' if v else 'aligned')
+
+
+def stream():
+  """The raw handle of torch's current stream, as the C entries take it."""
+  return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+  """The device pointer of an optional operand: None (null) where it is absent."""
+  return None if t is None else t.data_ptr()
+
+
+def nan(shape, dev, shifted=False):
+  """An output buffer full of NaN, placed like an operand: whatever a launch leaves unwritten shows."""
+  return place(torch.full(shape, float('nan')), dev, shifted)
+
+
+# vector path; n = 315, scalar path; one element; a 16-byte-aligned buffer entered one element in (scalar path); 3072 blocks
+# of vector items against stk_ew_grid's cap of 2048 (the grid strides); the same entered one element in (scalar grid strides)
+SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True),
+          ((16, 3, 256, 256), False), ((16, 3, 256, 256), True)]
+# ... and for the per-sample kernels: 48 blocks share each row; 3000 rows of 4 stride the 2048 rows of the grid
+ROW_SHAPES = SHAPES + [((4, 3, 256, 256), False), ((3000, 1, 2, 2), False)]
+
+
+def drawn_operands(cases=ROW_SHAPES, scales=(1.5, 2.0, 1.0, 0.8)):
+  """One fp32 tensor per scale and per shape of `cases` on the host (numpy), drawn from a seed the shape gives."""
+  out = {}
+  for shape in sorted({s for s, _ in cases}):
+    rng = np.random.RandomState(sum(shape))
+    out[shape] = [(rng.standard_normal(shape) * scale).astype(np.float32) for scale in scales]
+  return out

@@ -26,7 +26,7 @@ import torch
 
 import _adaptive_ref as R
 from _sampler_util import sampler, setup, shape_of as _shape
-from _stream_util import case_id, place, within
+from _stream_util import case_id, place, stream as _stream, within
 
 pytestmark = pytest.mark.gpu
 
@@ -53,10 +53,6 @@ F09 = float(np.float32(0.9))          # the controller's constants as the entry 
 # twelve blocks on the scalar path); 2048 blocks, each striding along its row
 SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True), ((2, 3, 32, 32), False),
           ((2, 3, 32, 32), True), ((16, 3, 256, 256), False)]
-
-
-def _stream():
-  return torch.cuda.current_stream().cuda_stream
 
 
 def _rows(B):

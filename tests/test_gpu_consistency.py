@@ -49,8 +49,8 @@ import pytest
 import torch
 
 import _consistency_ref as R
-from _model_util import make_state, patched_rng, randomize_, tiny_config
-from _stream_util import U, case_id, place, within
+from _model_util import Tap as _Tap, make_state, patched_rng, randomize_, tiny_config
+from _stream_util import ROW_SHAPES, SHAPES, U, case_id, drawn_operands, nan as _nan, place, ptr as _ptr, stream as _stream, within
 
 pytestmark = pytest.mark.gpu
 
@@ -71,34 +71,10 @@ E32 = float(np.float32(S_MIN))
 EINVAL, EUNSUPPORTED = -1, -3
 INF = float('inf')
 f32 = lambda v: float(np.float32(v))
-# vector path; n = 315, scalar path; one element; a 16-byte-aligned buffer entered one element in (scalar path); 3072 blocks
-# of vector items against stk_ew_grid's cap of 2048 (the grid strides); the same entered one element in (scalar grid strides)
-SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True),
-          ((16, 3, 256, 256), False), ((16, 3, 256, 256), True)]
-# ... and for the per-sample kernels: 48 blocks share each row; 3000 rows of 4 stride the 2048 rows of the grid
-ROW_SHAPES = SHAPES + [((4, 3, 256, 256), False), ((3000, 1, 2, 2), False)]
-
-
-def _stream():
-  return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
-def _nan(shape, dev, shifted=False):
-  return place(torch.full(shape, float('nan')), dev, shifted)
-
-
 @pytest.fixture(scope='module')
 def operands():
   """Four fp32 tensors per shape on the host (numpy), drawn once: x / y, z / n, F / F_hi, F_lo."""
-  out = {}
-  for shape in sorted({s for s, _ in ROW_SHAPES}):
-    rng = np.random.RandomState(sum(shape))
-    out[shape] = [(rng.standard_normal(shape) * scale).astype(np.float32) for scale in (1.5, 2.0, 1.0, 0.8)]
-  return out
+  return drawn_operands()
 
 
 def _pairs(B):
@@ -421,25 +397,6 @@ def test_return_codes_and_nothing_written(hip_lib):
 
 
 # ---- the fused loss against the torch-expression loss ---------------------------------------------------------------------
-class _Tap(torch.nn.Module):
-  """Records what the loss hands to the network and keeps the gradient of what it returns; the engine and the dropout
-  predicate show through, so the loss takes the path it would take on the model itself."""
-
-  def __init__(self, model):
-    super().__init__()
-    self.inner = model
-    self.engine = model.module.engine
-    self._uses_dropout = model.module._uses_dropout
-    self.seen = []
-
-  def forward(self, x, cond):
-    out = self.inner(x, cond)
-    if out.requires_grad:
-      out.retain_grad()
-    self.seen.append((x.detach().clone(), cond.detach().clone(), out, torch.is_grad_enabled()))
-    return out
-
-
 _built = {}
 
 

@@ -41,8 +41,8 @@ import pytest
 import torch
 
 import _edm_ref as R
-from _model_util import build_pair, patched_rng, tiny_config
-from _stream_util import U, case_id, place, within
+from _model_util import Tap as _Tap, build_pair, patched_rng, tiny_config
+from _stream_util import ROW_SHAPES, SHAPES, U, case_id, drawn_operands, nan as _nan, place, ptr as _ptr, stream as _stream, within
 
 pytestmark = pytest.mark.gpu
 
@@ -63,34 +63,10 @@ EINVAL, EUNSUPPORTED = -1, -3
 f32 = lambda v: float(np.float32(v))
 # (cs, co, t, h, c_next): a step from t^ = 2.6 to 1.9 at sigma_data = 0.5
 ROW = tuple(f32(v) for v in (0.0357, 0.491, 2.6, -0.7, 0.509))
-# vector path; n = 315, scalar path; one element; a 16-byte-aligned buffer entered one element in (scalar path); 3072 blocks
-# of vector items against stk_ew_grid's cap of 2048 (the grid strides); the same entered one element in (scalar grid strides)
-SHAPES = [((2, 3, 8, 8), False), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 8, 8), True),
-          ((16, 3, 256, 256), False), ((16, 3, 256, 256), True)]
-# ... and for the per-sample kernels: 48 blocks share each row; 3000 rows of 4 stride the 2048 rows of the grid
-ROW_SHAPES = SHAPES + [((4, 3, 256, 256), False), ((3000, 1, 2, 2), False)]
-
-
-def _stream():
-  return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
-def _nan(shape, dev, shifted):
-  return place(torch.full(shape, float('nan')), dev, shifted)
-
-
 @pytest.fixture(scope='module')
 def operands():
   """Four fp32 tensors per shape on the host (numpy), drawn once: xb / y, xe / n, F, d_prev."""
-  out = {}
-  for shape in sorted({s for s, _ in ROW_SHAPES}):
-    rng = np.random.RandomState(sum(shape))
-    out[shape] = [(rng.standard_normal(shape) * scale).astype(np.float32) for scale in (1.5, 2.0, 1.0, 0.8)]
-  return out
+  return drawn_operands()
 
 
 # ---- stk_edm_step_f32 ---------------------------------------------------------------------------------------------------
@@ -392,24 +368,6 @@ def test_return_codes_and_nothing_written(hip_lib):
 
 
 # ---- the fused loss against the torch-expression loss ---------------------------------------------------------------------
-class _Tap(torch.nn.Module):
-  """Records what the loss hands to the network and keeps the gradient of what it returns; the engine shows through, so the
-  loss takes the path it would take on the model itself."""
-
-  def __init__(self, model):
-    super().__init__()
-    self.inner = model
-    self.engine = model.module.engine
-    self.seen = []
-
-  def forward(self, x, cond):
-    out = self.inner(x, cond)
-    if out.requires_grad:
-      out.retain_grad()
-    self.seen.append((x.detach().clone(), cond.detach().clone(), out))
-    return out
-
-
 _built = {}
 
 
@@ -456,7 +414,7 @@ def test_fused_loss_matches_the_torch_expressions(st, hip_lib, family, reduce_me
         losses = loss_fn(tap, batch)
       (losses * go).sum().backward()
       assert calls == ['loss'], f'fused={fused}: stk_edm_loss_f32 ran {len(calls)} times so far'
-      x_in, cond, F = tap.seen[0]
+      x_in, cond, F, _ = tap.seen[0]
       seen[fused] = (x_in, cond)
       F64 = F.detach().cpu().double().numpy()
       r = w(rows[2]) * (y + w(sg64) * n64) + w(rows[3]) * F64 - y

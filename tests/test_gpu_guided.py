@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import _guided_ref as G
-from _stream_util import case_id, place, within
+from _stream_util import case_id, place, stream as _stream, within
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +18,6 @@ NAN = float('nan')
 EINVAL, EUNSUPPORTED = -1, -3
 f32 = lambda v: float(np.float32(v))
 ROW = tuple(f32(v) for v in (1.3, 0.7, 0.45, 0.8, 0.35))          # (cx, cs, g, A, B): a second-order step
-
-
-def _stream():
-  return torch.cuda.current_stream().cuda_stream
 
 
 def _ws(lib, B, n, dev):

@@ -23,7 +23,7 @@ import pytest
 import torch
 
 import _posterior_ref as R
-from _stream_util import case_id, place, within
+from _stream_util import case_id, place, stream as _stream, within
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +37,6 @@ ZETA = float(np.float32(0.7))
 SHAPES = [((2, 3, 8, 8), False), ((2, 3, 8, 8), True), ((3, 3, 5, 7), False), ((1, 1, 1, 1), False), ((2, 3, 32, 32), False),
           ((2, 3, 32, 32), True), ((2049, 1, 2, 2), False)]
 ROWS = (5, 48)
-
-
-def _stream():
-  return torch.cuda.current_stream().cuda_stream
 
 
 def _operands(shape, seed):

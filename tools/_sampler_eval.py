@@ -1,7 +1,10 @@
-"""What the sampler evaluation scripts share (inpaint_eval.py, solver_eval.py, adaptive_eval.py): the benchmark workload with
-a random-weight model on the device, the timing of back-to-back launches and of one network evaluation, and the report."""
+"""What the evaluation scripts share (inpaint_eval.py, solver_eval.py, adaptive_eval.py, posterior_eval.py, superres_eval.py,
+guided_eval.py, adagn_eval.py, edm_eval.py, consistency_eval.py): the benchmark workload with a random-weight model on the
+device, the timing of back-to-back launches (on one buffer set or rotating over several), of whole calls and of one network
+evaluation, and the report."""
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -47,6 +50,56 @@ def launches_alone(call, reps, bytes_moved):
   e1.synchronize()
   us = 1e3 * e0.elapsed_time(e1) / reps
   return us, bytes_moved / (us * 1e-6) / 1e12
+
+
+ROTATE_BYTES, MAX_SETS = 1 << 30, 64
+
+
+def set_count(per_set, most=MAX_SETS):
+  """Buffer sets to rotate over so that ROTATE_BYTES pass between two uses of one set: at least 2, at most `most`."""
+  sets = max(2, -(-ROTATE_BYTES // per_set))
+  return sets if most is None else min(most, sets)
+
+
+def rotating(call, sets):
+  """A callable whose i-th call is ``call(sets[i % len(sets)])``."""
+  state = {'i': 0}
+
+  def step():
+    call(sets[state['i'] % len(sets)])
+    state['i'] += 1
+  return step
+
+
+def timed(calls, reps, warm=4):
+  """us per call of `reps` calls between two events; call i is calls[i % len(calls)] (one per buffer set), after one warm-up
+  of each of the first `warm` (None: all)."""
+  for c in calls[:warm]:
+    c()
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  for i in range(reps):
+    calls[i % len(calls)]()
+  e1.record()
+  e1.synchronize()
+  return 1e3 * e0.elapsed_time(e1) / reps
+
+
+def wall(fn, rounds):
+  """ms per call of each of the callables `fn` (a dict): wall time over a synchronisation, one warm-up each, `rounds`
+  alternating rounds, medians."""
+  for f in fn.values():
+    f()
+  torch.cuda.synchronize()
+  took = {k: [] for k in fn}
+  for r in range(rounds):
+    for k in (list(fn) if r % 2 == 0 else reversed(list(fn))):
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      fn[k]()
+      torch.cuda.synchronize()
+      took[k].append(1e3 * (time.perf_counter() - t0))
+  return {k: statistics.median(v) for k, v in took.items()}
 
 
 def evaluation(score_fn, sde, shape, device, reps=5):

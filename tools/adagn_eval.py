@@ -40,25 +40,11 @@ args = ap.parse_args()
 assert torch.cuda.is_available(), 'adagn_eval.py measures on the GPU: there is nothing to report without one'
 device = torch.device('cuda', 0)
 G, EPS, ACT = 32, 1e-6, 1
-ROTATE_BYTES = 1 << 30
-
-
-def timed(calls, reps):
-  """us per launch of `reps` launches between two events; launch i takes calls[i % len(calls)] (one per buffer set)."""
-  for c in calls:
-    c()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for i in range(reps):
-    calls[i % len(calls)]()
-  e1.record()
-  e1.synchronize()
-  return 1e3 * e0.elapsed_time(e1) / reps
 
 
 def kernels(lib, N, C, HW, lines):
   n = N * C * HW
-  sets = max(2, -(-ROTATE_BYTES // (16 * n)))             # x, y, dy, dx of 4 n bytes each per set
+  sets = E.set_count(16 * n, most=None)           # x, y, dy, dx of 4 n bytes each per set
   s = torch.cuda.current_stream().cuda_stream
   p = lambda t: t.data_ptr()
   gamma, beta = 1 + 0.2 * torch.randn(C, device=device), 0.3 * torch.randn(C, device=device)
@@ -88,7 +74,7 @@ def kernels(lib, N, C, HW, lines):
   lines.append(f'  (N, C, HW) = ({N}, {C}, {HW}), {4 * n / 2 ** 20:.0f} MiB per tensor, {sets} buffer sets in the rotation:')
   for label, pick in (('one set (cache-resident where it fits)', lambda c: c[:1]), ('rotating sets (from HBM)', lambda c: c)):
     # the four forms in one order in the even rounds and in the reverse order in the odd ones: no form always runs behind the same one
-    rounds = [{k: timed(pick(forms[k]), args.reps) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
+    rounds = [{k: E.timed(pick(forms[k]), args.reps, warm=None) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
               for r in range(args.rounds)]
     med = {k: statistics.median(r[k] for r in rounds) for k in forms}
     lines.append(f'    {label}: ' + '; '.join(f'{k} {med[k]:.1f} us = {nbytes[k] / (med[k] * 1e-6) / 1e12:.2f} TB/s' for k in forms)

@@ -38,7 +38,7 @@ def launches_alone(reps=200):
   row1, row2 = ada.stage_rows(sde, t, h), ada.heun_rows(sde, ada.next_time(t, h, eps), h)
   ws_bytes = lib.sde_ws_bytes(B, n)
   ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=device)
-  t_out, h_out, E = (torch.empty(B, device=device) for _ in range(3))
+  t_out, h_out, err = (torch.empty(B, device=device) for _ in range(3))
   accept = torch.empty(B, dtype=torch.int32, device=device)
   stream = stk_lib.stream_ptr(device)
   p = lambda v: v.data_ptr()
@@ -48,7 +48,7 @@ def launches_alone(reps=200):
     'stk_sde_heun_error_f32': (6, lambda: lib.sde_heun_error_f32(p(x), p(x1), p(x1_prev), p(s), p(z), p(row2), atol, 1e30, p(x2),
                                                                  p(ws), ws_bytes, B, n, stream)),
     'stk_sde_commit_f32': (4, lambda: lib.sde_commit_f32(p(xc), p(pc), p(x2), p(x1), p(t), p(h), eps, 0.9, 0.9, p(ws), ws_bytes,
-                                                         p(t_out), p(h_out), p(E), p(accept), B, n, stream)),
+                                                         p(t_out), p(h_out), p(err), p(accept), B, n, stream)),
   }
   out = []
   for name, (tensors, call) in calls.items():

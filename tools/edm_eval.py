@@ -27,7 +27,6 @@ import argparse
 import gc
 import os
 import statistics
-import time
 
 import torch
 
@@ -44,29 +43,15 @@ ap.add_argument('--out', default=os.path.join(E.ROOT, 'profiles', 'edm_eval.txt'
 args = ap.parse_args()
 assert torch.cuda.is_available(), 'edm_eval.py measures on the GPU: there is nothing to report without one'
 device = torch.device('cuda', 0)
-ROTATE_BYTES, MAX_SETS = 1 << 30, 64
 DPM_ROW = (1.3, 0.7, 0.45, 0.8, 0.35)      # (cx, cs, g, A, B): a second-order step
 ROW = (0.0357, 0.491, 2.6, -0.7, 0.509)    # (cs, co, t, h, c_next): a step from t^ = 2.6 to 1.9 at sigma_data = 0.5
 INF = float('inf')
 
 
-def timed(calls, reps):
-  """us per call of `reps` calls between two events; call i is calls[i % len(calls)] (one per buffer set)."""
-  for c in calls[:4]:
-    c()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for i in range(reps):
-    calls[i % len(calls)]()
-  e1.record()
-  e1.synchronize()
-  return 1e3 * e0.elapsed_time(e1) / reps
-
-
 def measure(lib, B, n, lines):
   total = B * n
   per_set = 9 * 4 * total                       # x, x', F, d, n, r, x-out, d-out, xin-out
-  sets = max(2, min(MAX_SETS, -(-ROTATE_BYTES // per_set)))
+  sets = E.set_count(per_set)
   s = torch.cuda.current_stream().cuda_stream
   p = lambda t: t.data_ptr()
   nbytes = int(lib.edm_ws_bytes(B, n))
@@ -121,30 +106,13 @@ def measure(lib, B, n, lines):
   lines.append(f'  (B, n) = ({B}, {n}), {4 * total / 2 ** 20:.1f} MiB per tensor, {sets} buffer sets in the rotation '
                f'({sets * per_set / 2 ** 20:.0f} MiB):')
   for label, pick in (('one set (cache-resident where it fits)', lambda c: c[:1]), ('rotating sets', lambda c: c)):
-    rounds = [{k: timed(pick(forms[k]), args.reps) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
+    rounds = [{k: E.timed(pick(forms[k]), args.reps) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
               for r in range(args.rounds)]
     med = {k: statistics.median(r[k] for r in rounds) for k in forms}
     lines.append(f'    {label}:')
     for k in forms:
       lines.append(f'      {k:18s} {med[k]:9.1f} us = {per_elem[k] * total / (med[k] * 1e-6) / 1e12:5.2f} TB/s of {per_elem[k]} B per element')
     lines.append('      fused / torch: ' + ', '.join(f'{k} {med[k] / med["torch " + k]:.3f}x' for k in ('loss pair', 'euler', 'correction')))
-
-
-def wall(fn, rounds):
-  """ms per call of each of the callables `fn` (a dict): wall time over a synchronisation, one warm-up each, `rounds`
-  alternating rounds, medians."""
-  for f in fn.values():
-    f()
-  torch.cuda.synchronize()
-  took = {k: [] for k in fn}
-  for r in range(rounds):
-    for k in (list(fn) if r % 2 == 0 else reversed(list(fn))):
-      torch.cuda.synchronize()
-      t0 = time.perf_counter()
-      fn[k]()
-      torch.cuda.synchronize()
-      took[k].append(1e3 * (time.perf_counter() - t0))
-  return {k: statistics.median(v) for k, v in took.items()}
 
 
 def network_parts(lines):
@@ -171,11 +139,11 @@ def network_parts(lines):
     step_fn = st.losses.get_step_fn(cfg, sde, train=True, optimize_fn=st.losses.optimization_manager(cfg))
     batch = st.datasets.synthetic_batch(cfg, B, device=device, generator=torch.Generator().manual_seed(4321))
     steps[name] = (lambda step_fn=step_fn, state=state, batch=batch: [step_fn(state, batch) for _ in range(5)])
-  ms = wall(runs, args.rounds)
+  ms = E.wall(runs, args.rounds)
   lines.append(f'  whole run on the CIFAR-10 DDPM++ network, batch {B}, random weights:')
   lines.append(f'    DPM-Solver++ 2M, 20 steps + denoise (21 evaluations, VP)  {ms["vp"]:8.1f} ms = {ms["vp"] / 21:.2f} ms per evaluation')
   lines.append(f'    EDM Heun, 18 steps (35 evaluations)                       {ms["edm"]:8.1f} ms = {ms["edm"] / 35:.2f} ms per evaluation')
-  ms = wall(steps, args.rounds)
+  ms = E.wall(steps, args.rounds)
   lines.append(f'  training step, batch {B} (five steps per figure):')
   lines.append(f'    VP soft-truncation step   {ms["vp"] / 5:7.2f} ms = {B / (ms["vp"] / 5) * 1e3:.0f} images/s')
   lines.append(f'    EDM step (configs.edm)    {ms["edm"] / 5:7.2f} ms = {B / (ms["edm"] / 5) * 1e3:.0f} images/s')

@@ -38,30 +38,16 @@ ap.add_argument('--out', default=os.path.join(E.ROOT, 'profiles', 'guided_eval.t
 args = ap.parse_args()
 assert torch.cuda.is_available(), 'guided_eval.py measures on the GPU: there is nothing to report without one'
 device = torch.device('cuda', 0)
-ROTATE_BYTES, MAX_SETS = 1 << 30, 64
 P, FLOOR = 0.995, 1.0
 ROW = (1.3, 0.7, 0.45, 0.8, 0.35)          # (cx, cs, g, A, B): a second-order step
 W, PHI = 2.0, 0.7
 INF = float('inf')
 
 
-def timed(calls, reps):
-  """us per call of `reps` calls between two events; call i is calls[i % len(calls)] (one per buffer set)."""
-  for c in calls[:4]:
-    c()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for i in range(reps):
-    calls[i % len(calls)]()
-  e1.record()
-  e1.synchronize()
-  return 1e3 * e0.elapsed_time(e1) / reps
-
-
 def measure(lib, B, n, lines):
   total = B * n
   per_set = 7 * 4 * total                       # x, score, d_prev, d_raw, c-out, x-out, d-out
-  sets = max(2, min(MAX_SETS, -(-ROTATE_BYTES // per_set)))
+  sets = E.set_count(per_set)
   s = torch.cuda.current_stream().cuda_stream
   p = lambda t: t.data_ptr()
   nbytes = int(lib.guided_ws_bytes(B, n))
@@ -113,7 +99,7 @@ def measure(lib, B, n, lines):
   for label, pick in (('one set (cache-resident where it fits)', lambda c: c[:1]), ('rotating sets', lambda c: c)):
     # "select after predict" times the two levels and the finish on the histogram the last predict pass of ANY set left: the
     # counts are another set's, the streaming work is the same
-    rounds = [{k: timed(pick(forms[k]), args.reps) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
+    rounds = [{k: E.timed(pick(forms[k]), args.reps) for k in (list(forms) if r % 2 == 0 else reversed(list(forms)))}
               for r in range(args.rounds)]
     med = {k: statistics.median(r[k] for r in rounds) for k in forms}
     lines.append(f'    {label}:')

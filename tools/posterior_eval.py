@@ -82,15 +82,6 @@ def composed(b, a, s):
   return x0, r, rnorm, seed, b['xp'] + step, b['xpm'] + step
 
 
-def rotating(call, sets):
-  state = {'i': 0}
-
-  def step():
-    call(sets[state['i'] % len(sets)])
-    state['i'] += 1
-  return step
-
-
 def launches_section(lines):
   B, C, H = args.batch, 3, args.size
   state_bytes, meas_bytes = 4 * B * C * H * H, 4 * B * C * (H // 4) ** 2
@@ -108,8 +99,8 @@ def launches_section(lines):
   for _ in range(3):
     rounds.append((E.launches_alone(lambda: kernel(sets[0]), args.reps, moved),
                    E.launches_alone(lambda: torch_form(sets[0]), args.reps, moved),
-                   E.launches_alone(rotating(kernel, sets), args.reps, moved),
-                   E.launches_alone(rotating(torch_form, sets), args.reps, moved)))
+                   E.launches_alone(E.rotating(kernel, sets), args.reps, moved),
+                   E.launches_alone(E.rotating(torch_form, sets), args.reps, moved)))
   lines.append(f'1. The four launches of include/stk_posterior.h on a [{B},{C},{H},{H}] fp32 state with a [{B},{C},{H // 4},{H // 4}] '
                f'measurement, clamp [-1, 1], x_mean written: {moved / 1e6:.1f} MB per step by their byte count (12 state-sized and 3 '
                f'measurement-sized tensors).  {args.reps} back-to-back steps between two device events after 10 warm-ups; three '

@@ -50,15 +50,6 @@ def composed(x, low, z, a, s, r):
   return x + up(known - m), x + up(mean - m)
 
 
-def rotating(call, sets):
-  state = {'i': 0}
-
-  def step():
-    call(*sets[state['i'] % len(sets)])
-    state['i'] += 1
-  return step
-
-
 lines = [f'stk_superres_f32 on a [{B},{C},{H},{H}] fp32 state, x_mean written, {args.reps} back-to-back launches between two device '
          f'events after 10 warm-ups; three rounds, kernel and torch composition alternating.  "resident": one set of buffers (it '
          f'fits the 256 MiB last-level cache); "rotating": as many sets as exceed that cache.']
@@ -78,8 +69,8 @@ for r in cg.FACTORS:
   for _ in range(3):
     rounds.append((E.launches_alone(lambda: kernel(*sets[0]), args.reps, moved),
                    E.launches_alone(lambda: torch_form(*sets[0]), args.reps, moved),
-                   E.launches_alone(rotating(kernel, sets), args.reps, moved),
-                   E.launches_alone(rotating(torch_form, sets), args.reps, moved)))
+                   E.launches_alone(E.rotating(lambda b: kernel(*b), sets), args.reps, moved),
+                   E.launches_alone(E.rotating(lambda b: torch_form(*b), sets), args.reps, moved)))
   lines.append(f'factor {r}: {moved / 1e6:.1f} MB per launch by its byte count, {n_sets} buffer sets when rotating')
   for j, name in enumerate(('kernel, resident', 'torch,  resident', 'kernel, rotating', 'torch,  rotating')):
     best = min(rd[j][0] for rd in rounds)
