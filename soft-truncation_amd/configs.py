@@ -295,6 +295,15 @@ def edm(config, sigma_min=0.002, sigma_max=80., sigma_data=0.5, p_mean=-1.2, p_s
   return config
 
 
+def edm_augment(config, p=0.12, **edm_options):
+  """`edm(config)` trained under non-leaky augmentation (Karras et al. 2022, appendix F.2; augment.py): every transform fires
+  with probability p = 0.12 (the paper's CIFAR-10 setting) and the network takes the nine augmentation labels."""
+  config = edm(config, **edm_options)
+  config.training.augment = p
+  config.model.augment_dim = 9
+  return config
+
+
 def consistency(config, s0=10, s1=1280, p_mean=-1.1, p_std=2.0, huber_c=0.00054, levels=None, clip=True, **edm_options):
   """The consistency-training variant of any config above (Song & Dhariwal 2023, iCT): :func:`edm` of it (``edm_options`` are
   its keywords) with ``training.consistency`` on -- the discretised log-normal over neighbouring levels, the curriculum from

@@ -380,10 +380,10 @@ class Program:
 
 class _NetFn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, ex, training, anchor, x, emb_in, sigma, cls=None):
+  def forward(ctx, ex, training, anchor, x, emb_in, sigma, cls=None, aug=None):
     need_xgrad = bool(ctx.needs_input_grad[3])
     # grad mode is OFF inside autograd.Function.forward: say explicitly that a backward will follow
-    out, c = ex.run_forward(x, emb_in, sigma, training, need_xgrad, with_backward=True, flat=ex.flat, cls=cls)
+    out, c = ex.run_forward(x, emb_in, sigma, training, need_xgrad, with_backward=True, flat=ex.flat, cls=cls, aug=aug)
     ctx.ex, ctx.c, ctx.need_xgrad = ex, c, need_xgrad
     ex._awaiting.add(c)       # a backward of this evaluation may still come (dropped with the autograd graph otherwise)
     return out
@@ -398,7 +398,7 @@ class _NetFn(torch.autograd.Function):
     # weight / bias / affine gradients are neither computed nor added into p.grad -- as in the reference, where autograd
     # only walks the branches that were asked for.
     gx = ctx.ex.run_backward(ctx.c, gout, param_grads=_wants_param_grads(ctx.ex._anchor_acc))
-    return None, None, None, (gx if ctx.need_xgrad else None), None, None, None
+    return None, None, None, (gx if ctx.need_xgrad else None), None, None, None, None
 
 
 def _wants_param_grads(anchor_acc):
@@ -680,13 +680,13 @@ class Executor:
     self.graph_replays += 1
     return True
 
-  def run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward=False, flat=None, cls=None):
+  def run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward=False, flat=None, cls=None, aug=None):
     if flat is None:                      # apply() has just checked the layout: one walk over the ~570 parameters per call
       flat = self.ensure_flat()
     with stk_lib.device_guard(flat.device):
-      return self._run_forward(x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls)
+      return self._run_forward(x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls, aug)
 
-  def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls=None):
+  def _run_forward(self, x, emb_in, sigma, training, need_xgrad, with_backward, flat, cls=None, aug=None):
     B, _, H, W = x.shape
     if (with_backward or need_xgrad) and self.train_mode != 'fp32':
       precision = self.train_mode + '-train'
@@ -701,6 +701,8 @@ class Executor:
       inputs['sigma'] = sigma
     if cls is not None:                   # the class indices of a class-conditional network, [B] fp32-encoded integers
       inputs['cls'] = cls
+    if aug is not None:                   # the augmentation labels of a network with an augmentation embedding, [B, K]
+      inputs['aug'] = aug
     return self._launch_forward(prog, inputs, training, with_backward, flat)
 
   def _uses_dropout(self):
@@ -886,14 +888,14 @@ class Executor:
     rows.sort(key=lambda r: -r[3])
     return rows
 
-  def apply(self, x, emb_in, sigma=None, cls=None):
+  def apply(self, x, emb_in, sigma=None, cls=None, aug=None):
     """Differentiable network evaluation (forward now, backward when autograd asks)."""
     self.ensure_flat()
     training = self.model.training
     x = x.contiguous()
     if torch.is_grad_enabled():
-      return _NetFn.apply(self, training, self._anchor, x, emb_in, sigma, cls)
-    out, c = self.run_forward(x, emb_in, sigma, training, False, flat=self.flat, cls=cls)
+      return _NetFn.apply(self, training, self._anchor, x, emb_in, sigma, cls, aug)
+    out, c = self.run_forward(x, emb_in, sigma, training, False, flat=self.flat, cls=cls, aug=aug)
     c.prog.release(c)
     return out
 

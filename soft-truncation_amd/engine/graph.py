@@ -815,6 +815,37 @@ class ClassEmbedding(Op):
       rt.lib.class_embed_bwd_f32(rt.g(self.y), rt.v(self.cls), gt, self.b(self.t), gtable, self.B, self.C, self.D, rt.stream)
 
 
+class AugmentEmbedding(Op):
+  """y[b] = t[b] + W labels[b] -- the augmentation labels of a network trained under non-leaky augmentation, mapped linearly
+  into the time embedding between its two activations, after the class row where there is one (include/stk_augment.h).
+  `aug` is a graph input [B, K]; W is [D, K] as nn.Linear keeps it, without a bias.  Only the product library has the
+  kernels: on any other the operation is refused here, when the graph is planned.  The backward passes the gradient of t
+  through and accumulates the weight's into its slot of the flat gradient -- unless the backward is input-only
+  (Runtime.param_grads), which skips it as it skips every parameter."""
+
+  def __init__(self, g, t, aug, weight, name='temb.augment'):
+    lib = g.lib
+    if not getattr(lib, 'has_augment', False):
+      raise NotImplementedError(f'backend {getattr(lib, "backend", None)} does not export include/stk_augment.h: no kernel '
+                                f'adds the augmentation embedding of config.model.augment_dim > 0')
+    self.t, self.aug, self.weight = t, aug, weight
+    self.B, self.D = t.shape
+    self.K = weight.shape[1]
+    if weight.shape[0] != self.D or aug.shape != (self.B, self.K):
+      raise RuntimeError(f'{name}: weight {tuple(weight.shape)} and labels {tuple(aug.shape)} do not fit an embedding '
+                         f'{tuple(t.shape)}')
+    self.y = g.new(t.shape, name=name)
+    self.inputs = (t,)
+
+  def forward(self, rt):
+    rt.lib.aug_embed_fwd_f32(rt.v(self.t), rt.v(self.aug), rt.v(self.weight), rt.v(self.y), self.B, self.K, self.D, rt.stream)
+
+  def backward(self, rt):
+    gt, gw = rt.g(self.t), rt.g(self.weight)
+    if gt is not None or gw is not None:
+      rt.lib.aug_embed_bwd_f32(rt.g(self.y), rt.v(self.aug), gt, self.b(self.t), gw, self.B, self.K, self.D, rt.stream)
+
+
 class Affine(Op):
   """y = a*x + b (the `2x - 1` recentring, models/ncsnpp.py:296-298)."""
 

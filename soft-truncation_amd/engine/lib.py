@@ -232,6 +232,15 @@ SIGNATURES_GUIDED = {
   'stk_cfg_rescale_f32': [P, P, F, F, P, I, L, P, L, S],
 }
 _RESTYPE_GUIDED = {'stk_guided_ws_bytes': c_long}
+# include/stk_augment.h: the non-leaky geometric augmentation in one launch (the taps are a HOST pointer) and the embedding of
+# the augmentation labels (engine.graph.AugmentEmbedding refuses to plan without it).
+SIGNATURES_AUGMENT = {
+  'stk_aug_ok': [I, I, I],
+  'stk_aug_warp_f32': [P, P, P, I, P, I, I, I, I, S],
+  'stk_aug_embed_fwd_f32': [P, P, P, P, I, I, I, S],
+  'stk_aug_embed_bwd_f32': [P, P, P, F, P, I, I, I, S],
+}
+_NO_CHECK_AUGMENT = {'stk_aug_ok'}                                               # its query
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -255,6 +264,7 @@ OPTIONAL_HEADERS = (
   Header('has_posterior', 'include/stk_posterior.h', SIGNATURES_POSTERIOR, _RESTYPE_POSTERIOR, ()),
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
+  Header('has_augment', 'include/stk_augment.h', SIGNATURES_AUGMENT, {}, _NO_CHECK_AUGMENT),
   Header('has_consistency', 'include/stk_consistency.h', SIGNATURES_CONSISTENCY, _RESTYPE_CONSISTENCY, ()),
   Header('has_edm', 'include/stk_edm.h', SIGNATURES_EDM, _RESTYPE_EDM, ()),
   Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),

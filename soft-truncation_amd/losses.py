@@ -617,6 +617,24 @@ def _warn_dynamic_range(model, step):
   return rows
 
 
+def _augment_pipe(config):
+  """The AugmentPipe of config.training.augment = p > 0 (None when the key is absent or 0), after the checks get_step_fn
+  documents."""
+  from . import augment
+  p = augment.check_probability(mutils.config_option(config, 'training', 'augment', 0) or 0)
+  if p == 0:
+    return None
+  K = int(mutils.config_option(config, 'model', 'augment_dim', 0) or 0)
+  if K != augment.NUM_LABELS:
+    raise ValueError(f'config.training.augment = {p} needs config.model.augment_dim = {augment.NUM_LABELS} (the labels the '
+                     f'pipe produces), got {K}')
+  pipe = augment.AugmentPipe(p, augment.check_filter(mutils.config_option(config, 'training', 'augment_filter', None)),
+                             seed=int(getattr(config, 'seed', 0) or 0) + ddp.rank())      # offset by rank, as torch's streams are
+  size = int(config.data.image_size)
+  pipe.check_shape(size, size)
+  return pipe
+
+
 def get_step_fn(config, sde, train, optimize_fn=None):
   """One training step: ``step_fn(state, batch) -> losses`` on the CPU (losses.py:218-325).
 
@@ -635,15 +653,29 @@ def get_step_fn(config, sde, train, optimize_fn=None):
   nothing) is drawn BEFORE the loss's own draws and sends those samples to the null class: the unconditional branch
   classifier-free guidance needs.  The values of a device tensor are not read back (no host synchronisation per step):
   an index outside [0, C] takes the null row in the kernels.  ValueError: a conditional model without classes, an
-  unconditional one with classes, classes of another length than the batch."""
+  unconditional one with classes, classes of another length than the batch.
+
+  ``config.training.augment = p > 0`` (configs.edm_augment; any loss) trains under non-leaky augmentation (augment.py): the
+  whole batch goes through ONE launch of stk_aug_warp_f32 before the loss, with per-sample transforms drawn on the host from
+  a generator of the pipe's own seeded by ``config.seed`` (the device RNG stream is the unaugmented step's), and the nine
+  augmentation labels follow the images through the micro-batches and the halves of ``training.mixed`` as the classes do;
+  every network evaluation of a chunk -- both of the consistency loss -- sees that chunk's labels
+  (models.utils.augment_condition).  ``config.training.augment_filter``: other symmetric low-pass taps.  ValueError, here:
+  p outside [0, 1], ``config.model.augment_dim`` other than 9, images the kernel does not take (even sides in [8, 64]), an
+  unsymmetric filter.  Absent or 0: nothing of this exists in the step."""
   precision = mutils.config_training_precision(config)
+  pipe = _augment_pipe(config)
   loss_fn = _pick_loss_fn(config, sde, train)
   tr = config.training
   mixed = bool(tr.mixed)
   class_dropout = float(mutils.config_option(config, 'training', 'class_dropout', 0.1))
 
-  def evaluated(model, chunk, cls, **kw):
-    """loss_fn on one chunk, under its classes (None: an unconditional model) after label dropout."""
+  def evaluated(model, chunk, cls, aug=None, **kw):
+    """loss_fn on one chunk, under its classes (None: an unconditional model) after label dropout, and under its augmentation
+    labels (None: no augmentation)."""
+    if aug is not None:
+      with mutils.augment_in_force(model, aug):
+        return evaluated(model, chunk, cls, **kw)
     if cls is None:
       return loss_fn(model, chunk, **kw)
     if class_dropout > 0:
@@ -651,13 +683,14 @@ def get_step_fn(config, sde, train, optimize_fn=None):
     with mutils.classes_in_force(model, cls):
       return loss_fn(model, chunk, **kw)
 
-  def plain_losses(model, chunk, t_min, cls=None):
-    return evaluated(model, chunk, cls, importance_sampling=tr.importance_sampling, t_min=t_min)
+  def plain_losses(model, chunk, t_min, cls=None, aug=None):
+    return evaluated(model, chunk, cls, aug, importance_sampling=tr.importance_sampling, t_min=t_min)
 
-  def mixed_losses(model, chunk, t_min, cls=None):
+  def mixed_losses(model, chunk, t_min, cls=None, aug=None):
     half = chunk.shape[0] // 2
-    l_is = evaluated(model, chunk[:half], None if cls is None else cls[:half], importance_sampling=True, t_min=t_min)
-    l_ddpm = evaluated(model, chunk[half:], None if cls is None else cls[half:], importance_sampling=False, t_min=t_min)
+    first, second = (lambda v: None if v is None else v[:half]), (lambda v: None if v is None else v[half:])
+    l_is = evaluated(model, chunk[:half], first(cls), first(aug), importance_sampling=True, t_min=t_min)
+    l_ddpm = evaluated(model, chunk[half:], second(cls), second(aug), importance_sampling=False, t_min=t_min)
     weight = tr.ddpm_weight
     if tr.balanced:
       weight = weight * torch.mean(l_is / l_ddpm).detach().item()
@@ -688,6 +721,9 @@ def get_step_fn(config, sde, train, optimize_fn=None):
       # the reference has no evaluation branch either: its `return losses_` raises exactly this (losses.py:279-293)
       raise UnboundLocalError("local variable 'losses_' referenced before assignment")
     cls = step_classes(model, batch, classes)
+    aug = None
+    if pipe is not None:
+      batch, aug = pipe(batch)
     optimizer.zero_grad()
     n, parts = batch.shape[0], config.optim.num_micro_batch
     per = n // parts
@@ -700,12 +736,12 @@ def get_step_fn(config, sde, train, optimize_fn=None):
     ddp.begin_step(model)
     try:
       for k in range(parts):
-        of_chunk = () if cls is None else (cls[per * k: per * (k + 1)],)
+        of_chunk = {name: v[per * k: per * (k + 1)] for name, v in (('cls', cls), ('aug', aug)) if v is not None}
         if precision != 'fp32':
           with mutils.training_precision(model, precision):
-            losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, *of_chunk)
+            losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, **of_chunk)
         else:
-          losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, *of_chunk)
+          losses = micro_losses(model, batch[per * k: per * (k + 1)], t_min, **of_chunk)
         if k == parts - 1 and OVERLAP_EXCHANGE:
           # multi-GPU: buckets of the flat gradient buffer are all-reduced as the last backward finishes them (with
           # several network evaluations per loss -- training.mixed -- as the LAST of their backwards does)

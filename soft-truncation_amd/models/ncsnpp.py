@@ -43,6 +43,17 @@ class ClassTable(nn.Module):
     self.weight = nn.Parameter(torch.zeros(num_classes + 1, dim))
 
 
+class AugmentTable(nn.Module):
+  """The augmentation embedding of a network trained under non-leaky augmentation (augment.py): ``weight`` [D, K], a linear
+  map of the K augmentation labels into the time embedding without a bias, all zeros at first -- a fresh network then
+  computes what the plain one does, and a plain checkpoint loaded with ``strict=False`` is a warm start.  A holder of the
+  parameter only: the product is added inside the planned graph (engine.graph.AugmentEmbedding)."""
+
+  def __init__(self, augment_dim, dim):
+    super().__init__()
+    self.weight = nn.Parameter(torch.zeros(dim, augment_dim))
+
+
 @utils.register_model(name='ncsnpp')
 class NCSNpp(nn.Module):
   """NCSN++ model."""
@@ -72,6 +83,11 @@ class NCSNpp(nn.Module):
     self.num_classes = num_classes = int(utils.config_option(config, 'model', 'num_classes', 0) or 0)
     if num_classes < 0 or (num_classes > 0 and not conditional):
       raise ValueError(f'config.model.num_classes = {num_classes} needs config.model.conditional (the class row is added to '
+                       f'the time embedding) and must not be negative')
+    # augmentation labels (absent from the reference): 0 = off, the network of the reference, key for key
+    self.augment_dim = augment_dim = int(utils.config_option(config, 'model', 'augment_dim', 0) or 0)
+    if augment_dim < 0 or (augment_dim > 0 and not conditional):
+      raise ValueError(f'config.model.augment_dim = {augment_dim} needs config.model.conditional (the labels are mapped into '
                        f'the time embedding) and must not be negative')
     # scale-shift GroupNorm conditioning (absent from the reference): False = off, the network of the reference, key for key
     self.scale_shift_norm = ssn = bool(utils.config_option(config, 'model', 'scale_shift_norm', False))
@@ -246,7 +262,11 @@ class NCSNpp(nn.Module):
     self.all_modules = nn.ModuleList(modules)
     if num_classes > 0:         # outside all_modules: the all_modules.<i>.* keys keep their indices
       self.class_emb = ClassTable(num_classes, embed_dim_2 * 4)
+    if augment_dim > 0:         # outside all_modules too, after the class rows
+      self.augment_emb = AugmentTable(augment_dim, embed_dim_2 * 4)
     self._class_ctx = None      # (classes, guidance, [classes; null]) in force: models.utils.class_condition
+    self._aug_ctx = None        # the [B, K] augmentation labels in force: models.utils.augment_condition
+    self._null_aug = {}
     self._cfg_rescale = 0.0     # ... and its guidance rescale, saved and restored with it
     self._rescale_ws = {}
     self._null_rows = {}
@@ -279,6 +299,8 @@ class NCSNpp(nn.Module):
       # beside the stacked projections at the bottom of the flat buffers: its gradient is among the last the backward
       # writes, as theirs are, so the buckets above become final as early as in the unconditional network
       groups.append([self.class_emb.weight])
+    if self.augment_dim:
+      groups.append([self.augment_emb.weight])      # beside the class rows, for the same reason
     for mod in self.modules():
       if isinstance(mod, layerspp.AttnBlockpp):
         ws, bs = mod.qkv_params()
@@ -295,6 +317,20 @@ class NCSNpp(nn.Module):
       t = self._null_rows[(B, device)] = torch.full((B,), float(self.num_classes), dtype=torch.float32, device=device)
     return t
 
+  def augment_labels(self, B, device):
+    """The [B, K] augmentation labels the engine takes: those in force (models.utils.augment_condition), zeros -- a clean
+    image, as in sampling -- with none; None for a network without the embedding."""
+    if not self.augment_dim:
+      return None
+    if self._aug_ctx is not None:
+      if self._aug_ctx.shape[0] != B:
+        raise ValueError(f'augment_condition holds labels of {self._aug_ctx.shape[0]} samples, the batch evaluated has {B}')
+      return self._aug_ctx
+    t = self._null_aug.get((B, device))
+    if t is None:
+      t = self._null_aug[(B, device)] = torch.zeros(B, self.augment_dim, dtype=torch.float32, device=device)
+    return t
+
   def forward(self, x, time_cond):
     """x [B,C,H,W] fp32, time_cond [B] fp32 -> [B,C,H,W] (models/ncsnpp.py:258-432).  A class-conditional network
     (config.model.num_classes > 0) takes the classes and the guidance weight in force (models.utils.class_condition): no
@@ -302,15 +338,16 @@ class NCSNpp(nn.Module):
     out = c + w (c - u) of its halves -- by stk_cfg_combine_f32, or by torch operators under grad mode, where autograd
     has to see it.  A guidance rescale phi != 0 in force: out = (phi std(c) / std(g) + 1 - phi) g per sample instead, by
     stk_cfg_rescale_f32 (include/stk_guided.h), or by torch operators under grad mode."""
-    if not self.num_classes:
-      return self._forward(x, time_cond, None)
     B = x.shape[0]
+    aug = self.augment_labels(B, x.device)
+    if not self.num_classes:
+      return self._forward(x, time_cond, None, aug)
     cls, w, both = self._class_ctx if self._class_ctx is not None else (self.null_classes(B, x.device), 0.0, None)
     if cls.shape[0] != B:
       raise ValueError(f'class_condition holds {cls.shape[0]} classes, the batch evaluated has {B} samples')
     if w == 0.0:
-      return self._forward(x, time_cond, cls)
-    out = self._forward(torch.cat([x, x]), torch.cat([time_cond, time_cond]), both)
+      return self._forward(x, time_cond, cls, aug)
+    out = self._forward(torch.cat([x, x]), torch.cat([time_cond, time_cond]), both, None if aug is None else torch.cat([aug, aug]))
     c, u = out[:B], out[B:]
     phi = self._cfg_rescale
     if torch.is_grad_enabled():
@@ -345,7 +382,7 @@ class NCSNpp(nn.Module):
       ws = self._rescale_ws[(B, n, device)] = torch.empty(int(lib.guided_ws_bytes(B, n)), dtype=torch.uint8, device=device)
     return ws
 
-  def _forward(self, x, time_cond, cls):
+  def _forward(self, x, time_cond, cls, aug=None):
     sigma = None
     if self.embedding_type == 'fourier':
       used_sigmas = time_cond
@@ -359,7 +396,7 @@ class NCSNpp(nn.Module):
         used_sigmas = self.sigmas[time_cond.long()].to(torch.float32)
     if self.config.model.scale_by_sigma:
       sigma = used_sigmas
-    return self.engine().apply(x, emb_in.to(torch.float32), sigma, cls)
+    return self.engine().apply(x, emb_in.to(torch.float32), sigma, cls, aug)
 
   # ------------------------------------------------------------------------------------------------
   # lowering: the walk of models/ncsnpp.py:258-432, emitted into the engine graph
@@ -374,6 +411,7 @@ class NCSNpp(nn.Module):
     emb_in = g.input('emb', (B,))
     sigma = g.input('sigma', (B,)) if cfg.model.scale_by_sigma else None
     cls = g.input('cls', (B,)) if self.num_classes else None
+    aug = g.input('aug', (B, self.augment_dim)) if self.augment_dim else None
 
     if self.embedding_type == 'fourier':
       temb = g.add(G.FourierEmbedding(g, emb_in, g.param(modules[m_idx].W)))
@@ -389,6 +427,8 @@ class NCSNpp(nn.Module):
       m_idx += 1
       if cls is not None:
         temb = g.add(G.ClassEmbedding(g, temb, cls, g.param(self.class_emb.weight)))
+      if aug is not None:
+        temb = g.add(G.AugmentEmbedding(g, temb, aug, g.param(self.augment_emb.weight)))
       dense = self._dense_blocks()
       if dense:
         # all Dense_0(act(temb)) of the residual blocks as ONE GEMM over the stacked weights

@@ -245,6 +245,48 @@ def class_condition(model, classes, guidance=0.0, rescale=0.0):
     inner._class_ctx, inner._cfg_rescale = saved, saved_rescale
 
 
+# ---- augmentation labels (include/stk_augment.h, augment.py) ---------------------------------------------------------------
+def augment_dim(model):
+  """K of a network with an augmentation embedding (config.model.augment_dim), 0 for any other; sees through DataParallel."""
+  return int(getattr(getattr(model, 'module', model), 'augment_dim', 0) or 0)
+
+
+@contextlib.contextmanager
+def augment_in_force(model, labels):
+  """The unchecked core of :func:`augment_condition`, for callers that have checked already (get_step_fn): `labels` is a
+  [B, K] float32 tensor on the model's device."""
+  inner = getattr(model, 'module', model)
+  saved, inner._aug_ctx = inner._aug_ctx, labels
+  try:
+    yield
+  finally:
+    inner._aug_ctx = saved
+
+
+@contextlib.contextmanager
+def augment_condition(model, labels):
+  """Context manager: every network evaluation of `model` inside it is told the augmentation `labels` -- a [B, K] float
+  tensor, K = config.model.augment_dim -- of the images it sees (losses.get_step_fn under config.training.augment).  With no
+  context in force the labels are zeros: a clean image, which is what sampling, the likelihood and DPS evaluate.  Under
+  classifier-free guidance (class_condition with a weight) the labels are repeated for the [x; x] batch.  ValueError: a
+  model without the embedding, labels of another shape; an evaluation of a batch of another size inside it raises ValueError
+  too.  Contexts nest and restore; `model` may be the DataParallel wrapper."""
+  inner = getattr(model, 'module', model)
+  K = augment_dim(model)
+  if K <= 0:
+    raise ValueError(f'{type(inner).__name__} has no augmentation embedding (config.model.augment_dim is absent or 0)')
+  if not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[1] != K or labels.shape[0] == 0 or \
+      not labels.dtype.is_floating_point:
+    raise ValueError(f'augmentation labels must be a [B, {K}] float tensor (config.model.augment_dim = {K}), got '
+                     f'{tuple(labels.shape) if torch.is_tensor(labels) else type(labels).__name__}')
+  device = next(inner.parameters()).device
+  saved, inner._aug_ctx = inner._aug_ctx, labels.detach().to(device=device, dtype=torch.float32).contiguous()
+  try:
+    yield
+  finally:
+    inner._aug_ctx = saved
+
+
 # ---- what the samplers share (sampling.py, controllable_generation.py, dpm_solver.py, adaptive_sde.py) --------------------
 def require(has, header, entries, user):
   """The bound library, which must implement the optional header `header` (``has``: its StkLib attribute, engine/lib.py
