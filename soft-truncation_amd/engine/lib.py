@@ -241,6 +241,14 @@ SIGNATURES_AUGMENT = {
   'stk_aug_embed_bwd_f32': [P, P, P, F, P, I, I, I, S],
 }
 _NO_CHECK_AUGMENT = {'stk_aug_ok'}                                               # its query
+# include/stk_parallel.h: the scan, the stride decision and the slide of the parallel-in-time (Picard) sampler.
+SIGNATURES_PARALLEL = {
+  'stk_picard_ws_bytes': [I, I, L],
+  'stk_picard_scan_f32': [P, P, P, P, I, I, I, P, L, I, L, S],
+  'stk_picard_stride': [P, L, P, I, I, I, I, L, P, P, S],
+  'stk_picard_slide_f32': [P, P, I, I, I, L, S],
+}
+_RESTYPE_PARALLEL = {'stk_picard_ws_bytes': c_long}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -265,6 +273,7 @@ OPTIONAL_HEADERS = (
   Header('has_cond', 'include/stk_cond.h', SIGNATURES_COND, {}, ()),
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
   Header('has_augment', 'include/stk_augment.h', SIGNATURES_AUGMENT, {}, _NO_CHECK_AUGMENT),
+  Header('has_parallel', 'include/stk_parallel.h', SIGNATURES_PARALLEL, _RESTYPE_PARALLEL, ()),
   Header('has_consistency', 'include/stk_consistency.h', SIGNATURES_CONSISTENCY, _RESTYPE_CONSISTENCY, ()),
   Header('has_edm', 'include/stk_edm.h', SIGNATURES_EDM, _RESTYPE_EDM, ()),
   Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),

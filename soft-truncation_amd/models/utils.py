@@ -287,6 +287,39 @@ def augment_condition(model, labels):
     inner._aug_ctx = saved
 
 
+@contextlib.contextmanager
+def tiled_conditions(model, reps):
+  """Context manager: the class context in force (models.utils.class_condition: the classes, and [classes; null] under
+  guidance) and the augmentation labels in force (augment_condition) are repeated `reps` times, slot-major -- the conditions of
+  a batch [reps, B] that stacks `reps` copies of the batch they were given for (the window of parallel_sampling.py).  With
+  no context in force it does nothing.  Contexts nest and restore; `model` may be the DataParallel wrapper."""
+  try:
+    ok = not isinstance(reps, bool) and int(reps) == reps and reps >= 1
+  except (TypeError, ValueError, OverflowError):
+    ok = False
+  if not ok:
+    raise ValueError(f'reps must be a positive integer, got {reps!r}')
+  reps = int(reps)
+  inner = getattr(model, 'module', model)
+  ctx, aug = getattr(inner, '_class_ctx', None), getattr(inner, '_aug_ctx', None)
+  if reps == 1 or (ctx is None and aug is None):
+    yield
+    return
+  if ctx is not None:
+    cls, w, both = ctx
+    tiled = cls.repeat(reps)
+    inner._class_ctx = (tiled, w, None if both is None else torch.cat([tiled, both[cls.shape[0]:].repeat(reps)]))
+  if aug is not None:
+    inner._aug_ctx = aug.repeat(reps, 1)
+  try:
+    yield
+  finally:
+    if ctx is not None:
+      inner._class_ctx = ctx
+    if aug is not None:
+      inner._aug_ctx = aug
+
+
 # ---- what the samplers share (sampling.py, controllable_generation.py, dpm_solver.py, adaptive_sde.py) --------------------
 def require(has, header, entries, user):
   """The bound library, which must implement the optional header `header` (``has``: its StkLib attribute, engine/lib.py

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import adaptive_sde, consistency, dpm_solver, edm, sde_lib
+from . import adaptive_sde, consistency, dpm_solver, edm, parallel_sampling, sde_lib
 from .engine import rk45
 from .models import utils as mutils
 from .models.utils import from_flattened_numpy, get_score_fn, to_flattened_numpy
@@ -319,7 +319,9 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   (adaptive_sde.py; ``config.sampling.adaptive_rtol / adaptive_atol / adaptive_h_init / adaptive_safety / adaptive_exponent``)
   or 'edm' (edm.py, on sde_lib.EDM alone; ``config.sampling.edm_steps / edm_rho / edm_s_churn / edm_s_tmin / edm_s_tmax /
   edm_s_noise``; it runs down to noise level 0, so `eps` and ``noise_removal`` do not apply) or 'consistency'
-  (consistency.py, on sde_lib.EDM alone; ``config.sampling.ct_levels / ct_clip``; one network evaluation per level)."""
+  (consistency.py, on sde_lib.EDM alone; ``config.sampling.ct_levels / ct_clip``; one network evaluation per level) or
+  'parallel' (parallel_sampling.py: Picard iteration over a sliding window of grid points; ``config.sampling.parallel_steps /
+  parallel_window / parallel_tol / parallel_eta / parallel_skip``)."""
   s = config.sampling
   kind = s.method.lower()
   precision = mutils.sampling_precision(config)
@@ -356,6 +358,11 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
     levels, clip = consistency.sampling_options(config)
     return consistency.get_consistency_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler,
                                                levels=levels, clip=clip, device=config.device, precision=precision)
+  if kind == 'parallel':
+    steps, window, tol, eta, skip = parallel_sampling.sampling_options(config)
+    return parallel_sampling.get_parallel_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler,
+                                                  steps=steps, window=window, tol=tol, eta=eta, skip=skip,
+                                                  denoise=s.noise_removal, eps=eps, device=config.device, precision=precision)
   raise ValueError(f"Sampler name {s.method} unknown.")
 
 
