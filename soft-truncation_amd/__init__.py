@@ -17,10 +17,10 @@ from . import op
 from .models import utils as _mutils  # noqa: F401
 from .models import ema, layers, layerspp, ncsnpp, up_or_down_sampling  # noqa: F401
 from . import models
-from . import adaptive_sde, augment, consistency, controllable_generation, dpm_solver, edm, likelihood, losses, parallel_sampling, posterior_sampling, sampling, sampling_lib, utils
+from . import adaptive_sde, augment, consistency, controllable_generation, dpm_solver, edm, flow, likelihood, losses, parallel_sampling, posterior_sampling, sampling, sampling_lib, utils
 
 __all__ = ['configs', 'datasets', 'sde_lib', 'op', 'models', 'likelihood', 'losses', 'sampling', 'sampling_lib', 'utils',
-           'controllable_generation', 'dpm_solver', 'adaptive_sde', 'posterior_sampling', 'edm', 'consistency', 'augment', 'parallel_sampling', 'install']
+           'controllable_generation', 'dpm_solver', 'adaptive_sde', 'posterior_sampling', 'edm', 'consistency', 'augment', 'parallel_sampling', 'flow', 'install']
 
 # name the reference's modules import under -> our module
 _REFERENCE_NAMES = {
@@ -36,6 +36,7 @@ _REFERENCE_NAMES = {
   'consistency': consistency,   # consistency training's definitions and sampler; neither the reference nor score_sde has one
   'augment': augment,           # the non-leaky augmentation pipe; neither the reference nor score_sde has such a module
   'parallel_sampling': parallel_sampling,   # the parallel-in-time sampler; neither the reference nor score_sde has such a module
+  'flow': flow,                 # the rectified-flow sampler; neither the reference nor score_sde has such a module
   'utils': utils,
   'op': op,
   'models': models,

@@ -295,6 +295,26 @@ def edm(config, sigma_min=0.002, sigma_max=80., sigma_data=0.5, p_mean=-1.2, p_s
   return config
 
 
+def flow(config, steps=50, order=1, shift=1.0, eta=0.0, p_mean=0.0, p_std=1.0):
+  """The rectified-flow variant of any config above (Liu et al. 2022): the same network under ``training.sde =
+  'rectified_flow'`` as the velocity of the straight-line interpolant, the logit-normal training times, and the `steps`-step
+  flow sampler (flow.py).  ``scale_by_sigma = False`` is what the family needs (models.utils.check_flow_config); the switches
+  of the Soft-Truncation objective it refuses are set off; ``data.centered`` stays as it is."""
+  config = copy.deepcopy(config)
+  t = config.training
+  t.sde = 'rectified_flow'
+  t.continuous = True
+  t.flow_time = 'logit_normal'
+  t.flow_p_mean, t.flow_p_std = p_mean, p_std
+  t.mixed = t.importance_sampling = t.likelihood_weighting = t.reconstruction_loss = False
+  config.model.scale_by_sigma = False
+  s = config.sampling
+  s.method = 'flow'
+  s.flow_steps, s.flow_order, s.flow_shift, s.flow_eta = steps, order, shift, eta
+  s.flow_t_end, s.flow_rtol, s.flow_atol = 1e-3, 1e-5, 1e-5
+  return config
+
+
 def edm_augment(config, p=0.12, **edm_options):
   """`edm(config)` trained under non-leaky augmentation (Karras et al. 2022, appendix F.2; augment.py): every transform fires
   with probability p = 0.12 (the paper's CIFAR-10 setting) and the network takes the nine augmentation labels."""

@@ -10,7 +10,7 @@
 //
 // No fused multiply-add in this file (header, "Arithmetic"): the pragma below holds for every function that follows.
 // stream.h, included before it, holds loads, stores and host code only; sqloss.h (the loss, finish and gradient kernels shared
-// with consistency.hip, on the scaffold of rowsum.h) holds arithmetic and follows the pragma.
+// with consistency.hip and flow.hip, on the scaffold of rowsum.h) holds arithmetic and follows the pragma.
 #include "stream.h"
 #include "stk_edm.h"
 

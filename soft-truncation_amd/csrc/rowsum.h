@@ -1,5 +1,5 @@
 // rowsum.h -- the whole scaffold of a per-sample streaming kernel file (adaptive.hip, posterior.hip, guided.hip, edm.hip,
-// consistency.hip, and sqloss.h between the last two): the size checks of their entries, the row grid, the layout of their
+// consistency.hip, flow.hip, and sqloss.h between the last three): the size checks of their entries, the row grid, the layout of their
 // [B, parts] workspaces of float64 partial sums, the device-side walk over that grid and the fixed-order float64 sums.
 //
 // The grid is two-dimensional because everything in those files is per sample: blockIdx.y walks the samples (striding when

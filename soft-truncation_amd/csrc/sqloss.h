@@ -1,4 +1,4 @@
-// sqloss.h -- the squared-residual loss that edm.hip and consistency.hip share: one loss kernel, one finishing kernel and
+// sqloss.h -- the squared-residual loss that edm.hip, consistency.hip and flow.hip share: one loss kernel, one finishing kernel and
 // one gradient kernel on the scaffold of rowsum.h, and the two launch sequences of their entries.  The files that include
 // it give the expressions: how r is formed, what the row's sum becomes, where the gradient's factor comes from.
 //

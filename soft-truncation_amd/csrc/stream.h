@@ -1,5 +1,5 @@
 // stream.h -- what the HBM-bound streaming kernels share (elementwise.hip, impute.hip, solver.hip, superres.hip, cond.hip and,
-// through rowsum.h, the per-sample files adaptive.hip, posterior.hip, guided.hip, edm.hip, consistency.hip).
+// through rowsum.h, the per-sample files adaptive.hip, posterior.hip, guided.hip, edm.hip, consistency.hip, flow.hip).
 //
 // The layout they all follow: lanes walk consecutive addresses, 16 B per lane (one float4) whenever the length -- or the
 // plane or row a thread stays inside -- is a multiple of 4 and every pointer given is 16-byte aligned, a scalar path

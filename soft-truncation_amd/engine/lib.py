@@ -249,6 +249,13 @@ SIGNATURES_PARALLEL = {
   'stk_picard_slide_f32': [P, P, I, I, I, L, S],
 }
 _RESTYPE_PARALLEL = {'stk_picard_ws_bytes': c_long}
+# include/stk_flow.h: the velocity loss pair and the step launch of rectified flow.
+SIGNATURES_FLOW = {
+  'stk_flow_ws_bytes': [I, L],
+  'stk_flow_loss_f32': [P, P, P, P, L, P, P, I, L, I, S],
+  'stk_flow_loss_grad_f32': [P, P, P, I, L, I, S],
+  'stk_flow_step_f32': [P, P, P, P, F, F, F, P, L, S],
+}
 
 # One row per optional header, bound in this order by StkLib: all of a header's entries when the library exports them, none
 # otherwise (the plain-C checker has none; the samplers and planners that need one refuse a library without it).
@@ -274,6 +281,7 @@ OPTIONAL_HEADERS = (
   Header('has_adagn', 'include/stk_adagn.h', SIGNATURES_ADAGN, {'stk_gn_mod_ws_bytes': c_long}, _NO_CHECK_ADAGN),
   Header('has_augment', 'include/stk_augment.h', SIGNATURES_AUGMENT, {}, _NO_CHECK_AUGMENT),
   Header('has_parallel', 'include/stk_parallel.h', SIGNATURES_PARALLEL, _RESTYPE_PARALLEL, ()),
+  Header('has_flow', 'include/stk_flow.h', SIGNATURES_FLOW, {'stk_flow_ws_bytes': c_long}, ()),
   Header('has_consistency', 'include/stk_consistency.h', SIGNATURES_CONSISTENCY, _RESTYPE_CONSISTENCY, ()),
   Header('has_edm', 'include/stk_edm.h', SIGNATURES_EDM, _RESTYPE_EDM, ()),
   Header('has_guided', 'include/stk_guided.h', SIGNATURES_GUIDED, _RESTYPE_GUIDED, ()),

@@ -27,7 +27,7 @@ from .engine import ddp
 from .engine.flat import flat_of
 from .engine.optim import FusedAdam
 from .models import utils as mutils
-from .sde_lib import EDM, VESDE, VPSDE, reciprocal_VESDE
+from .sde_lib import EDM, VESDE, VPSDE, RectifiedFlow, reciprocal_VESDE
 
 
 def _wide(v):
@@ -400,6 +400,98 @@ def get_edm_loss_fn(config, sde, train):
   return loss_fn
 
 
+class _FlowLoss(_KeptResidual):
+  """losses[b] = reduce(r^2), r = F - (n - y): the tail of the rectified-flow loss on the raw network output F as
+  stk_flow_loss_f32 (include/stk_flow.h), whose residual r is kept; the backward is stk_flow_loss_grad_f32 on that r (24 B per
+  element for the pair)."""
+  NAME, WS_QUERY = 'flow', 'flow_ws_bytes'
+
+  @staticmethod
+  def forward(ctx, F, y, n, lib, reduce_mean):
+    F, y, n = F.contiguous(), y.contiguous(), n.contiguous()
+
+    def launch(ws, r, losses, B, inner, stream):
+      lib.flow_loss_f32(F.data_ptr(), y.data_ptr(), n.data_ptr(), ws.data_ptr(), ws.numel(), mutils.optional_ptr(r),
+                        losses.data_ptr(), B, inner, int(reduce_mean), stream)
+      return int(reduce_mean)
+
+    return _FlowLoss.keep(ctx, lib, F, launch)
+
+  @staticmethod
+  def backward(ctx, dloss):
+    def launch_grad(lib, r, reduce_mean, dloss, B, inner, stream):
+      lib.flow_loss_grad_f32(r.data_ptr(), dloss.data_ptr(), r.data_ptr(), B, inner, reduce_mean, stream)
+
+    return (_FlowLoss.spend(ctx, dloss, launch_grad),) + (None,) * 4
+
+
+FLOW_TIMES = ('logit_normal', 'uniform')
+
+
+def get_flow_loss_fn(config, sde, train):
+  """The rectified-flow training loss (Liu et al. 2022; the time law of Esser et al. 2024): ``loss_fn(model, batch,
+  importance_sampling=None, t_min=None) -> [B]``, both keywords accepted and unused.  Per evaluation, in this order: one [B]
+  fp32 draw on the batch's device for the time -- ``training.flow_time = 'logit_normal'`` (the default):
+  t = sigmoid(P_mean + P_std torch.randn(B)) with ``training.flow_p_mean`` = 0 and ``training.flow_p_std`` = 1 where absent;
+  'uniform': t = 1 - torch.rand(B), which lies in (0, 1] -- then ``torch.randn_like(batch)`` for n.  With a = 1 - t,
+
+    x_t = a y + t n;  F = v(x_t, t);  u = n - y;  r = F - u;  loss[b] = sum r^2   (the mean over C H W under
+    ``training.reduce_mean``)
+
+  every element in fp32 in that order, the squares summed in float64; the loss weight is 1.  On an engine model with a device
+  fp32 batch, a library with include/stk_flow.h and STK_FUSED_LOSS != 0 this is stk_perturb_f32, the network and
+  stk_flow_loss_f32 / stk_flow_loss_grad_f32; otherwise the same expressions by torch operators.  ValueError naming the key:
+  a config the family refuses (models.utils.check_flow_config), ``flow_p_std`` <= 0, an unknown ``flow_time``."""
+  mutils.check_flow_config(config, training=True)
+  if not isinstance(sde, RectifiedFlow):
+    raise ValueError(f'get_flow_loss_fn needs sde_lib.RectifiedFlow, got {type(sde).__name__}')
+  time_law = mutils.config_option(config, 'training', 'flow_time', 'logit_normal')
+  if time_law not in FLOW_TIMES:
+    raise ValueError(f'config.training.flow_time must be one of {FLOW_TIMES}, got {time_law!r}')
+  p_mean = float(mutils.config_option(config, 'training', 'flow_p_mean', 0.))
+  p_std = float(mutils.config_option(config, 'training', 'flow_p_std', 1.))
+  if not p_std > 0:
+    raise ValueError(f'config.training.flow_p_std must be positive, got {p_std!r}')
+  reduce_mean = bool(config.training.reduce_mean)
+
+  def fused_losses(lib, v_fn, batch, t, a, n):
+    from .engine import lib as stk_lib
+    B = batch.shape[0]
+    y = batch.contiguous()
+    t, a = t.contiguous(), a.contiguous()
+    x_t = torch.empty_like(y)
+    with stk_lib.device_guard(y.device):
+      lib.perturb_f32(y.data_ptr(), n.data_ptr(), a.data_ptr(), t.data_ptr(), x_t.data_ptr(), B, y[0].numel(),
+                      stk_lib.stream_ptr(y.device))
+    return _FlowLoss.apply(v_fn(x_t, t), y, n, lib, reduce_mean)
+
+  def torch_losses(v_fn, batch, t, a, n):
+    x_t = _wide(a) * batch + _wide(t) * n
+    F = v_fn(x_t, t)
+    u = n - batch
+    r = F - u
+    total = (r * r).double().reshape(r.shape[0], -1).sum(dim=-1)
+    if reduce_mean:
+      total = total / float(np.prod(batch.shape[1:]))
+    return total.to(torch.float32)
+
+  def loss_fn(model, batch, importance_sampling=None, t_min=None):
+    B = batch.shape[0]
+    if time_law == 'uniform':
+      t = 1. - torch.rand(B, device=batch.device)
+    else:
+      t = torch.sigmoid(p_mean + p_std * torch.randn(B, device=batch.device)).to(torch.float32)
+    a = 1. - t
+    n = torch.randn_like(batch)
+    v_fn = mutils.get_flow_model_fn(config, model, train=train)
+    lib = _engine_lib(model, batch) if FUSED_LOSS else None
+    if lib is not None and lib.has_flow:
+      return fused_losses(lib, v_fn, batch, t, a, n.contiguous())
+    return torch_losses(v_fn, batch, t, a, n)
+
+  return loss_fn
+
+
 class _CtLoss(_KeptResidual):
   """losses[b] = lambda_b (sqrt(S + c^2) - c) (/ inner), S = sum r^2, r = f(y + sigma_hi n; sigma_hi) - f(y + sigma_lo n;
   sigma_lo): the tail of the consistency loss on the two raw network outputs as stk_ct_loss_f32 (include/stk_consistency.h),
@@ -557,11 +649,14 @@ def get_consistency_loss_fn(config, sde, train):
   return ConsistencyLoss(config, sde, train)
 
 
-def _pick_loss_fn(config, sde, train):
+def get_loss_fn(config, sde, train):
+  """The loss of `sde` under `config`: what get_step_fn evaluates on every chunk."""
   if isinstance(sde, EDM):
     if mutils.config_option(config, 'training', 'consistency', False):
       return get_consistency_loss_fn(config, sde, train)
     return get_edm_loss_fn(config, sde, train)
+  if isinstance(sde, RectifiedFlow):
+    return get_flow_loss_fn(config, sde, train)
   if config.training.continuous:
     return get_sde_loss_fn(config, sde, train)
   assert not config.training.likelihood_weighting, \
@@ -571,6 +666,9 @@ def _pick_loss_fn(config, sde, train):
   if isinstance(sde, VPSDE):
     return get_ddpm_loss_fn(config, sde, train)
   raise ValueError(f"Discrete training for {sde.__class__.__name__} is not recommended.")
+
+
+_pick_loss_fn = get_loss_fn      # its name before it was public
 
 
 # STK_DDP_OVERLAP=0: exchange the gradients after the backward (one bucketed all-reduce) instead of during it
@@ -665,7 +763,7 @@ def get_step_fn(config, sde, train, optimize_fn=None):
   unsymmetric filter.  Absent or 0: nothing of this exists in the step."""
   precision = mutils.config_training_precision(config)
   pipe = _augment_pipe(config)
-  loss_fn = _pick_loss_fn(config, sde, train)
+  loss_fn = get_loss_fn(config, sde, train)
   tr = config.training
   mixed = bool(tr.mixed)
   class_dropout = float(mutils.config_option(config, 'training', 'class_dropout', 0.1))

@@ -525,13 +525,60 @@ def _edm_score_fn(config, sde, model, train):
   return score_fn
 
 
+# ---- rectified flow (sde_lib.RectifiedFlow, include/stk_flow.h) ------------------------------------------------------------------
+def check_flow_config(config, training=False):
+  """What sde_lib.RectifiedFlow asks of a config, checked when a velocity or score function, a loss, a step function or a
+  sampler is built on it; ValueError naming the key.  ``model.scale_by_sigma`` must be false (the velocity is the network's
+  output as it is) and ``training.continuous`` true; training: ``training.mixed / importance_sampling / likelihood_weighting
+  / reconstruction_loss`` must all be off (they belong to the Soft-Truncation objective).  Centred and uncentred data are both
+  allowed: the network recentres x_t as it does for VP."""
+  if config_option(config, 'model', 'scale_by_sigma', False):
+    raise ValueError('rectified flow needs config.model.scale_by_sigma = False: the velocity is the output of the network')
+  if not config_option(config, 'training', 'continuous', True):
+    raise ValueError('rectified flow needs config.training.continuous = True: the time of the interpolant is continuous')
+  if training:
+    for key in EDM_TRAINING_REFUSED:
+      if config_option(config, 'training', key, False):
+        raise ValueError(f'the flow loss does not take config.training.{key}: it belongs to the Soft-Truncation objective')
+
+
+def get_flow_model_fn(config, model, train=False):
+  """``v(x, t)``: the raw network as the velocity of the interpolant at the [B] times `t` -- conditioned on 999 t for
+  ``embedding_type = 'positional'`` (the range of the VP labels), on t itself for 'fourier', whose forward takes the log.
+  Classifier-free guidance, guidance rescale and augmentation labels act inside the model.  ValueError for a config the family
+  refuses (:func:`check_flow_config`)."""
+  check_flow_config(config)
+  model_fn = get_model_fn(model, train=train)
+  if config.model.embedding_type.lower() == 'fourier':
+    return model_fn
+  return lambda x, t: model_fn(x, t * 999)
+
+
+get_velocity_fn = get_flow_model_fn
+
+
+def _flow_score_fn(config, model, train):
+  """score(x, t) = -(x + (1 - t) v(x, t)) / t of the Gaussian bridge x_t = (1 - t) x_0 + t z, by torch operators (autograd
+  sees it).  Valid for 0 < t <= 1."""
+  v = get_flow_model_fn(config, model, train)
+
+  def score_fn(x, t):
+    tt = t.to(x.dtype)[:, None, None, None]
+    return -(x + (1. - tt) * v(x, t)) / tt
+
+  return score_fn
+
+
 def get_raw_fn(config, sde, model, train=False, continuous=False):
   """The pieces of :func:`get_score_fn` for callers that fuse what follows the network (losses.py's fused loss path):
   ``raw_fn(x, t) -> network output`` with exactly the conditioning labels `get_score_fn` computes, and ``neg_over_std``:
   whether the score is ``-output / std(t)`` (VP family with ``training.ddpm_score``) or the output itself.  Returns
   ``(None, None)`` for the combinations it does not cover (discrete ladders).  sde_lib.EDM: ``raw_fn(x_in, sigma) = F``, the
-  network on an input the caller has scaled by c_in already (the score is :func:`get_score_fn`'s, not the output)."""
+  network on an input the caller has scaled by c_in already (the score is :func:`get_score_fn`'s, not the output);
+  sde_lib.RectifiedFlow: ``raw_fn(x, t) = v``, the velocity (likewise)."""
   model_fn = get_model_fn(model, train=train)
+  if isinstance(sde, sde_lib.RectifiedFlow):
+    return get_flow_model_fn(config, model, train), False
   if isinstance(sde, sde_lib.EDM):
     check_edm_config(config)
     F = get_edm_model_fn(config, model, train)
@@ -551,9 +598,12 @@ def get_score_fn(config, sde, model, train=False, continuous=False):
 
   VP / subVP: labels = 999 t (continuous), score = -net/std when ``training.ddpm_score``;
   VE / RVE:   labels = sigma(t) (continuous), the network output is already the score;
-  EDM:        t = sigma, score = (D(x; sigma) - x) / sigma^2 of the preconditioned denoiser D."""
+  EDM:        t = sigma, score = (D(x; sigma) - x) / sigma^2 of the preconditioned denoiser D;
+  RectifiedFlow: score = -(x + (1 - t) v(x, t)) / t of the velocity v, for 0 < t <= 1."""
   if isinstance(sde, sde_lib.EDM):
     return _edm_score_fn(config, sde, model, train)
+  if isinstance(sde, sde_lib.RectifiedFlow):
+    return _flow_score_fn(config, model, train)
   model_fn = get_model_fn(model, train=train)
   if isinstance(sde, (sde_lib.VPSDE, sde_lib.subVPSDE)):
     return _vp_score_fn(config, sde, model_fn, continuous)

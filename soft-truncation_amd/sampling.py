@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import adaptive_sde, consistency, dpm_solver, edm, parallel_sampling, sde_lib
+from . import adaptive_sde, consistency, dpm_solver, edm, flow, parallel_sampling, sde_lib
 from .engine import rk45
 from .models import utils as mutils
 from .models.utils import from_flattened_numpy, get_score_fn, to_flattened_numpy
@@ -321,10 +321,21 @@ def get_sampling_fn(config, sde, shape, inverse_scaler, eps):
   edm_s_noise``; it runs down to noise level 0, so `eps` and ``noise_removal`` do not apply) or 'consistency'
   (consistency.py, on sde_lib.EDM alone; ``config.sampling.ct_levels / ct_clip``; one network evaluation per level) or
   'parallel' (parallel_sampling.py: Picard iteration over a sliding window of grid points; ``config.sampling.parallel_steps /
-  parallel_window / parallel_tol / parallel_eta / parallel_skip``)."""
+  parallel_window / parallel_tol / parallel_eta / parallel_skip``) or 'flow' (flow.py, on sde_lib.RectifiedFlow alone;
+  ``config.sampling.flow_steps / flow_order / flow_shift / flow_eta / flow_t_end / flow_rtol / flow_atol``; it runs down to
+  t = 0, so `eps` and ``noise_removal`` do not apply).  On sde_lib.RectifiedFlow every other method raises ValueError: those
+  samplers need ``sde()`` at T, which is singular there, or a data prediction through 1 / alpha."""
   s = config.sampling
   kind = s.method.lower()
   precision = mutils.sampling_precision(config)
+  if kind == 'flow':
+    steps, order, shift, eta, t_end, rtol, atol = flow.sampling_options(config)
+    return flow.get_flow_sampler(config=config, sde=sde, shape=shape, inverse_scaler=inverse_scaler, steps=steps, order=order,
+                                 shift=shift, eta=eta, t_end=t_end, rtol=rtol, atol=atol, device=config.device,
+                                 precision=precision)
+  if isinstance(sde, sde_lib.RectifiedFlow):
+    raise ValueError(f"config.sampling.method = {s.method!r} is not available on sde_lib.RectifiedFlow: it needs sde() at T, which "
+                     f"is singular for this family, or a data prediction through 1 / alpha; use method = 'flow'")
   if kind == 'ode':
     if precision != 'fp32':
       raise ValueError(f"config.sampling.precision={precision!r} is not supported by the ODE sampler: RK45 at rtol = atol = "

@@ -3,7 +3,8 @@
 Interface parity with the reference ``sde_lib.py`` (file:line = /root/reference/sde_lib.py): abstract ``SDE``
 (:8-119) with ``T, sde, marginal_prob, prior_sampling, prior_logp, discretize, reverse``; ``VPSDE`` (:121-207),
 ``subVPSDE`` (:209-246), ``VESDE`` (:248-332), ``reciprocal_VESDE`` (:334-430); factory ``get_sde`` (:433-445), which
-also knows ``EDM`` (this package's own: the sigma-parametrised family of Karras et al. 2022); the
+also knows ``EDM`` (this package's own: the sigma-parametrised family of Karras et al. 2022) and ``RectifiedFlow`` (the
+straight-line interpolant with a velocity target); the
 Soft-Truncation additions ``integral_beta / antiderivative / normalizing_constant / get_diffusion_time / get_t_min``.
 
 How this file is organised (it is not laid out like the reference): the pieces several SDEs share live once, in
@@ -395,6 +396,31 @@ class EDM(_GaussianPrior, SDE):
     return self.eps
 
 
+# ---- rectified flow -------------------------------------------------------------------------------------------------
+class RectifiedFlow(_UnitHorizon, _GaussianPrior, SDE):
+  """The straight-line interpolant of rectified flow / flow matching (Liu et al. 2022; Lipman et al. 2022):
+  x_t = (1 - t) x_0 + t z on [eps, 1], so alpha(1) = 0 and the prior is N(0, I).  Not in the reference.  The network predicts
+  the velocity z - x_0 (models.utils.get_flow_model_fn); the loss is losses.get_flow_loss_fn and the sampler
+  flow.get_flow_sampler.  ``marginal_prob`` carries the dtype of `t` through.  ``sde`` is the EQUIVALENT diffusion, the one
+  with these marginals: drift -x / (1 - t) and diffusion sqrt(2 t / (1 - t)), both SINGULAR at t = T = 1 -- which is why the
+  samplers that evaluate ``sde`` at T are refused for this family (sampling.get_sampling_fn).  There is no Soft-Truncation
+  time sampling: ``get_t_min`` is ``eps``."""
+
+  def __init__(self, eps=1e-3, N=1000):
+    super().__init__(N)
+    self.eps = eps
+
+  def sde(self, x, t):
+    a = 1. - t
+    return -x / _bcast(a), torch.sqrt(2. * t / a)
+
+  def marginal_prob(self, x, t):
+    return _bcast(1. - t) * x, t
+
+  def get_t_min(self, config):
+    return self.eps
+
+
 # ---- factory --------------------------------------------------------------------------------------------------------
 def get_sde(config, state):
   """Factory keyed on ``config.training.sde`` (sde_lib.py:433-445)."""
@@ -410,4 +436,7 @@ def get_sde(config, state):
     from .models.utils import config_option
     return EDM(sigma_min=config_option(config, 'model', 'sigma_min', 0.002), sigma_max=config_option(config, 'model', 'sigma_max', 80),
                sigma_data=config_option(config, 'model', 'sigma_data', 0.5), N=config_option(config, 'model', 'num_scales', 1000))
+  if kind == 'rectified_flow':
+    from .models.utils import config_option
+    return RectifiedFlow(N=config_option(config, 'model', 'num_scales', 1000))
   raise NotImplementedError(f"SDE {config.training.sde} unknown.")
