@@ -25,6 +25,18 @@ static inline int stk_ew_grid(long work_items, int threads = 256) {
   return (int)g;
 }
 
+// Raw buffer accesses: a wave-uniform resource (base + byte count in SGPRs), a 32-bit per-lane byte offset and a scalar
+// offset.  An access whose per-lane offset lies outside the byte count returns 0 (load) or is dropped (store).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t stk_make_rsrc(const void* base, long bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float stk_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ void stk_buf_store(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 0);
+}
+
 // 64-lane wavefront reductions (wave = 64 on CDNA; never 32).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -20,6 +20,7 @@
 // fixed order into dw (deterministic -- no float atomics).
 #include "igemm.h"
 #include "split.h"
+#include "ep_range.h"
 #include "stk_fp16.h"
 #include "stk_fp16_train.h"
 
@@ -407,8 +408,34 @@ struct BWgrad {       // B(k=pixel, n=ci) = x[b, ci, oy*s + kh - pad, ox*s + kw 
 };
 
 // ---- epilogues: one 16-row strip of one output column per call, loads batched ------------------------------
+// Straight-line element code.  The first form -- `if (ok) y[idx] = v`, `if (d[u]) *d[u] = ...` -- compiled to one exec-masked
+// basic block per element with an `s_waitcnt vmcnt(0)` in front of it; stores count on the same counter as loads on this
+// target, so each of a thread's 64 output rows waited for the previous row's store to be acknowledged (and, in the forward,
+// for all sixteen residual loads at once): 113 full waits and 322 exec branches behind the halo kernel's last MFMA
+// (profiles/epilogue_isa.txt, tools/epilogue_isa.py).  Now every output store, residual load and old-gradient load is a raw
+// BUFFER access (common.h: stk_make_rsrc, stk_buf_load, stk_buf_store): a wave-uniform resource, one per-lane byte offset per strip, the row step in the scalar offset.  A row or
+// column outside the problem, or a row that belongs to the other concat source, gets the dead offset the loaders use (bit 31
+// set: the range check returns 0 for a load and drops a store), so no element needs control flow; the options (bias, temb,
+// res, use_div, beta != 0, a missing destination) are wave-uniform and are tested per strip.  An absent addend is -0.f and an
+// absent divisor 1.f: x + -0.f and x * 1.f are x for every x, so the arithmetic and its order are those of the first form.
+// The loads of a strip are issued back to back and nothing waits for a store.
+//
+// Tensors of 2 GiB or more (the host admits up to 2^31 - 1 elements): byte offsets are 32 bits wide and bit 31 is the marker,
+// so such a tensor keeps the element code with 64-bit addresses (`strip_wide`), chosen by ONE wave-uniform test per kernel
+// (stk_ep_fits_buffer, ep_range.h).  No test allocates such a tensor: inside the split kernels only the predicate is tested
+// (tests/test_ep_range_cpu.py); the element code of EpFwd / EpDgrad itself runs in every test of the f32-operand kernels
+// (strip_f32 below), the four-line fallbacks of EpSlab / EpWgrad in none.  Re-basing the resource at the tile's first image instead would not be safe for every
+// shape the host admits: one image of a wide layer on a large map can itself pass 2 GiB.
+constexpr unsigned EP_DEAD = 0x80000000u;
+// offset of element e of a strip: the strip's per-lane offset, or the dead one for a row outside [lo, hi) / a dead column
+__device__ __forceinline__ unsigned ep_voff(unsigned voff, bool nok, int mbase, int e, int lo, int hi) {
+  const int m = mbase + strip_row(e);
+  return (nok && (unsigned)(m - lo) < (unsigned)(hi - lo)) ? voff : EP_DEAD;       // lo <= hi
+}
+
+
 struct EpFwd {        // y = (acc + bias + temb + res) * inv_div
-  int b; int col_off;
+  int b; int col_off; bool wide = false;
   // Tile-level staging of the per-row addends (split kernels; conv_x2.h / conv_pl.h): a 128-row tile needs 128 bias
   // values and 128 time-embedding values per image it touches.  Fetched into registers BEFORE the main loop (their
   // latency hides under it), parked in LDS after it, read back with ds_read_b128 -- the epilogue itself then waits
@@ -416,16 +443,21 @@ struct EpFwd {        // y = (acc + bias + temb + res) * inv_div
   // four rows: sixteen dependent round trips per wave, ~20 us of a 150 us launch at K = 1152.)
   static constexpr int TEMB_IMGS = 9;                 // 128-pixel tile over maps of >= 16 pixels
   float rb; float rt[5]; int m0 = 0, b0 = 0, nimg = 0, tb = 0;
-  const float* sb = nullptr; const float* stm = nullptr;     // null: not staged (the f32-input and bf16 kernels)
+  const float* sb = nullptr; const float* stm = nullptr;     // null: stage() was not called (igemm::kernel, which takes strip_f32)
+  // per-strip addressing of y / res: one per-lane byte offset, row strip_row(e) in the scalar offset
+  struct Addr {
+    __amdgpu_buffer_rsrc_t yrs, rrs; unsigned voff, rstep; float mul;
+  };
   __device__ void preload(const ConvP& p, int m0_, int n0, int tn, int M, int Nn, int tid) {
     m0 = m0_; sb = nullptr; stm = nullptr;
     b0 = n0 / p.OHW;
     nimg = min(n0 + tn - 1, Nn - 1) / p.OHW - b0 + 1;
-    rb = (p.bias && tid < 128 && m0 + tid < M) ? p.bias[m0 + tid] : 0.f;
+    // an absent addend is staged as -0.f (x + -0.f == x for every x): the strip adds what it reads, unconditionally
+    rb = (p.bias && tid < 128 && m0 + tid < M) ? p.bias[m0 + tid] : -0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       const int idx = tid + 256 * k, img = idx >> 7, r = idx & 127;
-      rt[k] = (p.temb && nimg <= TEMB_IMGS && img < nimg && m0 + r < M) ? p.temb[(long)(b0 + img) * p.temb_stride + m0 + r] : 0.f;
+      rt[k] = (p.temb && nimg <= TEMB_IMGS && img < nimg && m0 + r < M) ? p.temb[(long)(b0 + img) * p.temb_stride + m0 + r] : -0.f;
     }
   }
   __device__ void stage(unsigned char* lds, int tid) {      // all waves are past their last operand read when they arrive
@@ -440,43 +472,97 @@ struct EpFwd {        // y = (acc + bias + temb + res) * inv_div
     __syncthreads();
     sb = s; stm = s + 128;
   }
-  __device__ void init(const ConvP&, int, int) {}
+  __device__ void init(const ConvP& p, int, int) {
+    wide = !(stk_ep_fits_buffer((long)p.N * p.Cout * p.OHW) &&
+             (!p.temb || stk_ep_fits_buffer((long)(p.N - 1) * p.temb_stride + p.Cout)));
+  }
   __device__ void finish(const ConvP&, unsigned char*, int) {}
   __device__ void col(const ConvP& p, int n) {
     b = n / p.OHW;
     col_off = b * p.Cout * p.OHW + (n - b * p.OHW);
-    tb = (b - b0) * 128;
+    tb = p.temb ? (b - b0) * 128 : 0;       // no temb: image 0's slots, which hold the staged -0.f
+  }
+  // Staged addends.  RES: the 16 residual loads go out back to back in front of the element code, which then needs only
+  // counted waits; without a residual the strip has no load at all.
+  template <bool RES>
+  __device__ __forceinline__ void staged(const Addr& a, int mbase, int M, bool nok, const floatx16& acc) {
+#pragma clang fp contract(off)              // the additions stay additions: acc * unscale is not fused into the first one
+    const int ml = mbase - m0;
+    float rv[16];
+    if constexpr (RES) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) rv[e] = stk_buf_load(a.rrs, ep_voff(a.voff, nok, mbase, e, 0, M), strip_row(e) * a.rstep);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 bb = *reinterpret_cast<const float4*>(sb + ml + 8 * g);
+      const float4 tt = *reinterpret_cast<const float4*>(stm + tb + ml + 8 * g);
+      const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = 4 * g + u;
+        float v = acc[e];
+        v += bv[u];
+        v += tv[u];
+        if constexpr (RES) v += rv[e];
+        v *= a.mul;
+        stk_buf_store(v, a.yrs, ep_voff(a.voff, nok, mbase, e, 0, M), strip_row(e) * a.rstep);
+      }
+    }
   }
   __device__ void strip(const ConvP& p, int mbase, int M, bool nok, int, const floatx16& acc) {
-    if (sb && (!p.temb || nimg <= TEMB_IMGS)) {      // staged addends (wave-uniform branch)
-      const int ml = mbase - m0;
-      float rv[16]; int idx[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = mbase + strip_row(e);
-        const bool ok = nok && m < M;
-        idx[e] = ok ? col_off + m * p.OHW : -1;
-        rv[e] = (p.res && ok) ? p.res[idx[e]] : 0.f;
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 bb = *reinterpret_cast<const float4*>(sb + ml + 8 * g);
-        const float4 tt = *reinterpret_cast<const float4*>(stm + tb + ml + 8 * g);
-        const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float v = acc[4 * g + u];
-          if (p.bias) v += bv[u];
-          if (p.temb) v += tv[u];
-          if (p.res) v += rv[4 * g + u];
-          if (p.use_div) v *= p.inv_div;
-          if (idx[4 * g + u] >= 0) p.y[idx[4 * g + u]] = v;
-        }
-      }
+#pragma clang fp contract(off)
+    if (wide) return strip_wide(p, mbase, M, nok, acc);
+    const long ybytes = (long)p.N * p.Cout * p.OHW * 4;
+    Addr a;
+    a.yrs = stk_make_rsrc(p.y, ybytes);
+    a.rrs = stk_make_rsrc(p.res, p.res ? ybytes : 0);
+    a.voff = ((unsigned)col_off + (unsigned)mbase * (unsigned)p.OHW) * 4u;
+    a.rstep = (unsigned)p.OHW * 4u;
+    a.mul = p.use_div ? p.inv_div : 1.f;
+    if (sb && (!p.temb || nimg <= TEMB_IMGS)) {      // staged addends (wave-uniform branches)
+      if (p.res) staged<true>(a, mbase, M, nok, acc);
+      else staged<false>(a, mbase, M, nok, acc);
       return;
     }
-    // 4 rows at a time: up to 12 independent loads in flight, and only a dozen live registers on top of
-    // the accumulators (a 16-row batch pushed the whole kernel to 249 VGPRs = 2 waves/SIMD).
+    // Addends not usable from LDS: a tile of the split kernels over more than TEMB_IMGS images with a temb (2 x 2 and 3 x 3
+    // maps; igemm::kernel never comes here, it takes strip_f32).  4 rows at a time,
+    // 12 independent loads in flight and only a dozen live registers on top of the accumulators (a 16-row batch pushed the
+    // whole kernel to 249 VGPRs = 2 waves/SIMD).  An absent addend costs its loads all the same -- every lane dead, the
+    // value replaced by -0.f -- and the element code no branch.
+    const __amdgpu_buffer_rsrc_t brs = stk_make_rsrc(p.bias, p.bias ? (long)p.Cout * 4 : 0);
+    const __amdgpu_buffer_rsrc_t trs = stk_make_rsrc(p.temb, p.temb ? ((long)(p.N - 1) * p.temb_stride + p.Cout) * 4 : 0);
+    const unsigned boff = (unsigned)mbase * 4u, toff = ((unsigned)b * (unsigned)p.temb_stride + (unsigned)mbase) * 4u;
+    const bool hb = p.bias != nullptr, ht = p.temb != nullptr, hr = p.res != nullptr;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float bv[4], tv[4], rv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = 4 * g + u;
+        bv[u] = stk_buf_load(brs, ep_voff(boff, nok && hb, mbase, e, 0, M), strip_row(e) * 4u);
+        tv[u] = stk_buf_load(trs, ep_voff(toff, nok && ht, mbase, e, 0, M), strip_row(e) * 4u);
+        rv[u] = stk_buf_load(a.rrs, ep_voff(a.voff, nok && hr, mbase, e, 0, M), strip_row(e) * a.rstep);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = 4 * g + u;
+        float v = acc[e];
+        v += hb ? bv[u] : -0.f;
+        v += ht ? tv[u] : -0.f;
+        v += hr ? rv[u] : -0.f;
+        v *= a.mul;
+        stk_buf_store(v, a.yrs, ep_voff(a.voff, nok, mbase, e, 0, M), strip_row(e) * a.rstep);
+      }
+    }
+  }
+  // The f32-operand kernels of igemm.h keep the element code too: their 64 x 64-tile instantiations run on 57 - 76 registers
+  // (57 - 64 with this epilogue), which the buffer strips (12 loads and three offsets live) would raise past a wave per SIMD; so those kernels compile to
+  // what they were, and this path runs in every test of theirs.
+  __device__ void strip_f32(const ConvP& p, int mbase, int M, bool nok, int, const floatx16& acc) { strip_wide(p, mbase, M, nok, acc); }
+  // the element code with 64-bit addresses: tensors whose byte offsets do not fit below bit 31 (see the head of this section)
+  __device__ void strip_wide(const ConvP& p, int mbase, int M, bool nok, const floatx16& acc) {
+#pragma clang fp contract(off)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float bv[4], tv[4], rv[4];
@@ -504,12 +590,56 @@ struct EpFwd {        // y = (acc + bias + temb + res) * inv_div
   }
 };
 struct EpDgrad {      // dx{1,2} = beta*dx + alpha*acc, rows routed to the two sources of the concat
-  int b, hw;
+  int b, hw; bool wide = false;
   __device__ void preload(const ConvP&, int, int, int, int, int, int) {}
   __device__ void stage(unsigned char*, int) {}
-  __device__ void init(const ConvP&, int, int) {}
+  __device__ void init(const ConvP& p, int, int) {
+    wide = !(stk_ep_fits_buffer((long)p.N * p.C1 * p.HW) && stk_ep_fits_buffer((long)p.N * p.C2 * p.HW));
+  }
   __device__ void col(const ConvP& p, int n) { b = n / p.HW; hw = n - b * p.HW; }
+  // The rows [lo, hi) of a strip that belong to one concat source: dst[b, m - lo, hw] = beta * old + alpha * acc, where
+  // beta * old is a product of its own and the sum one fma (as the first form compiled).  `beta` is the source's, so "no
+  // accumulation" is a wave-uniform case without loads; with it, the 16 old values are loaded back to back.
+  template <bool ACC>
+  __device__ __forceinline__ void rows_of(const ConvP& p, float* dst, int C, int lo, int hi, float beta, int mbase, bool nok,
+                                          const floatx16& acc) {
+#pragma clang fp contract(off)
+    const __amdgpu_buffer_rsrc_t rs = stk_make_rsrc(dst, (long)p.N * C * p.HW * 4);
+    // The row step is added per lane here, not passed as the scalar offset: the two destinations may meet anywhere (the plan
+    // asks nothing of C1 in this direction: 48 + 48 reaches the halo kernel), so a strip may start in front of `lo`; its own
+    // offset is then negative, and the range check -- which sees the per-lane offset alone -- would drop rows that do belong
+    // to this destination.
+    const unsigned voff = (((unsigned)b * (unsigned)C + (unsigned)(mbase - lo)) * (unsigned)p.HW + (unsigned)hw) * 4u;
+    const unsigned rstep = (unsigned)p.HW * 4u;
+    float old[16];
+    if constexpr (ACC) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) old[e] = stk_buf_load(rs, ep_voff(voff + strip_row(e) * rstep, nok, mbase, e, lo, hi), 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float o = ACC ? beta * old[e] : 0.f;
+      stk_buf_store(__builtin_fmaf(p.alpha, acc[e], o), rs, ep_voff(voff + strip_row(e) * rstep, nok, mbase, e, lo, hi), 0);
+    }
+  }
+  __device__ __forceinline__ void rows(const ConvP& p, float* dst, int C, int lo, int hi, float beta, int mbase, bool nok,
+                                       const floatx16& acc) {
+    if (beta != 0.f) rows_of<true>(p, dst, C, lo, hi, beta, mbase, nok, acc);
+    else rows_of<false>(p, dst, C, lo, hi, beta, mbase, nok, acc);
+  }
   __device__ void strip(const ConvP& p, int mbase, int M, bool nok, int, const floatx16& acc) {
+    if (wide) return strip_wide(p, mbase, M, nok, acc);
+    // a strip's 32 rows (16 per lane half) start at a multiple of 32: which sources they reach is wave-uniform, and a
+    // missing destination (dx1 / dx2 NULL) drops its rows here
+    const int sbase = __builtin_amdgcn_readfirstlane(mbase) & ~31;
+    if (p.dx1 && sbase < p.C1) rows(p, p.dx1, p.C1, 0, min(p.C1, M), p.beta1, mbase, nok, acc);
+    if (p.dx2 && sbase + 32 > p.C1 && M > p.C1) rows(p, p.dx2, p.C2, p.C1, M, p.beta2, mbase, nok, acc);
+  }
+  // the f32-operand kernels of igemm.h keep the element code (see EpFwd::strip_f32): 16 old values live at once cost
+  // their 64 x 64-tile instantiations a wave per SIMD
+  __device__ void strip_f32(const ConvP& p, int mbase, int M, bool nok, int, const floatx16& acc) { strip_wide(p, mbase, M, nok, acc); }
+  // the element code with 64-bit addresses: tensors whose byte offsets do not fit below bit 31
+  __device__ void strip_wide(const ConvP& p, int mbase, int M, bool nok, const floatx16& acc) {
     // four elements at a time (the rows of one 4-row group of the strip): 16 pointers + 16 old values live at once kept every kernel with
     // this epilogue at 155 registers where the forward's has 126
     const bool acc1 = p.beta1 != 0.f, acc2 = p.beta2 != 0.f;
@@ -543,13 +673,22 @@ struct EpWgrad {      // partial slab of split zs as [tap][Cout][Cin] (coalesced
   __device__ void init(const ConvP& p, int zb, int zs) { slab = p.part + (long)zs * p.part_stride; tap = zb; }
   __device__ void col(const ConvP&, int) {}
   __device__ void strip(const ConvP& p, int mbase, int M, bool nok, int n, const floatx16& acc) {
+    const long elems = (long)p.taps * p.Cout * p.Cin;
+    if (!stk_ep_fits_buffer(elems)) {            // wave-uniform: the element code with 64-bit addresses
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int m = mbase + strip_row(e);
-      if (nok && m < M) {
-        slab[((long)tap * p.Cout + m) * p.Cin + n] = acc[e];     // [tap][co][ci]: lanes (= ci) contiguous
+      for (int e = 0; e < 16; ++e) {
+        const int m = mbase + strip_row(e);
+        if (nok && m < M) {
+          slab[((long)tap * p.Cout + m) * p.Cin + n] = acc[e];     // [tap][co][ci]: lanes (= ci) contiguous
+        }
       }
+      return;
     }
+    const __amdgpu_buffer_rsrc_t rs = stk_make_rsrc(slab, elems * 4);
+    const unsigned voff = (((unsigned)tap * (unsigned)p.Cout + (unsigned)mbase) * (unsigned)p.Cin + (unsigned)n) * 4u;
+    const unsigned rstep = (unsigned)p.Cin * 4u;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) stk_buf_store(acc[e], rs, ep_voff(voff, nok, mbase, e, 0, M), strip_row(e) * rstep);
   }
 };
 
@@ -562,11 +701,18 @@ struct EpSlab {
   __device__ void finish(const ConvP&, unsigned char*, int) {}
   __device__ void col(const ConvP&, int) {}
   __device__ void strip(const ConvP&, int mbase, int M, bool nok, int n, const floatx16& acc) {
+    if (!stk_ep_fits_buffer((long)M * Nn)) {     // wave-uniform: the element code with 64-bit addresses
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int m = mbase + strip_row(e);
-      if (nok && m < M) slab[(long)m * Nn + n] = acc[e];
+      for (int e = 0; e < 16; ++e) {
+        const int m = mbase + strip_row(e);
+        if (nok && m < M) slab[(long)m * Nn + n] = acc[e];
+      }
+      return;
     }
+    const __amdgpu_buffer_rsrc_t rs = stk_make_rsrc(slab, (long)M * Nn * 4);
+    const unsigned voff = ((unsigned)mbase * (unsigned)Nn + (unsigned)n) * 4u, rstep = (unsigned)Nn * 4u;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) stk_buf_store(acc[e], rs, ep_voff(voff, nok, mbase, e, 0, M), strip_row(e) * rstep);
   }
 };
 // OneProduct<EP>: epilogue EP of the one-product kernels (include/stk_fp16.h, include/stk_fp16_train.h; conv_x2.h / conv_x2d.h

@@ -51,12 +51,9 @@ struct Src {             // the activation operand: channel-concat of two NCHW t
 // outside the tensor returns 0 instead of faulting, which is how halo lanes are zeroed (offset bit 31 set) and why
 // a shifted 16-pixel run may start one element before / end one element after its tensor.
 // (Buffer offsets are 32-bit: the host side keeps these kernels to tensors below 2 GB.)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
-}
+// The wrappers themselves are common.h's (stk_make_rsrc, stk_buf_load), shared with the epilogues of conv.hip.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes) { return stk_make_rsrc(base, bytes); }
+__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) { return stk_buf_load(r, voff, soff); }
 
 inline int pad128(int v) { return (v + 127) / 128 * 128; }
 

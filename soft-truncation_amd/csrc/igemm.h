@@ -85,6 +85,9 @@ struct KMajor {
 // Grid: x = tiles (XCD-remapped, m fastest), y = split-K slice, z = batch;  or, with flat_z > 0, one flat
 // x dimension of flat_z * tiles * splits blocks (see the kernel body).
 // ------------------------------------------------------------------------------------------------
+template <class EP, class = void> struct has_strip_f32 { static constexpr bool value = false; };
+template <class EP> struct has_strip_f32<EP, decltype((void)&EP::strip_f32)> { static constexpr bool value = true; };
+
 template <class C, class P, class AL, class BL, class EP>
 __global__ __launch_bounds__(256) void kernel(P p, int M, int N, int K, int tiles_m, int tiles_n, int k_per_split,
                                               int flat_z) {
@@ -172,7 +175,12 @@ __global__ __launch_bounds__(256) void kernel(P p, int M, int N, int K, int tile
     const bool nok = n < N;
     ep.col(p, nok ? n : 0);
 #pragma unroll
-    for (int i = 0; i < C::TM; ++i) ep.strip(p, m0 + wm0 + i * 32 + 4 * fk, M, nok, nok ? n : 0, acc[i][j]);
+    for (int i = 0; i < C::TM; ++i) {
+      // an epilogue may keep a leaner strip for this kernel (strip_f32): the 64 x 64 tiles live on 57 - 76 registers,
+      // and a strip that batches 16 loads would cost them a wave per SIMD
+      if constexpr (has_strip_f32<EP>::value) ep.strip_f32(p, m0 + wm0 + i * 32 + 4 * fk, M, nok, nok ? n : 0, acc[i][j]);
+      else ep.strip(p, m0 + wm0 + i * 32 + 4 * fk, M, nok, nok ? n : 0, acc[i][j]);
+    }
   }
 }
 
